@@ -163,7 +163,7 @@ def measured_stream_gbs(torch, device=0):
     return out
 
 
-def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None):
+def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None, keep_last=False):
     """`steps` runs to convergence on the staged evidence, bracketed by synchronize on both sides, with
     nothing but the run itself in the timed region.  Two clocks give the sweep launch duration:
       * the device's own 100 MHz clock, read by the kernels at the first sweep's start and the last
@@ -190,6 +190,9 @@ def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None):
         dev_ms += st["sweep_devclock_ms"]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # keep_last: what the last timed step gave its caller (beliefs copied off the device only now, outside the timed region;
+    # the event repeats below overwrite them)
+    last = {"beliefs": eng.bp_beliefs(), "sweeps": r["sweeps"], "residual": r["residual"]} if keep_last else None
     path = eng.last_path()
     eng.set_option("timing", 1)
     ev_steps = event_steps if event_steps is not None else min(steps, 20)
@@ -217,7 +220,7 @@ def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None):
     return {"dt": dt, "sweeps_total": sweeps_total, "msgs": g.messages_per_sweep() * sweeps_total,
             "avg_sweep_s": avg_sweep_s, "avg_launch_s": avg_launch_s, "sweeps_per_launch": ev_sweeps / max(launches, 1),
             "avg_sweep_devclock_s": avg_dev_s, "achieved": achieved, "stats": st,
-            "path": path, "ms_per_step_with_events": dt_ev / max(ev_steps, 1) * 1e3, "event_steps": ev_steps,
+            "path": path, "ms_per_step_with_events": dt_ev / max(ev_steps, 1) * 1e3, "event_steps": ev_steps, "last": last,
             "n_tiles": eng.layout()["n_tiles"], "cpt_bytes": 8 * len(g.cpt),
             "waves_per_block": {2: eng.info("resident_waves"), 5: 8}.get(path)}
 
@@ -832,6 +835,27 @@ def leg_grid2048(a, local_rank, torch):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this much on disk
+DUMP_SAMPLE = 1 << 21       # entries kept of a beliefs array beyond that (a fixed, seeded sample)
+
+
+def dump_outputs(dirname, last):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as float64 .npy files -- beliefs.npy (every node's
+    marginal in the flat layout bn_bp_copy_beliefs gives), sweeps.npy and residual.npy (one entry each).  A beliefs array of
+    more than DUMP_MAX_BYTES is replaced by DUMP_SAMPLE entries picked with a fixed seed, their positions in beliefs_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    bel = np.ascontiguousarray(last["beliefs"], dtype=np.float64)
+    arrays = {"sweeps": np.array([last["sweeps"]], np.float64), "residual": np.array([last["residual"]], np.float64)}
+    if bel.nbytes + 16 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(20240501).choice(bel.size, DUMP_SAMPLE, replace=False))
+        arrays["beliefs_index"] = idx.astype(np.float64)
+        bel = bel[idx]
+    arrays["beliefs"] = bel
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), arr)
+
+
 def main():
     import faulthandler
     faulthandler.enable()   # a native crash prints the Python stack on stderr instead of dying silently
@@ -852,7 +876,11 @@ def main():
                     help="headline only: skip the config2_dag / config5_lw / grid2048 / host-to-host extras")
     ap.add_argument("--no-weak", dest="no_weak", action="store_true", help="N>1: skip the weak-scaling extra")
     ap.add_argument("--no-replicas", dest="no_replicas", action="store_true", help="N>1: skip the replicated-queries extra")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="grid / dag on 1 GPU: write what the last timed step returned (beliefs, sweeps, residual) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.dump_outputs and (a.workload not in ("grid", "dag") or a.gpus != 1):
+        ap.error("--dump-outputs is implemented for --workload grid / dag with --gpus 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -945,7 +973,9 @@ def main():
     ev = synth.random_evidence(g, a.evidence, seed=7)
     eng = Engine(g, device=local_rank)
     eng.bp_set_evidence(ev)  # inputs resident in HBM before the timed region
-    t = time_bp(eng, g, a.eps, a.steps, a.warmup, torch)
+    t = time_bp(eng, g, a.eps, a.steps, a.warmup, torch, keep_last=bool(a.dump_outputs))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, t["last"])
     if label == "grid316" and t["path"] == 0:
         label = "grid316_launch"  # the profile of the same grid with one launch per sweep (BN_MULTISWEEP=0)
     if label == "dag10k" and t["path"] == 0:

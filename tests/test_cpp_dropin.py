@@ -1,10 +1,11 @@
 """The header-only C++14 drop-in (include/bayesian/inference/*.hpp) over the C ABI.
 
 CPU: the test program compiles against this repository's stand-in data model AND against the
-reference's own graph.hpp / matrix.hpp (where /root/reference exists), and the flattened networks
-equal the flat models used everywhere else.  GPU: the reference's seven BP test cases run through
-bn::inference::belief_propagation, teacher tolerances of the reference tests, and the marginals are
-bit-identical to the reference's golden outputs."""
+reference's own graph.hpp / matrix.hpp (oracle/_ref/dropin_ref, which build() compiles where the
+reference's headers are), and the flattened networks equal the flat models used everywhere else.
+GPU: the reference's seven BP test cases run through bn::inference::belief_propagation, teacher
+tolerances of the reference tests, and the marginals are bit-identical to the reference's golden
+outputs."""
 import json
 import os
 import subprocess
@@ -17,6 +18,8 @@ from helpers import load_golden
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "test_dropin.cpp")
 LIBDIR = os.path.join(ROOT, "bayesiannetwork_amd")
+REF_DROPIN = os.path.join(ROOT, "oracle", "_ref", "dropin_ref")   # (oracle/Makefile: the program over the reference's data model)
+NO_REF_DROPIN = "oracle/_ref/dropin_ref not built: the reference's headers were not there when build() ran"
 
 
 def build(tmp_path, model_include, name):
@@ -44,10 +47,10 @@ def test_flatten_with_compat_model(bnlib, tmp_path):
     check_flatten(build(tmp_path, os.path.join(ROOT, "include", "compat"), "dropin_compat"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/bayesian"), reason="reference headers not on this box")
-def test_flatten_with_reference_model(bnlib, tmp_path):
+@pytest.mark.skipif(not os.path.exists(REF_DROPIN), reason=NO_REF_DROPIN)
+def test_flatten_with_reference_model(bnlib):
     """True drop-in: the user's include path is the reference's; only bayesian/inference is ours."""
-    check_flatten(build(tmp_path, "/root/reference", "dropin_ref"))
+    check_flatten(REF_DROPIN)
 
 
 def check_dsc_flatten(exe):
@@ -65,9 +68,9 @@ def test_dsc_loader_compat_equals_reference_golden(bnlib, tmp_path):
     check_dsc_flatten(build(tmp_path, os.path.join(ROOT, "include", "compat"), "dropin_compat_dsc"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/bayesian"), reason="reference headers not on this box")
-def test_dsc_loader_reference_with_dropin_headers(bnlib, tmp_path):
-    check_dsc_flatten(build(tmp_path, "/root/reference", "dropin_ref_dsc"))
+@pytest.mark.skipif(not os.path.exists(REF_DROPIN), reason=NO_REF_DROPIN)
+def test_dsc_loader_reference_with_dropin_headers(bnlib):
+    check_dsc_flatten(REF_DROPIN)
 
 
 @pytest.mark.gpu
