@@ -108,6 +108,14 @@ SYMBOLS = [
     ("bn_layout_node_slots", ctypes.c_int, [ctypes.c_void_p, i32p]),
     ("bn_layout_node_tiles", ctypes.c_int, [ctypes.c_void_p, i32p]),
     ("bn_layout_class", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, i32p, i32p]),
+    ("bn_info_create", ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, u8p, ctypes.POINTER(ctypes.c_uint64), i32p, ctypes.c_int32,
+                                      ctypes.POINTER(ctypes.c_void_p)]),
+    ("bn_info_destroy", None, [ctypes.c_void_p]),
+    ("bn_info_entropy", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, ctypes.c_int32, f64p]),
+    ("bn_info_pair_entropies", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, f64p, f64p, f64p]),
+    ("bn_info_pair_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_info_last_pairs_ms", ctypes.c_int, [ctypes.c_void_p, f64p]),
+    ("bn_info_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, i64p]),
 ]
 
 

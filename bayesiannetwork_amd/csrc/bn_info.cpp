@@ -1,0 +1,339 @@
+// bn_info.cpp -- C ABI of the entropy / mutual-information table (include/bn_mi355x.h, bn_info_*),
+// reference bayesian/evaluation/transinformation.hpp.  Kernels: bn_info_kernels.hip.
+#include <cmath>
+#include <memory>
+
+#include "bn_engine_internal.hpp"
+#include "bn_info.hpp"
+#include "../../include/bn_mi355x.h"
+
+struct bn_info_table {
+    int device = 0;
+    int32_t n = 0;
+    int64_t P = 0, Ppad = 0;
+    int32_t D = 1;
+    std::vector<int32_t> k;
+    double Nd = 0.0;
+    hipStream_t stream = nullptr;
+    uint8_t* d_T = nullptr;
+    unsigned long long* d_w = nullptr;
+    uint8_t* d_wd = nullptr;
+    float last_pairs_ms = 0.0f;
+
+    InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
+    ~bn_info_table() {
+        DeviceGuard g;
+        (void)g.enter(device);
+        void* ptrs[] = {d_T, d_w, d_wd};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+int slot_width(int32_t k) {
+    int w = 2;
+    while (w < k) w <<= 1;
+    return w;
+}
+
+// canonical set: sorted, duplicates dropped, arity-1 columns dropped (their only state adds no key digit)
+int make_set(const bn_info_table* t, int32_t nv, const int32_t* vars, InfoSet& s, uint64_t& cells, int& key_bits) {
+    if (nv < 0 || (nv > 0 && !vars)) return fail(BN_ERR_ARG, "bad variable list");
+    std::vector<int32_t> v(vars, vars + nv);
+    for (int32_t x : v)
+        if (x < 0 || x >= t->n) return fail(BN_ERR_ARG, "variable index out of range");
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    s.nv = 0;
+    unsigned __int128 prod = 1;
+    for (int32_t x : v) {
+        if (t->k[x] < 2) continue;
+        prod *= unsigned(t->k[x]);
+        if (prod > (unsigned __int128)1 << 64)
+            return fail(BN_ERR_ARG, "the joint key of the set needs more than 64 bits (product of the arities > 2^64)");
+        s.col[s.nv] = x;
+        s.k[s.nv] = t->k[x];
+        ++s.nv;   // (<= 64 columns of arity >= 2 before the product passes 2^64)
+    }
+    cells = prod == (unsigned __int128)1 << 64 ? 0 : uint64_t(prod);   // 0: the full 64-bit key space
+    key_bits = 0;
+    while (key_bits < 64 && (cells == 0 || (uint64_t(1) << key_bits) < cells)) ++key_bits;
+    return BN_OK;
+}
+
+int run_entropy(bn_info_table* t, const InfoSet& s, uint64_t cells, int key_bits, int route, double* h, unsigned long long* cells_out) {
+    if (route == 0) route = (cells != 0 && cells <= kInfoDenseMaxCells) ? 1 : 2;
+    if (route == 1 && (cells == 0 || cells > kInfoDenseMaxCells))
+        return fail(BN_ERR_ARG, "dense route: the set has more than 2^22 cells");
+    if (s.nv == 0) {   // every column of arity 1 (or none): one cell holding every sample
+        *h = 0.0;
+        return BN_OK;
+    }
+    const int e = info_entropy_run(t->dev(), s, route, cells, key_bits < 1 ? 1 : key_bits, t->Nd, h, cells_out, t->stream);
+    if (e) return fail(BN_ERR_HIP, std::string("entropy kernels: ") + hipGetErrorString(hipError_t(e)));
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" int bn_info_create(int64_t n_patterns, int32_t n_vars, const uint8_t* patterns, const uint64_t* counts,
+                              const int32_t* k, int32_t device, bn_info_table** out) {
+    if (!out) return fail(BN_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (n_vars <= 0 || n_vars > (1 << 23)) return fail(BN_ERR_ARG, "n_vars must be in 1..2^23");
+    if (n_patterns < 0) return fail(BN_ERR_ARG, "bad pattern table (n_patterns < 0)");
+    if (!k) return fail(BN_ERR_ARG, "null arity array");
+    if (n_patterns > 0 && (!patterns || !counts)) return fail(BN_ERR_ARG, "bad pattern table");
+    for (int32_t v = 0; v < n_vars; ++v)
+        if (k[v] < 1 || k[v] > 255) return fail(BN_ERR_ARG, "arity must be in 1..255");
+    uint64_t total = 0, maxc = 0;
+    for (int64_t i = 0; i < n_patterns; ++i) {
+        if (counts[i] > ~total) return fail(BN_ERR_ARG, "the total count does not fit in 64 bits");
+        total += counts[i];
+        maxc = std::max<uint64_t>(maxc, counts[i]);
+    }
+    if (total == 0) return fail(BN_ERR_ARG, "empty sample table (sampling_size() == 0)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(BN_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device >= ndev || device < BN_DEVICE_CURRENT) return fail(BN_ERR_ARG, "device ordinal out of range");
+    if (device == BN_DEVICE_CURRENT) HIPCHK(hipGetDevice(&device));
+    DeviceGuard guard;
+    HIPCHK(guard.enter(device));
+
+    std::unique_ptr<bn_info_table> t(new (std::nothrow) bn_info_table);
+    if (!t) return fail(BN_ERR_ALLOC, "host allocation failed");
+    t->device = device;
+    t->n = n_vars;
+    t->P = n_patterns;
+    t->Ppad = std::max<int64_t>((n_patterns + kInfoPatternAlign - 1) / kInfoPatternAlign * kInfoPatternAlign, kInfoPatternAlign);
+    t->k.assign(k, k + n_vars);
+    t->Nd = double(total);
+    int bits = 0;
+    while (bits < 64 && (maxc >> bits)) ++bits;
+    t->D = std::max(1, (bits + 6) / 7);
+    HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    uint8_t* d_raw = nullptr;
+    int32_t* d_k = nullptr;
+    unsigned* d_bad = nullptr;
+    unsigned bad = 0;
+    int rc = [&]() -> int {
+        const size_t raw_bytes = size_t(n_patterns) * size_t(n_vars);
+        if (int r = dalloc(&d_raw, raw_bytes)) return r;
+        if (int r = dalloc(&t->d_T, size_t(n_vars) * size_t(t->Ppad))) return r;
+        if (int r = dalloc(&t->d_w, size_t(n_patterns))) return r;
+        if (int r = dalloc(&t->d_wd, size_t(t->D) * size_t(t->Ppad))) return r;
+        if (int r = upload(&d_k, t->k, t->stream)) return r;
+        if (int r = dalloc(&d_bad, 1)) return r;
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, t->stream));
+        if (raw_bytes) HIPCHK(hipMemcpyAsync(d_raw, patterns, raw_bytes, hipMemcpyHostToDevice, t->stream));
+        if (n_patterns) HIPCHK(hipMemcpyAsync(t->d_w, counts, size_t(n_patterns) * 8, hipMemcpyHostToDevice, t->stream));
+        int e = info_launch_transpose(d_raw, n_patterns, n_vars, t->Ppad, d_k, t->d_T, d_bad, t->stream);
+        if (!e) e = info_launch_digits(t->d_w, n_patterns, t->Ppad, t->D, t->d_wd, t->stream);
+        if (e) return fail(BN_ERR_HIP, std::string("table kernels: ") + hipGetErrorString(hipError_t(e)));
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+        return BN_OK;
+    }();
+    void* ptrs[] = {d_raw, d_k, d_bad};
+    for (void* q : ptrs)
+        if (q) (void)hipFree(q);
+    if (rc) return rc;
+    if (bad) return fail(BN_ERR_ARG, "pattern state out of range (a state >= its column's arity)");
+    *out = t.release();
+    return BN_OK;
+}
+
+extern "C" void bn_info_destroy(bn_info_table* t) { delete t; }
+
+extern "C" int bn_info_entropy(bn_info_table* t, int32_t n_set, const int32_t* set, int32_t route, double* h_out) {
+    if (!t || !h_out) return fail(BN_ERR_ARG, "null argument");
+    if (route < 0 || route > 2) return fail(BN_ERR_ARG, "route: 0 automatic, 1 dense cells, 2 sorted keys");
+    InfoSet s{};
+    uint64_t cells = 0;
+    int key_bits = 0;
+    if (int r = make_set(t, n_set, set, s, cells, key_bits)) return r;
+    ON_DEVICE(t);
+    return run_entropy(t, s, cells, key_bits, route, h_out, nullptr);
+}
+
+namespace {
+
+// The all-pairs kernel over the columns `vars` of arity <= 32, the dense route for every pair with a wider
+// column.  hxy [m][m] and h [m] on the host; dump_off / dump: the pair blocks pair_counts asks for.
+int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, double* hxy, const std::vector<int64_t>* dump_off,
+              unsigned long long* dump_host, size_t dump_len) {
+    // slots: widths 32, 16, 8, 4, 2 in that order (stable in the caller's order), so each starts aligned
+    std::vector<int32_t> order;
+    std::vector<int32_t> wide;
+    for (int w = 32; w >= 2; w >>= 1)
+        for (int32_t u = 0; u < m; ++u)
+            if (t->k[vars[u]] <= 32 && slot_width(t->k[vars[u]]) == w) order.push_back(u);
+    for (int32_t u = 0; u < m; ++u)
+        if (t->k[vars[u]] > 32) wide.push_back(u);
+    std::vector<int32_t> sv_start, sv_k, sv_col, sv_user;
+    int64_t K = 0;
+    for (int32_t u : order) {
+        sv_start.push_back(int32_t(K));
+        sv_k.push_back(t->k[vars[u]]);
+        sv_col.push_back(vars[u]);
+        sv_user.push_back(u);
+        K += slot_width(t->k[vars[u]]);
+    }
+    const int64_t Kpad = (K + kInfoTile - 1) / kInfoTile * kInfoTile;
+    if (Kpad > (int64_t(1) << 20)) return fail(BN_ERR_ARG, "more than 2^20 slot columns in one all-pairs call");
+    std::vector<int32_t> colinfo(size_t(Kpad), 255), colvar(size_t(Kpad), -1);   // padding: column 0, state 255 (never a state)
+    for (size_t v = 0; v < sv_start.size(); ++v)
+        for (int32_t st = 0; st < slot_width(sv_k[v]); ++st) {
+            const size_t c = size_t(sv_start[v] + st);
+            colvar[c] = int32_t(v);
+            colinfo[c] = st < sv_k[v] ? (sv_col[v] << 8) | st : 255;
+        }
+    for (size_t i = 0; i < size_t(m) * size_t(m); ++i) hxy[i] = 0.0;
+    t->last_pairs_ms = 0.0f;
+    if (Kpad > 0) {
+        int32_t *d_ci = nullptr, *d_cv = nullptr, *d_ss = nullptr, *d_sk = nullptr, *d_sc = nullptr, *d_su = nullptr;
+        double *d_hxy = nullptr, *d_h = nullptr;
+        int64_t* d_off = nullptr;
+        unsigned long long* d_dump = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        int rc = [&]() -> int {
+            int r;
+            if ((r = upload(&d_ci, colinfo, t->stream)) || (r = upload(&d_cv, colvar, t->stream)) || (r = upload(&d_ss, sv_start, t->stream)) ||
+                (r = upload(&d_sk, sv_k, t->stream)) || (r = upload(&d_sc, sv_col, t->stream)) || (r = upload(&d_su, sv_user, t->stream)))
+                return r;
+            if ((r = dalloc(&d_hxy, size_t(m) * size_t(m))) || (r = dalloc(&d_h, size_t(m)))) return r;
+            HIPCHK(hipMemsetAsync(d_hxy, 0, size_t(m) * size_t(m) * 8, t->stream));
+            if (dump_off) {
+                if ((r = upload(&d_off, *dump_off, t->stream)) || (r = dalloc(&d_dump, dump_len))) return r;
+                HIPCHK(hipMemsetAsync(d_dump, 0, std::max<size_t>(dump_len, 1) * 8, t->stream));
+            }
+            HIPCHK(hipEventCreate(&ev0));
+            HIPCHK(hipEventCreate(&ev1));
+            PairArgs a{t->d_T, t->Ppad, t->d_wd, t->D, int32_t(Kpad / kInfoTile), d_ci, d_cv, d_ss, d_sk, d_sc, d_su, m, t->Nd,
+                       d_hxy, d_h, d_off, d_dump};
+            const bool flush = t->D > 1 || t->Ppad > kInfoSegment;
+            HIPCHK(hipEventRecord(ev0, t->stream));
+            if (int e = info_launch_pairs(a, flush, t->stream))
+                return fail(BN_ERR_HIP, std::string("all-pairs kernel: ") + hipGetErrorString(hipError_t(e)));
+            HIPCHK(hipEventRecord(ev1, t->stream));
+            HIPCHK(hipMemcpyAsync(hxy, d_hxy, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
+            std::vector<double> hs(static_cast<size_t>(m));
+            HIPCHK(hipMemcpyAsync(hs.data(), d_h, size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
+            if (dump_off) HIPCHK(hipMemcpyAsync(dump_host, d_dump, dump_len * 8, hipMemcpyDeviceToHost, t->stream));
+            HIPCHK(hipStreamSynchronize(t->stream));
+            HIPCHK(hipEventElapsedTime(&t->last_pairs_ms, ev0, ev1));
+            for (int32_t u : order) h[u] = hs[size_t(u)];
+            return BN_OK;
+        }();
+        void* ptrs[] = {d_ci, d_cv, d_ss, d_sk, d_sc, d_su, d_hxy, d_h, d_off, d_dump};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (rc) return rc;
+    }
+    // pairs with a column of arity > 32: one dense joint table each (the single call's route, so its bits)
+    for (int32_t x : wide)
+        for (int32_t y = 0; y < m; ++y) {
+            if (t->k[vars[y]] > 32 && y < x) continue;   // (done as (y, x))
+            const int32_t pair[2] = {vars[x], vars[y]};
+            InfoSet s{};
+            uint64_t cells = 0;
+            int key_bits = 0;
+            if (int r = make_set(t, 2, pair, s, cells, key_bits)) return r;
+            std::vector<unsigned long long> c;
+            const int64_t o = dump_off ? (*dump_off)[size_t(x) * m + y] : -1, o2 = dump_off ? (*dump_off)[size_t(y) * m + x] : -1;
+            if (o >= 0 || o2 >= 0) c.assign(size_t(cells), 0);
+            double H = 0.0;
+            if (int r = run_entropy(t, s, cells, key_bits, 1, &H, c.empty() ? nullptr : c.data())) return r;
+            hxy[size_t(x) * m + y] = hxy[size_t(y) * m + x] = H;
+            if (x == y) h[x] = H;
+            if (c.empty()) continue;
+            // c is in key order: the smaller column the row; a column of arity 1 has no key digit
+            const int32_t kx = t->k[vars[x]], ky = t->k[vars[y]];
+            const bool x_major = vars[x] <= vars[y];
+            for (int32_t i = 0; i < kx; ++i)
+                for (int32_t j = 0; j < ky; ++j) {
+                    unsigned long long v;
+                    if (vars[x] == vars[y]) v = i == j ? c[size_t(i)] : 0;
+                    else v = x_major ? c[size_t(i) * ky + j] : c[size_t(j) * kx + i];
+                    if (o >= 0) dump_host[o + i * ky + j] = v;
+                    if (o2 >= 0 && x != y) dump_host[o2 + j * kx + i] = v;
+                }
+        }
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" int bn_info_pair_entropies(bn_info_table* t, int32_t m, const int32_t* vars, double* h_out, double* hxy_out, double* mi_out) {
+    if (!t || !h_out || !hxy_out) return fail(BN_ERR_ARG, "null argument");
+    std::vector<int32_t> all;
+    if (!vars) {
+        if (m != t->n) return fail(BN_ERR_ARG, "vars == NULL selects every column: m must equal n_vars");
+        all.resize(size_t(m));
+        for (int32_t v = 0; v < m; ++v) all[size_t(v)] = v;
+        vars = all.data();
+    }
+    if (m <= 0) return fail(BN_ERR_ARG, "m must be > 0");
+    for (int32_t u = 0; u < m; ++u)
+        if (vars[u] < 0 || vars[u] >= t->n) return fail(BN_ERR_ARG, "variable index out of range");
+    ON_DEVICE(t);
+    if (int r = all_pairs(t, m, vars, h_out, hxy_out, nullptr, nullptr, 0)) return r;
+    if (mi_out)   // transinformation.hpp:60 / :80: x_ent + y_ent - xy_ent
+        for (int32_t x = 0; x < m; ++x)
+            for (int32_t y = 0; y < m; ++y) mi_out[size_t(x) * m + y] = h_out[x] + h_out[y] - hxy_out[size_t(x) * m + y];
+    return BN_OK;
+}
+
+extern "C" int bn_info_pair_counts(bn_info_table* t, int32_t n_pairs, const int32_t* pairs, uint64_t* counts_out) {
+    if (!t || !counts_out || n_pairs <= 0 || !pairs) return fail(BN_ERR_ARG, "null argument or n_pairs <= 0");
+    std::vector<int32_t> uniq;
+    for (int32_t i = 0; i < 2 * n_pairs; ++i) {
+        if (pairs[i] < 0 || pairs[i] >= t->n) return fail(BN_ERR_ARG, "variable index out of range");
+        uniq.push_back(pairs[i]);
+    }
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const int32_t m = int32_t(uniq.size());
+    auto pos = [&](int32_t v) { return int32_t(std::lower_bound(uniq.begin(), uniq.end(), v) - uniq.begin()); };
+    std::vector<int64_t> off(size_t(m) * m, -1), where(static_cast<size_t>(n_pairs));
+    int64_t len = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const int32_t x = pos(pairs[2 * i]), y = pos(pairs[2 * i + 1]);
+        int64_t& o = off[size_t(x) * m + y];
+        if (o < 0) { o = len; len += int64_t(t->k[pairs[2 * i]]) * t->k[pairs[2 * i + 1]]; }
+        where[size_t(i)] = o;
+    }
+    std::vector<unsigned long long> dump(size_t(std::max<int64_t>(len, 1)));
+    std::vector<double> h(static_cast<size_t>(m)), hxy(size_t(m) * m);
+    ON_DEVICE(t);
+    if (int r = all_pairs(t, m, uniq.data(), h.data(), hxy.data(), &off, dump.data(), size_t(len))) return r;
+    uint64_t* o = counts_out;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const size_t cells = size_t(t->k[pairs[2 * i]]) * size_t(t->k[pairs[2 * i + 1]]);
+        std::copy(dump.begin() + where[size_t(i)], dump.begin() + where[size_t(i)] + int64_t(cells), o);
+        o += cells;
+    }
+    return BN_OK;
+}
+
+extern "C" int bn_info_last_pairs_ms(const bn_info_table* t, double* ms_out) {
+    if (!t || !ms_out) return fail(BN_ERR_ARG, "null argument");
+    *ms_out = double(t->last_pairs_ms);
+    return BN_OK;
+}
+
+extern "C" int bn_info_get(const bn_info_table* t, const char* name, int64_t* value_out) {
+    if (!t || !name || !value_out) return fail(BN_ERR_ARG, "null argument");
+    const std::string s(name);
+    if (s == "n_vars") *value_out = t->n;
+    else if (s == "n_patterns") *value_out = t->P;
+    else if (s == "digit_passes") *value_out = t->D;
+    else return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes)");
+    return BN_OK;
+}

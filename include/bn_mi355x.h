@@ -336,6 +336,40 @@ int bn_fit_cpt(const bn_model_desc *structure, int64_t n_patterns, const uint8_t
 /* Sampled states of the first `n` samples of the last bn_lw_run, sample-major [s][node]. */
 int bn_lw_states(bn_engine *eng, uint64_t n, uint8_t *states_out, double *weights_out);
 
+/* ---- entropy and mutual information over a pattern table ----
+ * Replaces: bn::evaluation::entropy / mutual_information (bayesian/evaluation/transinformation.hpp:10-84),
+ * which the reference declares but cannot compile (entropy::operator() calls lower_bound / key_comp on an
+ * unordered_map, :26-27).
+ *   bn_info_create: uploads a table once -- patterns [n_patterns][n_vars] states, counts [n_patterns]
+ *   occurrences (any uint64 whose total fits in 64 bits), k [n_vars] arities in 1..255 -- and transposes
+ *   it on the device.  Null pointers, arity, n_vars <= 0, n_patterns < 0 and a zero total: BN_ERR_ARG; no
+ *   device: BN_ERR_NO_DEVICE; a state >= its arity (checked on the device): BN_ERR_ARG, nothing kept.
+ *   bn_info_entropy: joint entropy of a set of columns (sorted, duplicates dropped),
+ *   H = -sum over non-zero cells of (c/N) log2(c/N), fp64, N the total count (:35-39).  The cells are summed
+ *   in a fixed order (increasing mixed-radix key, the smallest column the most significant digit, in chunks
+ *   of 4096 keys), so H does not depend on the order of the patterns.  route 0: automatic, 1: dense cells
+ *   (product of the arities <= 2^22), 2: sort on the packed key.  A key over 64 bits (product of the
+ *   arities > 2^64): BN_ERR_ARG.
+ *   bn_info_pair_entropies: for m columns (vars == NULL: every column, m == n_vars) h [m], hxy [m][m] and,
+ *   if mi_out is not NULL, mi [m][m] = h[x] + h[y] - hxy[x][y] (:60, :80; no clamping).  hxy is symmetric
+ *   bit for bit, its diagonal is h, and every entry has the bits of bn_info_entropy({x, y}).  Columns of
+ *   arity <= 32 go through one all-pairs int8 matrix-core kernel; pairs with a wider column through the
+ *   dense route of a single call.
+ *   bn_info_pair_counts: the exact joint counts of n_pairs pairs (pairs [n_pairs][2]) as the all-pairs
+ *   computation made them: for pair i a k_x x k_y block, x the row, blocks back to back in counts_out.
+ *   bn_info_last_pairs_ms: device time of the all-pairs kernel of the last pair call (0 if none ran).
+ *   bn_info_get: "n_vars", "n_patterns", "digit_passes" (7-bit passes over the counts). */
+typedef struct bn_info_table bn_info_table;
+int bn_info_create(int64_t n_patterns, int32_t n_vars, const uint8_t *patterns, const uint64_t *counts,
+                   const int32_t *k, int32_t device, bn_info_table **out);
+void bn_info_destroy(bn_info_table *table);
+int bn_info_entropy(bn_info_table *table, int32_t n_set, const int32_t *set, int32_t route, double *h_out);
+int bn_info_pair_entropies(bn_info_table *table, int32_t m, const int32_t *vars, double *h_out, double *hxy_out,
+                           double *mi_out);
+int bn_info_pair_counts(bn_info_table *table, int32_t n_pairs, const int32_t *pairs, uint64_t *counts_out);
+int bn_info_last_pairs_ms(const bn_info_table *table, double *ms_out);
+int bn_info_get(const bn_info_table *table, const char *name, int64_t *value_out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
