@@ -84,40 +84,20 @@ void park_stream(int device, hipStream_t s) {
 void bn_eng::free_engine(bn_engine* e) {
     if (!e) return;
     if (e->dense) { free_engine(e->dense); e->dense = nullptr; }
-    if (!e->host_only) {
-        DeviceGuard guard;
-        (void)guard.enter(e->device);
-        lw_free(e->lw);
-        for (void* q : e->ipc_opened) (void)hipIpcCloseMemHandle(q);
-        if (e->d_peers) (void)hipFree(e->d_peers);
-        if (e->d_pub_mask) (void)hipFree(e->d_pub_mask);
-        if (e->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(e->comm);
-        if (e->ev_swept) (void)hipEventDestroy(e->ev_swept);
-        if (e->ev_gathered) (void)hipEventDestroy(e->ev_gathered);
-        if (e->comm_stream) (void)hipStreamDestroy(e->comm_stream);
-        void* ptrs[] = {e->d_tiles, e->d_classes, e->d_flat_tab, e->d_cpt, e->d_rec[0], e->d_rec[1], e->d_node[0], e->d_node[1],
-                        e->d_out, e->d_frozen, e->d_slot_node, e->d_slot_boff, e->d_node_tile, e->d_node_nl,
-                        e->d_inrefs, e->d_res_hist, e->d_ctl, e->d_beliefs, e->d_ev, e->d_rsync, e->d_flow, e->d_nbr,
-                        e->d_s_ent, e->d_s_cpt, e->d_s_term, e->d_s_clist, e->d_s_bslot, e->d_s_cslot, e->d_s_nvidx, e->d_s_nvslot, e->d_s_init, e->d_s_state, e->d_s_nodeoff,
-                        e->d_m_parts, e->d_m_ent, e->d_m_cpt, e->d_m_term, e->d_m_clist, e->d_m_bslot, e->d_m_cslot, e->d_m_nvidx, e->d_m_nvslot,
-                        e->d_m_init, e->d_m_nodeoff, e->d_m_msgfirst, e->d_m_state, e->d_m_frz, e->d_m_sync,
-                        e->d_g_tiles, e->d_g_slotptr, e->d_g_cnode, e->d_g_pitem, e->d_g_oedge, e->d_g_eperm, e->d_g_nperm, e->d_g_cpt, e->d_g_init, e->d_g_state, e->d_g_frz, e->d_g_sync, e->d_g_k, e->d_g_inptr, e->d_g_inidx, e->d_g_noff, e->d_g_nbr, e->d_g_flow,
-                        e->batch.d_rec[0], e->batch.d_rec[1], e->batch.d_node[0], e->batch.d_node[1], e->batch.d_frozen,
-                        e->batch.d_beliefs, e->batch.d_res_hist, e->batch.d_sync, e->batch.d_ev, e->batch.d_ctl, e->batch.d_s_state,
-                        e->batch.d_g_state, e->batch.d_g_frz, e->batch.d_g_sync};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        if (e->h_ctl) (void)hipHostFree(e->h_ctl);
-        if (e->h_abort) (void)hipHostFree(e->h_abort);
-        if (e->batch.h_ctl) (void)hipHostFree(e->batch.h_ctl);
-        if (e->batch.h_ev) (void)hipHostFree(e->batch.h_ev);
-        if (e->batch.h_beliefs) (void)hipHostFree(e->batch.h_beliefs);
-        if (e->h_ev) (void)hipHostFree(e->h_ev);
-        if (e->h_beliefs) (void)hipHostFree(e->h_beliefs);
-        for (hipEvent_t ev : e->events) (void)hipEventDestroy(ev);
-        if (e->stream) park_stream(e->device, e->stream);
-    }
-    delete e;
+    if (e->host_only) { delete e; return; }
+    DeviceGuard guard;   // (the buffers' owners free on the current device: `delete e` stays inside the guard)
+    (void)guard.enter(e->device);
+    e->lw = LwState();
+    for (void* q : e->ipc_opened) (void)hipIpcCloseMemHandle(q);
+    if (e->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(e->comm);
+    if (e->ev_swept) (void)hipEventDestroy(e->ev_swept);
+    if (e->ev_gathered) (void)hipEventDestroy(e->ev_gathered);
+    if (e->comm_stream) (void)hipStreamDestroy(e->comm_stream);
+    for (hipEvent_t ev : e->events) (void)hipEventDestroy(ev);
+    const int device = e->device;
+    hipStream_t stream = e->stream;
+    delete e;   // device and page-locked memory
+    if (stream) park_stream(device, stream);
 }
 
 extern "C" const char* bn_last_error(void) { return g_err.c_str(); }
@@ -138,14 +118,11 @@ int bn_eng::mid_reserve_slots(bn_engine* e, int32_t slots) {
     if (slots <= e->mid_slots) return BN_OK;
     const SmallPlan& g0 = e->mid.parts[0];
     if (e->stream) HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_m_state) (void)hipFree(e->d_m_state);
-    if (e->d_m_frz) (void)hipFree(e->d_m_frz);
-    if (e->d_m_sync) (void)hipFree(e->d_m_sync);
-    e->d_m_state = nullptr; e->d_m_frz = nullptr; e->d_m_sync = nullptr; e->mid_slots = 0;
+    e->d_m_state.reset(); e->d_m_frz.reset(); e->d_m_sync.reset(); e->mid_slots = 0;
     int r;
-    if ((r = dalloc(&e->d_m_state, size_t(slots) * size_t(4 * g0.M + 4 * g0.N)))) return r;
-    if ((r = dalloc(&e->d_m_frz, size_t(slots) * size_t(g0.N)))) return r;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_m_sync), size_t(slots) * kMidSyncBytes));
+    if ((r = dalloc(e->d_m_state, size_t(slots) * size_t(4 * g0.M + 4 * g0.N)))) return r;
+    if ((r = dalloc(e->d_m_frz, size_t(slots) * size_t(g0.N)))) return r;
+    HIPCHK(dev_malloc(e->d_m_sync, size_t(slots) * kMidSyncBytes));
     e->mid_slots = slots;
     return BN_OK;
 }
@@ -155,69 +132,70 @@ int bn_eng::mid_reserve_slots(bn_engine* e, int32_t slots) {
 // are the default, the image alone is 51 MB and 140 ms of host work nobody asked for (missing #5).
 int bn_eng::ensure_dag(bn_engine* e) {
     if (!e->dag.ok) return fail(BN_ERR_STATE, "not eligible for the register-resident DAG path: " + (e->dag.why.empty() ? std::string("disabled") : e->dag.why));
-    if (e->dag.light) {
+    // Everything is built into locals and moved into the engine once the last fallible step has returned: a failure leaves the
+    // light plan (or the full plan with its own tables), no image and dag_ready false, and a later call starts over.
+    // (Declared before `img`: on a failure the image's frees wait for the device before the copies' sources go.)
+    DagPlan full;
+    DagDeviceTables tables;
+    const bool build = e->dag.light;
+    if (build) {
         try {
-            DagPlan full;
             build_dag_plan(e->plan, e->dag_cap, full, false);
             if (!full.ok || full.tiles.size() != e->dag.tiles.size() || full.blocks != e->dag.blocks || full.slot_ptr != e->dag.slot_ptr)
                 return fail(BN_ERR_STATE, "the register-resident DAG plan changed between its light and its full build");
-            e->dag = std::move(full);
-            build_dag_device_tables(e->dag, e->dag_tables);
+            build_dag_device_tables(full, tables);
         } catch (const std::bad_alloc&) {
             return fail(BN_ERR_ALLOC, "out of host memory while building the register-resident DAG plan");
+        }
+        if (e->host_only) {
+            e->dag = std::move(full);
+            e->dag_tables = std::move(tables);
         }
     }
     if (e->host_only || e->dag_ready) return BN_OK;
     ON_DEVICE(e);
     const Plan& p = e->plan;
-    const DagPlan& dp = e->dag;
+    const DagPlan& dp = build ? full : e->dag;
+    const DagDeviceTables& dt = build ? tables : e->dag_tables;
+    DagImage img;
     int r2;
-    {   // (an earlier attempt that failed half-way -- out of device memory -- must not leak what it had got)
-        void** mine[] = {reinterpret_cast<void**>(&e->d_g_slotptr), reinterpret_cast<void**>(&e->d_g_tiles), reinterpret_cast<void**>(&e->d_g_cnode),
-                         reinterpret_cast<void**>(&e->d_g_pitem), reinterpret_cast<void**>(&e->d_g_oedge), reinterpret_cast<void**>(&e->d_g_eperm),
-                         reinterpret_cast<void**>(&e->d_g_nperm), reinterpret_cast<void**>(&e->d_g_cpt), reinterpret_cast<void**>(&e->d_g_init),
-                         reinterpret_cast<void**>(&e->d_g_k), reinterpret_cast<void**>(&e->d_g_inptr), reinterpret_cast<void**>(&e->d_g_inidx),
-                         reinterpret_cast<void**>(&e->d_g_noff), reinterpret_cast<void**>(&e->d_g_state), reinterpret_cast<void**>(&e->d_g_frz),
-                         reinterpret_cast<void**>(&e->d_g_sync), reinterpret_cast<void**>(&e->d_g_nbr), reinterpret_cast<void**>(&e->d_g_flow)};
-        for (void** q : mine)
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-    }
-    if ((r2 = upload(&e->d_g_slotptr, dp.slot_ptr, e->stream))) return r2;
-    {
-        const DagDeviceTables& dt = e->dag_tables;
-        if ((r2 = upload(&e->d_g_tiles, dt.tiles, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_cnode, dp.cnode, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_pitem, dt.pitem, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_oedge, dt.oedge, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_eperm, dt.eperm, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_nperm, dt.nperm, e->stream))) return r2;
-    }
-    if ((r2 = upload(&e->d_g_cpt, dp.cpt_img, e->stream))) return r2;
-    if ((r2 = upload(&e->d_g_init, dp.npi_init, e->stream))) return r2;
+    if ((r2 = upload(img.slotptr, dp.slot_ptr, e->stream))) return r2;
+    if ((r2 = upload(img.tiles, dt.tiles, e->stream))) return r2;
+    if ((r2 = upload(img.cnode, dp.cnode, e->stream))) return r2;
+    if ((r2 = upload(img.pitem, dt.pitem, e->stream))) return r2;
+    if ((r2 = upload(img.oedge, dt.oedge, e->stream))) return r2;
+    if ((r2 = upload(img.eperm, dt.eperm, e->stream))) return r2;
+    if ((r2 = upload(img.nperm, dt.nperm, e->stream))) return r2;
+    if ((r2 = upload(img.cpt, dp.cpt_img, e->stream))) return r2;
+    if ((r2 = upload(img.init, dp.npi_init, e->stream))) return r2;
     if (!dp.uniform4) {
-        if ((r2 = upload(&e->d_g_k, p.k, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_inptr, p.in_ptr, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_inidx, p.in_idx, e->stream))) return r2;
-        if ((r2 = upload(&e->d_g_noff, p.node_off, e->stream))) return r2;
+        if ((r2 = upload(img.k, p.k, e->stream))) return r2;
+        if ((r2 = upload(img.inptr, p.in_ptr, e->stream))) return r2;
+        if ((r2 = upload(img.inidx, p.in_idx, e->stream))) return r2;
+        if ((r2 = upload(img.noff, p.node_off, e->stream))) return r2;
     }
     const size_t sd = size_t(dag_state_doubles(dp.E, dp.n));
-    if ((r2 = dalloc(&e->d_g_state, sd))) return r2;
-    HIPCHK(hipMemsetAsync(e->d_g_state, 0, std::max<size_t>(sd, 1) * 8, e->stream));
-    if ((r2 = dalloc(&e->d_g_frz, size_t(dp.n)))) return r2;
-    HIPCHK(hipMemsetAsync(e->d_g_frz, 0, size_t(dp.n), e->stream));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_g_sync), sizeof(ResidentSync)));
-    {   // the dataflow form of a single query (bn_dag.hip): neighbour tiles, granule table + verdict words
-        DagFlowTables ft;
-        try { build_dag_flow_tables(dp, p, ft); } catch (const std::bad_alloc&) { ft = DagFlowTables(); }
-        e->dag_flow_ok = ft.ok && int64_t(dp.blocks) + 1 <= int64_t(e->n_cus);   // (+ the service block: every block co-resident)
-        e->dag_flow_max_nbr = ft.max_nbr;
-        if (e->dag_flow_ok) {
-            if ((r2 = upload(&e->d_g_nbr, ft.nbr, e->stream))) return r2;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_g_flow), dag_flow_sync_bytes(dp.tiles.size())));
-            HIPCHK(hipStreamSynchronize(e->stream));   // (`ft` is a local)
-        }
+    if ((r2 = dalloc(img.state, sd))) return r2;
+    HIPCHK(hipMemsetAsync(img.state, 0, std::max<size_t>(sd, 1) * 8, e->stream));
+    if ((r2 = dalloc(img.frz, size_t(dp.n)))) return r2;
+    HIPCHK(hipMemsetAsync(img.frz, 0, size_t(dp.n), e->stream));
+    HIPCHK(dev_malloc(img.sync, sizeof(ResidentSync)));
+    // the dataflow form of a single query (bn_dag.hip): neighbour tiles, granule table + verdict words
+    DagFlowTables ft;
+    try { build_dag_flow_tables(dp, p, ft); } catch (const std::bad_alloc&) { ft = DagFlowTables(); }
+    const bool flow_ok = ft.ok && int64_t(dp.blocks) + 1 <= int64_t(e->n_cus);   // (+ the service block: every block co-resident)
+    if (flow_ok) {
+        if ((r2 = upload(img.nbr, ft.nbr, e->stream))) return r2;
+        HIPCHK(dev_malloc(img.flow, dag_flow_sync_bytes(dp.tiles.size())));
     }
-    HIPCHK(hipStreamSynchronize(e->stream));   // (upload() copies from the plan's vectors: they stay, but the order against a reload is then plain)
+    HIPCHK(hipStreamSynchronize(e->stream));   // (`ft`, and `full` / `tables` until they are moved, are locals)
+    if (build) {
+        e->dag = std::move(full);
+        e->dag_tables = std::move(tables);
+    }
+    e->dag_img = std::move(img);
+    e->dag_flow_ok = flow_ok;
+    e->dag_flow_max_nbr = ft.max_nbr;
     e->dag_sync_dirty = true;
     e->dag_ev_applied = false;
     e->dag_ready = true;
@@ -324,40 +302,39 @@ static int create_impl(const bn_model_desc* desc, const ShardSpec& shard, bn_eng
             if (const char* o = std::getenv("BN_OVERLAP")) e->overlap = std::atoi(o) != 0;
         }
         int r;
-        if ((r = upload(&e->d_tiles, p.tiles, e->stream))) return r;
-        if ((r = upload(&e->d_classes, p.classes, e->stream))) return r;
-        if ((r = upload(&e->d_flat_tab, p.flat_tab, e->stream))) return r;
-        if ((r = upload(&e->d_cpt, p.cpt_striped, e->stream))) return r;
-        if ((r = upload(&e->d_out, p.out_refs, e->stream))) return r;
-        if ((r = upload(&e->d_inrefs, p.in_refs, e->stream))) return r;
-        if ((r = upload(&e->d_slot_node, p.slot_node, e->stream))) return r;
-        if ((r = upload(&e->d_slot_boff, p.slot_boff, e->stream))) return r;
-        if ((r = upload(&e->d_node_tile, p.node_tile, e->stream))) return r;
-        if ((r = upload(&e->d_node_nl, p.node_nl, e->stream))) return r;
+        if ((r = upload(e->d_tiles, p.tiles, e->stream))) return r;
+        if ((r = upload(e->d_classes, p.classes, e->stream))) return r;
+        if ((r = upload(e->d_flat_tab, p.flat_tab, e->stream))) return r;
+        if ((r = upload(e->d_cpt, p.cpt_striped, e->stream))) return r;
+        if ((r = upload(e->d_out, p.out_refs, e->stream))) return r;
+        if ((r = upload(e->d_inrefs, p.in_refs, e->stream))) return r;
+        if ((r = upload(e->d_slot_node, p.slot_node, e->stream))) return r;
+        if ((r = upload(e->d_slot_boff, p.slot_boff, e->stream))) return r;
+        if ((r = upload(e->d_node_tile, p.node_tile, e->stream))) return r;
+        if ((r = upload(e->d_node_nl, p.node_nl, e->stream))) return r;
         dev_lap("tile tables + image upload");
         // shards: peers store cut-edge halves straight into these buffers from inside their kernels -> fine-grained
         // (system-coherent) allocations; BN_SHARD_COARSE=1 keeps plain hipMalloc (A/B on one device)
         e->fine_grained = p.nranks > 1 && !std::getenv("BN_SHARD_COARSE");
         for (int i = 0; i < 2; ++i) {
             if (e->fine_grained) {
-                HIPCHK(hipExtMallocWithFlags(reinterpret_cast<void**>(&e->d_rec[i]), std::max<size_t>(p.rec_total_doubles, 1) * 8,
-                                             hipDeviceMallocFinegrained));
-            } else if ((r = dalloc(&e->d_rec[i], size_t(p.rec_total_doubles)))) return r;
-            if ((r = dalloc(&e->d_node[i], size_t(p.node_doubles)))) return r;
+                HIPCHK(dev_malloc_fine(e->d_rec[i], std::max<size_t>(p.rec_total_doubles, 1) * 8));
+            } else if ((r = dalloc(e->d_rec[i], size_t(p.rec_total_doubles)))) return r;
+            if ((r = dalloc(e->d_node[i], size_t(p.node_doubles)))) return r;
             HIPCHK(hipMemsetAsync(e->d_rec[i], 0, std::max<size_t>(p.rec_total_doubles, 1) * 8, e->stream));
             HIPCHK(hipMemsetAsync(e->d_node[i], 0, std::max<size_t>(p.node_doubles, 1) * 8, e->stream));
         }
-        if ((r = dalloc(&e->d_frozen, size_t(p.n_slots)))) return r;
+        if ((r = dalloc(e->d_frozen, size_t(p.n_slots)))) return r;
         HIPCHK(hipMemsetAsync(e->d_frozen, 0, std::max<size_t>(p.n_slots, 1), e->stream));
         // store policy: working sets beyond the Infinity Cache stream their outputs non-temporally
         e->nontemporal = 8 * (p.cpt_doubles + 2 * p.rec_doubles + 2 * p.node_doubles) > (int64_t(192) << 20);
-        if ((r = dalloc(&e->d_res_hist, size_t(e->res_cap)))) return r;
-        if ((r = dalloc(&e->d_ctl, 1))) return r;
+        if ((r = dalloc(e->d_res_hist, size_t(e->res_cap)))) return r;
+        if ((r = dalloc(e->d_ctl, 1))) return r;
         HIPCHK(hipMemsetAsync(e->d_ctl, 0, sizeof(Ctl), e->stream));  // done_run = 0: no run is marked done
-        if ((r = dalloc(&e->d_beliefs, size_t(p.node_off[p.n])))) return r;
+        if ((r = dalloc(e->d_beliefs, size_t(p.node_off[p.n])))) return r;
         HIPCHK(hipMemsetAsync(e->d_beliefs, 0, std::max<size_t>(p.node_off[p.n], 1) * 8, e->stream));
         dev_lap("state buffers");
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_ctl), sizeof(Ctl), hipHostMallocMapped));
+        HIPCHK(host_malloc(e->h_ctl, sizeof(Ctl), hipHostMallocMapped));
         std::memset(e->h_ctl, 0, sizeof(Ctl));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ctl_dev), e->h_ctl, 0));
         {   // resident path (bn_resident.hip): one-lane tiles (<= 2 parents, <= 8 children per node), one wave per tile, every block co-resident (one 512-thread block of <= 256 VGPRs per CU)
@@ -401,31 +378,31 @@ static int create_impl(const bn_model_desc* desc, const ShardSpec& shard, bn_eng
             for (const TileDesc& td : p.tiles)
                 if (td.cmax > 2 || int(td.kv) != e->resident_lean) e->resident_lean = 0;
             e->grid_resident = int(nb);
-            if (ok) HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_rsync), sizeof(ResidentSync)));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_abort), 64, hipHostMallocMapped));
+            if (ok) HIPCHK(dev_malloc(e->d_rsync, sizeof(ResidentSync)));
+            HIPCHK(host_malloc(e->h_abort, 64, hipHostMallocMapped));
             std::memset(e->h_abort, 0, 64);
             HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_abort_dev), e->h_abort, 0));
             e->flow_ok = ok && nb > 1 && !p.nbr.empty() && nt <= kFlowMaxTiles;
             if (e->flow_ok) {
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_flow), flow_sync_bytes(1)));
+                HIPCHK(dev_malloc(e->d_flow, flow_sync_bytes(1)));
                 int r2;
-                if ((r2 = upload(&e->d_nbr, p.nbr, e->stream))) return r2;
+                if ((r2 = upload(e->d_nbr, p.nbr, e->stream))) return r2;
             }
             if (p.nranks > 1) {
                 // shards allocate their page-locked staging now: no allocation call may fall between two ranks' launches of a run
                 // (several shard engines in one process: such calls can wait for the whole device)
                 const size_t evb = ((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64;
                 e->ev_bytes_cap = evb;
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_ev), evb, hipHostMallocMapped));
+                HIPCHK(host_malloc(e->h_ev, evb, hipHostMallocMapped));
                 HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ev_dev), e->h_ev, 0));
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_beliefs), std::max<size_t>(p.node_off[p.n], 1) * sizeof(double), hipHostMallocMapped));
+                HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(p.node_off[p.n], 1) * sizeof(double), hipHostMallocMapped));
                 HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
             }
             if (e->shard_shapes_ok) {  // zeroed HERE, once: peers write into it from their kernels whenever they run
                 if (e->fine_grained)
-                    HIPCHK(hipExtMallocWithFlags(reinterpret_cast<void**>(&e->d_flow), flow_sync_bytes(p.nranks), hipDeviceMallocFinegrained));
+                    HIPCHK(dev_malloc_fine(e->d_flow, flow_sync_bytes(p.nranks)));
                 else
-                    HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_flow), flow_sync_bytes(p.nranks)));
+                    HIPCHK(dev_malloc(e->d_flow, flow_sync_bytes(p.nranks)));
                 HIPCHK(hipMemsetAsync(e->d_flow, 0, flow_sync_bytes(p.nranks), e->stream));
             }
             if (const char* f = std::getenv("BN_RESIDENT_FLOW")) e->flow = std::atoi(f) != 0;
@@ -438,17 +415,17 @@ static int create_impl(const bn_model_desc* desc, const ShardSpec& shard, bn_eng
             if (e->small.ok) {
                 const SmallPlan& sp = e->small;
                 int r2;
-                if ((r2 = upload(&e->d_s_ent, sp.ent, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_cpt, sp.ent_cpt, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_term, sp.term, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_clist, sp.clist, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_bslot, sp.bslot, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_cslot, sp.cslot, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_nvidx, sp.nv_idx, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_nvslot, sp.nv_slot, e->stream))) return r2;
-                if ((r2 = upload(&e->d_s_init, sp.npi_init, e->stream))) return r2;
-                if ((r2 = dalloc(&e->d_s_state, size_t(2 * sp.M + 2 * sp.N)))) return r2;
-                if ((r2 = upload(&e->d_s_nodeoff, sp.node_off, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_ent, sp.ent, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_cpt, sp.ent_cpt, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_term, sp.term, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_clist, sp.clist, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_bslot, sp.bslot, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_cslot, sp.cslot, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_nvidx, sp.nv_idx, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_nvslot, sp.nv_slot, e->stream))) return r2;
+                if ((r2 = upload(e->d_s_init, sp.npi_init, e->stream))) return r2;
+                if ((r2 = dalloc(e->d_s_state, size_t(2 * sp.M + 2 * sp.N)))) return r2;
+                if ((r2 = upload(e->d_s_nodeoff, sp.node_off, e->stream))) return r2;
                 if (int code = prepare_bp_small())
                     return fail(BN_ERR_HIP, std::string("bp_small attribute: ") + hipGetErrorString(hipError_t(code)));
                 e->small_ok = true;
@@ -482,18 +459,18 @@ static int create_impl(const bn_model_desc* desc, const ShardSpec& shard, bn_eng
             std::vector<int32_t> msg_first(p.n + 1);
             for (int v = 0; v <= p.n; ++v) msg_first[v] = int32_t(p.msg_off[v < p.n ? p.in_ptr[v] : p.in_ptr[p.n]]);
             int r2;
-            if ((r2 = upload(&e->d_m_parts, parts, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_ent, ent, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_cpt, cpt, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_term, term, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_clist, clist, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_bslot, bslot, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_cslot, cslot, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_nvidx, g0.nv_idx, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_nvslot, g0.nv_slot, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_init, g0.npi_init, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_nodeoff, g0.node_off, e->stream))) return r2;
-            if ((r2 = upload(&e->d_m_msgfirst, msg_first, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_parts, parts, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_ent, ent, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_cpt, cpt, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_term, term, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_clist, clist, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_bslot, bslot, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_cslot, cslot, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_nvidx, g0.nv_idx, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_nvslot, g0.nv_slot, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_init, g0.npi_init, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_nodeoff, g0.node_off, e->stream))) return r2;
+            if ((r2 = upload(e->d_m_msgfirst, msg_first, e->stream))) return r2;
             if ((r2 = mid_reserve_slots(e, 1))) return r2;
             if (int code = prepare_bp_mid())
                 return fail(BN_ERR_HIP, std::string("bp_mid attribute: ") + hipGetErrorString(hipError_t(code)));
@@ -664,10 +641,10 @@ static int set_evidence_impl(bn_engine* e, int32_t ne, const int32_t* ev_node, c
     }
     if (!e->h_ev) {
         // the staging block is sized ONCE, for the largest evidence set the model admits (every node observed): growing it
-        // later would mean hipHostFree, which waits for the whole device -- and where several shard engines share a process,
+        // later would mean freeing page-locked memory, which waits for the whole device -- and where several shard engines share a process,
         // a rank whose kernel is already waiting for this rank's would never let that return
         e->ev_bytes_cap = ((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_ev), e->ev_bytes_cap, hipHostMallocMapped));
+        HIPCHK(host_malloc(e->h_ev, e->ev_bytes_cap, hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ev_dev), e->h_ev, 0));
     }
     if (bytes > e->ev_bytes_cap) return fail(BN_ERR_ARG, "evidence larger than the model");
@@ -831,8 +808,8 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         ResidentArgs a{buffers_of(e), eps, max_sweeps, begin, kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
                        // one wait: 50 ms of the 100 MHz clock; shards: 2 s (the ranks' launches start up to a host hiccup apart)
                        shard ? 200000000ull : 5000000ull, e->d_rsync, e->h_ctl_dev,
-                       e->grid_resident, e->resident_waves, 1, 1u, 0, 0, 0, 0, 0, flow ? e->d_flow : nullptr,
-                       shard ? e->d_peers : nullptr, shard ? e->d_pub_mask : nullptr, shard ? e->plan.n_interior_tiles : 0,
+                       e->grid_resident, e->resident_waves, 1, 1u, 0, 0, 0, 0, 0, flow ? e->d_flow.get() : nullptr,
+                       shard ? e->d_peers.get() : nullptr, shard ? e->d_pub_mask.get() : nullptr, shard ? e->plan.n_interior_tiles : 0,
                        e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort_dev, (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin};
         if (e->timing) {
             int rc = ensure_events(e, 2);
@@ -851,7 +828,7 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         if (copy_to && shard) {  // through the engine's page-locked buffer: a plain DMA, nothing that blocks inside the runtime
             const size_t bytes = sizeof(double) * e->plan.node_off[e->plan.n];
             if (copy_to != e->h_beliefs && !e->h_beliefs) {
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_beliefs), std::max<size_t>(bytes, 8), hipHostMallocMapped));
+                HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(bytes, 8), hipHostMallocMapped));
                 HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
             }
             HIPCHK(hipMemcpyAsync(e->h_beliefs, e->d_beliefs, bytes, hipMemcpyDeviceToHost, s));
@@ -983,7 +960,7 @@ MidArgs bn_eng::mid_args_of(bn_engine* e, const BpBuffers& b0, const SetStrides&
     a.state_stride = 4 * int64_t(g0.M) + 4 * int64_t(g0.N);
     a.pi = e->d_m_state; a.lam = a.pi + 2 * size_t(g0.M); a.npi = a.lam + 2 * size_t(g0.M); a.nlam = a.npi + 2 * size_t(g0.N);
     a.frz = e->d_m_frz;
-    a.bar = reinterpret_cast<unsigned*>(e->d_m_sync);
+    a.bar = reinterpret_cast<unsigned*>(e->d_m_sync.get());
     a.res = reinterpret_cast<unsigned long long*>(e->d_m_sync + 8);
     a.abort = e->h_abort_dev;
     a.timeout_ticks = 5000000ull;  // one wait: 50 ms of the 100 MHz clock
@@ -1084,11 +1061,11 @@ static int flush_dag_evidence(bn_engine* e) {
     if (int rc = ensure_dag(e)) return rc;
     if (e->dag_ev_applied) return BN_OK;
     if (e->dag_mark == 255) {  // the mark values are used up: start over
-        HIPCHK(hipMemsetAsync(e->d_g_frz, 0, size_t(e->dag.n), e->stream));
+        HIPCHK(hipMemsetAsync(e->dag_img.frz, 0, size_t(e->dag.n), e->stream));
         e->dag_mark = 0;
     }
     ++e->dag_mark;
-    DagEvidenceArgs ea{e->ev_ne, e->dag.n, e->dag.E, e->d_ev_node, e->d_ev_off, e->d_ev_val, e->d_g_state, e->d_g_frz, e->dag_mark, e->d_g_k, e->d_g_nperm};
+    DagEvidenceArgs ea{e->ev_ne, e->dag.n, e->dag.E, e->d_ev_node, e->d_ev_off, e->d_ev_val, e->dag_img.state, e->dag_img.frz, e->dag_mark, e->dag_img.k, e->dag_img.nperm};
     if (int code = launch_dag_evidence(ea, e->stream))
         return fail(BN_ERR_HIP, std::string("dag_evidence launch failed: ") + hipGetErrorString(hipError_t(code)));
     e->dag_ev_applied = true;
@@ -1109,15 +1086,15 @@ int bn_eng::run_dag(bn_engine* e, double eps, int32_t max_sweeps, double* copy_t
     double dev_ticks = 0.0;
     const BpBuffers b = buffers_of(e);
     if (!dp.uniform4) {   // arities below 4: the run's initial state stands in memory (zeros in the padding), bn_dag_plan.cpp
-        DagInitArgs ia{dp.n, dp.E, e->d_g_inptr, e->d_g_inidx, e->d_g_k, e->d_g_init, e->d_g_state, e->d_g_frz, e->dag_mark, e->d_g_eperm, e->d_g_nperm};
+        DagInitArgs ia{dp.n, dp.E, e->dag_img.inptr, e->dag_img.inidx, e->dag_img.k, e->dag_img.init, e->dag_img.state, e->dag_img.frz, e->dag_mark, e->dag_img.eperm, e->dag_img.nperm};
         if (int code = launch_dag_init(ia, s))
             return fail(BN_ERR_HIP, std::string("dag_init launch failed: ") + hipGetErrorString(hipError_t(code)));
     }
     for (;;) {
         // polled words: generations count on from launch to launch; zeroed at creation, after an abort and before they would wrap
         if (e->dag_sync_dirty || e->dag_gen_base > (1u << 29)) {
-            HIPCHK(hipMemsetAsync(e->d_g_sync, 0, sizeof(ResidentSync), s));
-            if (e->d_g_flow) HIPCHK(hipMemsetAsync(e->d_g_flow, 0, dag_flow_sync_bytes(dp.tiles.size()), s));
+            HIPCHK(hipMemsetAsync(e->dag_img.sync, 0, sizeof(ResidentSync), s));
+            if (e->dag_img.flow) HIPCHK(hipMemsetAsync(e->dag_img.flow, 0, dag_flow_sync_bytes(dp.tiles.size()), s));
             e->dag_sync_dirty = false;
             e->dag_gen_base = 0;
         }
@@ -1127,22 +1104,22 @@ int bn_eng::run_dag(bn_engine* e, double eps, int32_t max_sweeps, double* copy_t
         const bool flow = e->dag_flow_ok && e->dag_flow != 0 && !dp.stream && dp.blocks > 1 && e->dag_flow_pause == 0;
         if (flow) {
             static const int flow_sleep = std::getenv("BN_DAG_FLOW_SLEEP") ? std::atoi(std::getenv("BN_DAG_FLOW_SLEEP")) : 4;   // x 512 cycles between polls; configs[1], us per executed iteration: 6.59 / 6.38 / 6.14 / 6.06 / 6.00 at 0 / 1 / 2 / 4 / 8
-            a.flow = e->d_g_flow; a.nbr = e->d_g_nbr; a.n_tiles = int32_t(dp.tiles.size()); a.flow_sleep = flow_sleep;
+            a.flow = e->dag_img.flow; a.nbr = e->dag_img.nbr; a.n_tiles = int32_t(dp.tiles.size()); a.flow_sleep = flow_sleep;
         }
         e->last_dag_flow = flow ? 1 : 0;
         a.b = b; a.eps = eps; a.max_sweeps = max_sweeps; a.sweep_begin = begin; a.budget = kDagBudget; a.run_id = e->run_id;
         a.gen_base = e->dag_gen_base;
         a.timeout_ticks = 5000000ull;  // one wait: 50 ms of the 100 MHz clock
-        a.sync = e->d_g_sync; a.host_ctl = e->h_ctl_dev; a.host_abort = e->h_abort_dev;
+        a.sync = e->dag_img.sync; a.host_ctl = e->h_ctl_dev; a.host_abort = e->h_abort_dev;
         a.n = dp.n; a.E = dp.E; a.n_blocks = dp.blocks;
-        a.tiles = e->d_g_tiles; a.slot_ptr = e->d_g_slotptr; a.cnode = e->d_g_cnode; a.pitem = e->d_g_pitem; a.oedge = e->d_g_oedge;
-        a.cpt_img = e->d_g_cpt; a.npi_init = e->d_g_init; a.state = e->d_g_state; a.frz = e->d_g_frz; a.frz_mark = e->dag_mark;
+        a.tiles = e->dag_img.tiles; a.slot_ptr = e->dag_img.slotptr; a.cnode = e->dag_img.cnode; a.pitem = e->dag_img.pitem; a.oedge = e->dag_img.oedge;
+        a.cpt_img = e->dag_img.cpt; a.npi_init = e->dag_img.init; a.state = e->dag_img.state; a.frz = e->dag_img.frz; a.frz_mark = e->dag_mark;
         static const int poll_sleep = std::getenv("BN_DAG_SLEEP") ? std::atoi(std::getenv("BN_DAG_SLEEP")) : 1;
         a.poll_sleep = poll_sleep;
         static const int first_delay = std::getenv("BN_DAG_DELAY") ? std::atoi(std::getenv("BN_DAG_DELAY")) : 30;   // 10 ns ticks: measured flat from 20 to 60 (config 2: 6.9 us per sweep at 0, 6.5-6.6 there)
         a.first_poll_delay = first_delay;
         a.n_sets = 1; a.set_mask = 1u;
-        a.state_init = dp.uniform4 ? 0 : 1; a.node_k = e->d_g_k; a.node_off = e->d_g_noff;
+        a.state_init = dp.uniform4 ? 0 : 1; a.node_k = e->dag_img.k; a.node_off = e->dag_img.noff;
         if (e->timing) {
             int rc = ensure_events(e, 2);
             if (rc) return rc;
@@ -1570,7 +1547,7 @@ extern "C" int bn_bp_run_view(bn_engine* e, int32_t ne, const int32_t* ev_node, 
     if (rc) return rc;
     if (!e->h_beliefs) {
         ON_DEVICE(e);
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_beliefs), std::max<size_t>(e->plan.node_off[e->plan.n], 1) * sizeof(double),
+        HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(e->plan.node_off[e->plan.n], 1) * sizeof(double),
                              hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
     }
@@ -1606,8 +1583,8 @@ extern "C" int bn_bp_messages(bn_engine* e, double* pi_msg_out, double* lambda_m
         // the records (tile-major in the state, bn_dag.hpp) back in CSR edge order; arities below 4: of a padded record edge e's first
         // k(parent of e) entries exist
         std::vector<double> pm(size_t(E) * 4), lm(size_t(E) * 4);
-        HIPCHK(hipMemcpy(pm.data(), e->d_g_state + 2 * dag_off_pim(E, n, par, 0), sizeof(double) * 4 * size_t(E), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(lm.data(), e->d_g_state + 2 * dag_off_lam(E, n, par, 0), sizeof(double) * 4 * size_t(E), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pm.data(), e->dag_img.state + 2 * dag_off_pim(E, n, par, 0), sizeof(double) * 4 * size_t(E), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(lm.data(), e->dag_img.state + 2 * dag_off_lam(E, n, par, 0), sizeof(double) * 4 * size_t(E), hipMemcpyDeviceToHost));
         size_t at = 0;
         for (int64_t ed = 0; ed < E; ++ed) {
             const int kp = e->dag.uniform4 ? 4 : e->plan.k[e->plan.in_idx[ed]];

@@ -12,32 +12,25 @@ static int batch_reserve(bn_engine* e, int32_t n_sets) {
     if (n_sets <= bt.cap_sets) return BN_OK;
     const Plan& p = e->plan;
     HIPCHK(hipStreamSynchronize(e->stream));
-    void* old[] = {bt.d_rec[0], bt.d_rec[1], bt.d_node[0], bt.d_node[1], bt.d_frozen, bt.d_beliefs, bt.d_res_hist, bt.d_sync, bt.d_ctl, bt.d_s_state,
-                   bt.d_ev, bt.d_g_state, bt.d_g_frz, bt.d_g_sync};
-    if (bt.h_ev) (void)hipHostFree(bt.h_ev);
-    if (bt.h_beliefs) (void)hipHostFree(bt.h_beliefs);
-    for (void* q : old)
-        if (q) (void)hipFree(q);
-    if (bt.h_ctl) (void)hipHostFree(bt.h_ctl);
     bt = bn_engine::Batch();
     int r;
     const size_t B = size_t(n_sets);
     for (int i = 0; i < 2; ++i) {
-        if ((r = dalloc(&bt.d_rec[i], B * size_t(p.rec_total_doubles)))) return r;
-        if ((r = dalloc(&bt.d_node[i], B * size_t(p.node_doubles)))) return r;
+        if ((r = dalloc(bt.d_rec[i], B * size_t(p.rec_total_doubles)))) return r;
+        if ((r = dalloc(bt.d_node[i], B * size_t(p.node_doubles)))) return r;
         HIPCHK(hipMemsetAsync(bt.d_rec[i], 0, std::max<size_t>(B * p.rec_total_doubles, 1) * 8, e->stream));
         HIPCHK(hipMemsetAsync(bt.d_node[i], 0, std::max<size_t>(B * p.node_doubles, 1) * 8, e->stream));
     }
-    if ((r = dalloc(&bt.d_frozen, B * size_t(std::max(p.n_slots, 1))))) return r;
-    if ((r = dalloc(&bt.d_beliefs, B * size_t(p.node_off[p.n])))) return r;
-    if ((r = dalloc(&bt.d_res_hist, B * size_t(e->res_cap)))) return r;
-    if ((r = dalloc(&bt.d_sync, std::min<size_t>(B, kResidentMaxSets)))) return r;
-    if ((r = dalloc(&bt.d_ctl, B))) return r;
-    if (e->small_ok && (r = dalloc(&bt.d_s_state, B * size_t(2 * e->small.M + 2 * e->small.N)))) return r;
+    if ((r = dalloc(bt.d_frozen, B * size_t(std::max(p.n_slots, 1))))) return r;
+    if ((r = dalloc(bt.d_beliefs, B * size_t(p.node_off[p.n])))) return r;
+    if ((r = dalloc(bt.d_res_hist, B * size_t(e->res_cap)))) return r;
+    if ((r = dalloc(bt.d_sync, std::min<size_t>(B, kResidentMaxSets)))) return r;
+    if ((r = dalloc(bt.d_ctl, B))) return r;
+    if (e->small_ok && (r = dalloc(bt.d_s_state, B * size_t(2 * e->small.M + 2 * e->small.N)))) return r;
     HIPCHK(hipMemsetAsync(bt.d_ctl, 0, sizeof(Ctl) * B, e->stream));  // done_run = 0: no run is marked done
     HIPCHK(hipMemsetAsync(bt.d_frozen, 0, B * size_t(std::max(p.n_slots, 1)), e->stream));
     HIPCHK(hipMemsetAsync(bt.d_beliefs, 0, std::max<size_t>(B * p.node_off[p.n], 1) * 8, e->stream));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&bt.h_ctl), sizeof(Ctl) * B, hipHostMallocMapped));
+    HIPCHK(host_malloc(bt.h_ctl, sizeof(Ctl) * B, hipHostMallocMapped));
     std::memset(bt.h_ctl, 0, sizeof(Ctl) * B);
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.h_ctl_dev), bt.h_ctl, 0));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -203,10 +196,8 @@ extern "C" int bn_bp_set_evidence_batch(bn_engine* e, int32_t n_sets, const int3
         // buffers get the marks and vectors only if another path runs the batch (flush_batch_evidence).  (No kernel is in
         // flight when the block is rewritten: every run entry point synchronises before it returns.)
         if (bytes > bt.h_ev_cap) {
-            if (bt.h_ev) (void)hipHostFree(bt.h_ev);
-            bt.h_ev = nullptr;
             bt.h_ev_cap = std::max<size_t>(bytes * 2, 4096);
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&bt.h_ev), bt.h_ev_cap, hipHostMallocMapped));
+            HIPCHK(host_malloc(bt.h_ev, bt.h_ev_cap, hipHostMallocMapped));
             HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.ev_base), bt.h_ev, 0));
         }
         fill(bt.h_ev);
@@ -215,10 +206,8 @@ extern "C" int bn_bp_set_evidence_batch(bn_engine* e, int32_t n_sets, const int3
     }
     // every other network: one H2D copy, then one evidence kernel per set
     if (bytes > bt.ev_cap) {
-        if (bt.d_ev) (void)hipFree(bt.d_ev);
-        bt.d_ev = nullptr;
         bt.ev_cap = std::max<size_t>(bytes * 2, 4096);
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&bt.d_ev), bt.ev_cap));
+        HIPCHK(dev_malloc(bt.d_ev, bt.ev_cap));
     }
     bt.ev_base = bt.d_ev;
     std::vector<char> host(std::max<size_t>(bytes, 1));
@@ -420,10 +409,8 @@ static int run_batch_small(bn_engine* e, double eps, int32_t max_sweeps) {
     const size_t per_set = size_t(p.node_off[p.n]);
     if (bt.direct_out) {  // bn_bp_run_batch: the marginals go straight into page-locked host memory (no copy command, no second sync)
         if (size_t(B) * per_set > bt.h_beliefs_cap) {
-            if (bt.h_beliefs) (void)hipHostFree(bt.h_beliefs);
-            bt.h_beliefs = nullptr;
             bt.h_beliefs_cap = size_t(bt.cap_sets) * per_set;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&bt.h_beliefs), std::max<size_t>(bt.h_beliefs_cap, 1) * sizeof(double), hipHostMallocMapped));
+            HIPCHK(host_malloc(bt.h_beliefs, std::max<size_t>(bt.h_beliefs_cap, 1) * sizeof(double), hipHostMallocMapped));
             HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.h_beliefs_dev), bt.h_beliefs, 0));
         }
         a.b.beliefs = bt.h_beliefs_dev;
@@ -560,9 +547,9 @@ static int enqueue_batch_dag_chunk(bn_engine* e, double eps, int32_t max_sweeps,
     const size_t state_d = size_t(dag_state_doubles(dp.E, dp.n));
     if (bt.dag_sets < kDagMaxSets) {   // first use: every set's state, marks and barrier words
         int r;
-        if ((r = dalloc(&bt.d_g_state, state_d * kDagMaxSets))) return r;
-        if ((r = dalloc(&bt.d_g_frz, size_t(dp.n) * kDagMaxSets))) return r;
-        if ((r = dalloc(&bt.d_g_sync, size_t(kDagMaxSets)))) return r;
+        if ((r = dalloc(bt.d_g_state, state_d * kDagMaxSets))) return r;
+        if ((r = dalloc(bt.d_g_frz, size_t(dp.n) * kDagMaxSets))) return r;
+        if ((r = dalloc(bt.d_g_sync, size_t(kDagMaxSets)))) return r;
         HIPCHK(hipMemsetAsync(bt.d_g_state, 0, state_d * kDagMaxSets * sizeof(double), s));
         HIPCHK(hipMemsetAsync(bt.d_g_frz, 0, size_t(dp.n) * kDagMaxSets, s));
         bt.dag_sets = kDagMaxSets;
@@ -589,9 +576,9 @@ static int enqueue_batch_dag_chunk(bn_engine* e, double eps, int32_t max_sweeps,
             eb.set[q] = DagEvidenceArgs{bt.ne[g], dp.n, dp.E, reinterpret_cast<int32_t*>(bt.ev_base + bt.ev_b_node) + bt.ev_node_at[g],
                                         reinterpret_cast<int32_t*>(bt.ev_base + bt.ev_b_off) + bt.ev_off_at[g],
                                         reinterpret_cast<double*>(bt.ev_base + bt.ev_b_val) + bt.ev_val_at[g], bt.d_g_state + size_t(q) * state_d,
-                                        bt.d_g_frz + size_t(q) * dp.n, bt.dag_mark, e->d_g_k, e->d_g_nperm};
-            ib.set[q] = DagInitArgs{dp.n, dp.E, e->d_g_inptr, e->d_g_inidx, e->d_g_k, e->d_g_init, bt.d_g_state + size_t(q) * state_d,
-                                    bt.d_g_frz + size_t(q) * dp.n, bt.dag_mark, e->d_g_eperm, e->d_g_nperm};
+                                        bt.d_g_frz + size_t(q) * dp.n, bt.dag_mark, e->dag_img.k, e->dag_img.nperm};
+            ib.set[q] = DagInitArgs{dp.n, dp.E, e->dag_img.inptr, e->dag_img.inidx, e->dag_img.k, e->dag_img.init, bt.d_g_state + size_t(q) * state_d,
+                                    bt.d_g_frz + size_t(q) * dp.n, bt.dag_mark, e->dag_img.eperm, e->dag_img.nperm};
         }
         if (int code = launch_dag_evidence_batch(eb, count, s))
             return fail(BN_ERR_HIP, std::string("dag_evidence launch failed: ") + hipGetErrorString(hipError_t(code)));
@@ -617,14 +604,14 @@ static int enqueue_batch_dag_chunk(bn_engine* e, double eps, int32_t max_sweeps,
     a.timeout_ticks = 5000000ull;
     a.sync = bt.d_g_sync; a.host_ctl = bt.h_ctl_dev + first; a.host_abort = e->h_abort_dev;
     a.n = dp.n; a.E = dp.E; a.n_blocks = dp.blocks;
-    a.tiles = e->d_g_tiles; a.slot_ptr = e->d_g_slotptr; a.cnode = e->d_g_cnode; a.pitem = e->d_g_pitem; a.oedge = e->d_g_oedge;
-    a.cpt_img = e->d_g_cpt; a.npi_init = e->d_g_init; a.state = bt.d_g_state; a.frz = bt.d_g_frz; a.frz_mark = bt.dag_mark;
+    a.tiles = e->dag_img.tiles; a.slot_ptr = e->dag_img.slotptr; a.cnode = e->dag_img.cnode; a.pitem = e->dag_img.pitem; a.oedge = e->dag_img.oedge;
+    a.cpt_img = e->dag_img.cpt; a.npi_init = e->dag_img.init; a.state = bt.d_g_state; a.frz = bt.d_g_frz; a.frz_mark = bt.dag_mark;
     static const int poll_sleep = std::getenv("BN_DAG_SLEEP") ? std::atoi(std::getenv("BN_DAG_SLEEP")) : 1;
     static const int first_delay = std::getenv("BN_DAG_DELAY") ? std::atoi(std::getenv("BN_DAG_DELAY")) : 30;
     a.poll_sleep = poll_sleep;
     a.first_poll_delay = first_delay;
     a.n_sets = count; a.set_mask = (1u << count) - 1u;
-    a.state_init = dp.uniform4 ? 0 : 1; a.node_k = e->d_g_k; a.node_off = e->d_g_noff;
+    a.state_init = dp.uniform4 ? 0 : 1; a.node_k = e->dag_img.k; a.node_off = e->dag_img.noff;
     a.state_stride = int64_t(state_d); a.frz_stride = dp.n; a.belief_stride = p.node_off[p.n]; a.res_hist_stride = e->res_cap;
     for (int32_t q = 0; q < count; ++q) bt.h_ctl[first + q].run_id = 0;
     if (int code = launch_bp_dag(a, dp.stream, s))

@@ -28,6 +28,7 @@
 #include "bn_lw.hpp"
 #include "bn_small.hpp"
 #include "bn_dag.hpp"
+#include "bn_buffer.hpp"
 
 using namespace bnmi;
 
@@ -81,6 +82,28 @@ struct RcclApi {
     ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;   // (optional: bn_get_info "rccl_ranks")
 };
 
+// The register-resident DAG path's device image for single queries: uploaded whole by ensure_dag, or not at all.
+struct DagImage {
+    DeviceBuf<DagTile> tiles;
+    DeviceBuf<int32_t> slotptr;
+    DeviceBuf<DagChildLane> cnode;      // (tiles, parent lanes and out-edges: with state records in place of CSR ids, build_dag_device_tables)
+    DeviceBuf<DagParentLaneDev> pitem;
+    DeviceBuf<int32_t> oedge;
+    DeviceBuf<int32_t> eperm;           // CSR edge id -> message record, node id -> slot of its vectors
+    DeviceBuf<int32_t> nperm;
+    DeviceBuf<double> cpt;
+    DeviceBuf<double> init;
+    DeviceBuf<int32_t> k;               // networks with arities below 4 (DagPlan::uniform4 == false): arity, in-edge CSR and marginal offsets for the padded form
+    DeviceBuf<int32_t> inptr;
+    DeviceBuf<int32_t> inidx;
+    DeviceBuf<int64_t> noff;
+    DeviceBuf<double> state;            // pi-/lambda-messages (CSR edge order), pi(v), lambda(v): two buffers each (bn_dag.hpp dag_off_*)
+    DeviceBuf<uint8_t> frz;
+    DeviceBuf<ResidentSync> sync;
+    DeviceBuf<int32_t> nbr;             // dataflow form (dag_flow_ok): neighbour tiles, granule table + verdict words
+    DeviceBuf<DagFlowSync> flow;
+};
+
 struct bn_engine {
     Plan plan;
     bool host_only = true;
@@ -89,32 +112,31 @@ struct bn_engine {
     int device = -1;
     hipStream_t stream = nullptr;
     // device images
-    TileDesc* d_tiles = nullptr;
-    ClassDesc* d_classes = nullptr;
-    FlatEntry* d_flat_tab = nullptr;
-    double* d_cpt = nullptr;
-    double* d_rec[2] = {nullptr, nullptr};
-    double* d_node[2] = {nullptr, nullptr};
-    MsgRef* d_out = nullptr;
-    MsgRef* d_inrefs = nullptr;
+    DeviceBuf<TileDesc> d_tiles;
+    DeviceBuf<ClassDesc> d_classes;
+    DeviceBuf<FlatEntry> d_flat_tab;
+    DeviceBuf<double> d_cpt;
+    DeviceBuf<double> d_rec[2];
+    DeviceBuf<double> d_node[2];
+    DeviceBuf<MsgRef> d_out;
+    DeviceBuf<MsgRef> d_inrefs;
     ncclComm_t comm = nullptr;
     hipStream_t comm_stream = nullptr;   // sharded runs: the all-gathers run here, beside the interior tiles' launch
     hipEvent_t ev_swept = nullptr;       // main stream: every tile of the current sweep has been launched
     hipEvent_t ev_gathered = nullptr;    // comm stream: the current sweep's all-gather
     bool overlap = true;                 // BN_OVERLAP=0 / bn_set_option("overlap", 0): kernel and collective back to back
-    uint8_t* d_frozen = nullptr;
+    DeviceBuf<uint8_t> d_frozen;
     uint8_t frozen_mark = 1;        // mark value of the evidence set in force (1..255; wrapping clears the array)
     char* h_ev_dev = nullptr;       // h_ev as the device sees it (mapped page-locked memory: the evidence kernel reads it in place)
-    int32_t* d_slot_node = nullptr;
-    int64_t* d_slot_boff = nullptr;
-    int32_t* d_node_tile = nullptr;
-    int32_t* d_node_nl = nullptr;
-    double* d_res_hist = nullptr;
-    Ctl* d_ctl = nullptr;
-    double* d_beliefs = nullptr;
-    // evidence staging: one device block + one pinned host block, sub-pointers into d_ev
-    char* d_ev = nullptr;
-    char* h_ev = nullptr;
+    DeviceBuf<int32_t> d_slot_node;
+    DeviceBuf<int64_t> d_slot_boff;
+    DeviceBuf<int32_t> d_node_tile;
+    DeviceBuf<int32_t> d_node_nl;
+    DeviceBuf<double> d_res_hist;
+    DeviceBuf<Ctl> d_ctl;
+    DeviceBuf<double> d_beliefs;
+    // evidence staging: one pinned host block the device reads mapped, sub-pointers into h_ev_dev
+    PinnedBuf<char> h_ev;
     size_t ev_bytes_cap = 0;
     int32_t ev_ne = 0;
     int32_t ev_nval = 0;            // values of the evidence in force (sum of the observed nodes' arities)
@@ -134,7 +156,7 @@ struct bn_engine {
     int32_t resident_aborts = 0;    // launches that gave up, over the engine's life (bn_bp_stats.resident_aborts)
     int32_t resident_cooldown = 0;  // runs left before the resident path is tried again
     int32_t resident_backoff = 8;   // length of the next pause
-    double* h_beliefs = nullptr;    // pinned: bn_bp_run_view hands this out, bn_bp_run stages nothing through it
+    PinnedBuf<double> h_beliefs;    // pinned: bn_bp_run_view hands this out, bn_bp_run stages nothing through it
     double* h_beliefs_dev = nullptr;  // ... as the device sees it
     double* beliefs_override = nullptr;  // where the kernels write the beliefs of the run in hand instead of d_beliefs
     bool beliefs_on_host_only = false;   // the last run wrote its marginals into h_beliefs, not d_beliefs (synced back on demand)
@@ -150,7 +172,7 @@ struct bn_engine {
     int resident_poll_margin = 30;  // direct form: 10 ns ticks between the predicted arrival of the last block and a block's first poll (BN_RESIDENT_DELAY)
     int resident_direct = 1;        // option "direct" / BN_RESIDENT_DIRECT: the grid barrier without a service block (bn_resident.hip wait_verdict);
                                     // measured against the service block, us per sweep: 32 x 32 grid 6.98 -> 6.46, 128 x 128 7.25 -> 6.80, 316 x 316 11.46 -> 11.04
-    ResidentSync* d_rsync = nullptr;
+    DeviceBuf<ResidentSync> d_rsync;
     bool rsync_dirty = true;        // the sync block must be zeroed before the next launch
     // dataflow form of the resident kernel (no grid barrier; single evidence set, more than one tile block)
     bool flow_ok = false;           // every tile has <= 64 neighbour tiles
@@ -158,38 +180,38 @@ struct bn_engine {
     int flow = 0;                   // option "flow" / BN_RESIDENT_FLOW: 1 = dataflow form where eligible, 0 = grid barrier per sweep
                                     // (the default on one GPU: measured equal per sweep, and the lagging stop decision costs one
                                     // speculative iteration per run; sharded engines exchange through the dataflow form)
-    FlowSync* d_flow = nullptr;
+    DeviceBuf<FlowSync> d_flow;
     bool flow_dirty = true;
     uint32_t flow_gen_base = 0;
-    int32_t* d_nbr = nullptr;
+    DeviceBuf<int32_t> d_nbr;
     // sharded engines: halo exchange inside the resident kernel (bn_peer_export / bn_peer_import)
     bool shard_shapes_ok = false;   // this shard's tiles are what the resident kernel runs (uniform arity, <= 2 parents, <= 8 children)
     bool shard_flow_ok = false;     // ... on every rank, and the peers' buffers are mapped: the dataflow form exchanges in-kernel
     bool fine_grained = false;      // record buffers / sync block allocated fine-grained (peers store into them)
     uint32_t shard_run_seq = 0;     // bn_bp_run_device calls on this sharded engine: every rank counts alike -> same generations
-    PeerTable* d_peers = nullptr;
-    uint32_t* d_pub_mask = nullptr;
+    DeviceBuf<PeerTable> d_peers;
+    DeviceBuf<uint32_t> d_pub_mask;
     std::vector<uint32_t> pub_mask; // host copy (introspection)
     std::vector<void*> ipc_opened;  // hipIpcOpenMemHandle results to close
-    unsigned* h_abort = nullptr;    // pinned + mapped: set by a kernel that gives up a bounded wait
+    PinnedBuf<unsigned> h_abort;    // pinned + mapped: set by a kernel that gives up a bounded wait
     unsigned* h_abort_dev = nullptr;
     uint32_t gen_base = 0;          // barrier generations used so far on d_rsync
     // several evidence sets per launch (bn_bp_*_batch): per-set records, node vectors, marks, beliefs, histories
     struct Batch {
         int32_t n_sets = 0, cap_sets = 0;
-        double* d_rec[2] = {nullptr, nullptr};
-        double* d_node[2] = {nullptr, nullptr};
-        uint8_t* d_frozen = nullptr;
-        double* d_beliefs = nullptr;
-        double* d_res_hist = nullptr;
-        ResidentSync* d_sync = nullptr;  // resident path: [min(cap_sets, kResidentMaxSets)]
+        DeviceBuf<double> d_rec[2];
+        DeviceBuf<double> d_node[2];
+        DeviceBuf<uint8_t> d_frozen;
+        DeviceBuf<double> d_beliefs;
+        DeviceBuf<double> d_res_hist;
+        DeviceBuf<ResidentSync> d_sync;  // resident path: [min(cap_sets, kResidentMaxSets)]
         bool sync_dirty = true;
         uint32_t gen_base = 0;
-        double* d_s_state = nullptr;  // one-workgroup path (bn_small.hip): [cap_sets][2 M + 2 N]
+        DeviceBuf<double> d_s_state;  // one-workgroup path (bn_small.hip): [cap_sets][2 M + 2 N]
         // register-resident DAG path (bn_dag.hip), several sets per launch: [dag_sets] states, marks, barrier words (allocated at first use)
-        double* d_g_state = nullptr;
-        uint8_t* d_g_frz = nullptr;
-        ResidentSync* d_g_sync = nullptr;
+        DeviceBuf<double> d_g_state;
+        DeviceBuf<uint8_t> d_g_frz;
+        DeviceBuf<ResidentSync> d_g_sync;
         int32_t dag_sets = 0;
         uint8_t dag_mark = 0;
         bool dag_ev_applied = false;  // state slot q holds set q's evidence under mark dag_mark (a batch of at most kDagMaxSets sets on a network
@@ -198,22 +220,22 @@ struct bn_engine {
         uint32_t dag_gen_base = 0;
         bool ev_deferred = false;     // the sets' evidence sits in d_ev only (read there by that kernel); d_ev_meta: per set {count, first node / offset / value}
         int32_t* d_ev_meta = nullptr;   // (inside the staging block)
-        char* h_ev = nullptr;           // small networks: the staging block is page-locked host memory the kernels read in place
+        PinnedBuf<char> h_ev;           // small networks: the staging block is page-locked host memory the kernels read in place
         char* ev_base = nullptr;        // the staging block as the device sees it: d_ev, or h_ev mapped
         size_t h_ev_cap = 0;
-        double* h_beliefs = nullptr;    // small networks, bn_bp_run_batch: the kernel writes every set's marginals here (mapped) ...
+        PinnedBuf<double> h_beliefs;    // small networks, bn_bp_run_batch: the kernel writes every set's marginals here (mapped) ...
         double* h_beliefs_dev = nullptr;
         size_t h_beliefs_cap = 0;
         bool direct_out = false;        // ... when this is set for the run at hand
         bool beliefs_on_host = false;   // the last run's marginals are in h_beliefs, not d_beliefs
         size_t ev_b_node = 0, ev_b_off = 0, ev_b_val = 0;  // where the three arrays start inside d_ev
         std::vector<int64_t> ev_node_at, ev_off_at, ev_val_at;
-        Ctl* d_ctl = nullptr;       // per-sweep launches: one control block per set
+        DeviceBuf<Ctl> d_ctl;       // per-sweep launches: one control block per set
         bool rows_clean = true;     // ... and every set's residual slots are zero
         int32_t predicted_sweeps = 0;
-        Ctl* h_ctl = nullptr;       // pinned, [cap_sets]
+        PinnedBuf<Ctl> h_ctl;       // pinned, [cap_sets]
         Ctl* h_ctl_dev = nullptr;
-        char* d_ev = nullptr;       // staging of every set's evidence
+        DeviceBuf<char> d_ev;       // staging of every set's evidence
         size_t ev_cap = 0;
         // host copy of the evidence (sets run one after another when the network is not resident-eligible)
         std::vector<int32_t> ne, ev_node, ev_off;
@@ -230,38 +252,38 @@ struct bn_engine {
     SmallPlan small;
     bool small_ok = false;
     int small_mode = 1;             // option "small": 0 never, 1 where it was measured faster than the other paths, 2 wherever eligible
-    SmallEntry* d_s_ent = nullptr;
-    double* d_s_cpt = nullptr;
-    uint32_t* d_s_term = nullptr;
-    uint16_t* d_s_clist = nullptr;
-    SmallSlot* d_s_bslot = nullptr;
-    SmallSlot* d_s_cslot = nullptr;
-    int32_t* d_s_nvidx = nullptr;
-    int32_t* d_s_nvslot = nullptr;
-    double* d_s_init = nullptr;
-    double* d_s_state = nullptr;    // [2 M + 2 N] the state the last launch stopped in
-    int32_t* d_s_nodeoff = nullptr;
+    DeviceBuf<SmallEntry> d_s_ent;
+    DeviceBuf<double> d_s_cpt;
+    DeviceBuf<uint32_t> d_s_term;
+    DeviceBuf<uint16_t> d_s_clist;
+    DeviceBuf<SmallSlot> d_s_bslot;
+    DeviceBuf<SmallSlot> d_s_cslot;
+    DeviceBuf<int32_t> d_s_nvidx;
+    DeviceBuf<int32_t> d_s_nvslot;
+    DeviceBuf<double> d_s_init;
+    DeviceBuf<double> d_s_state;    // [2 M + 2 N] the state the last launch stopped in
+    DeviceBuf<int32_t> d_s_nodeoff;
     // networks beyond one workgroup's LDS, spread over up to 32 (bn_mid.hip): the same items, state in device memory
     MidPlan mid;
     bool mid_ok = false;
     int mid_mode = 1;               // option "mid": 0 never, 1 where eligible and the resident tiles do not cover the network, 2 wherever eligible
     int32_t small_cooldown = 0;     // (never set: the one-workgroup path waits for nobody; the path table wants a member)
     int32_t mid_cooldown = 0, mid_aborts = 0;   // runs left on the tile kernels after a grid wait gave up; how often that happened
-    MidPart* d_m_parts = nullptr;
-    SmallEntry* d_m_ent = nullptr;
-    double* d_m_cpt = nullptr;
-    uint32_t* d_m_term = nullptr;
-    uint16_t* d_m_clist = nullptr;
-    SmallSlot* d_m_bslot = nullptr;
-    SmallSlot* d_m_cslot = nullptr;
-    int32_t* d_m_nvidx = nullptr;
-    int32_t* d_m_nvslot = nullptr;
-    double* d_m_init = nullptr;
-    int32_t* d_m_nodeoff = nullptr;
-    int32_t* d_m_msgfirst = nullptr;
-    double* d_m_state = nullptr;    // [4 M + 4 N]: pi[2][M], lam[2][M], npi[2][N], nlam[2][N]
-    uint8_t* d_m_frz = nullptr;
-    char* d_m_sync = nullptr;       // per state slot kMidSyncBytes: the barrier counter, the three residual words, the group counters
+    DeviceBuf<MidPart> d_m_parts;
+    DeviceBuf<SmallEntry> d_m_ent;
+    DeviceBuf<double> d_m_cpt;
+    DeviceBuf<uint32_t> d_m_term;
+    DeviceBuf<uint16_t> d_m_clist;
+    DeviceBuf<SmallSlot> d_m_bslot;
+    DeviceBuf<SmallSlot> d_m_cslot;
+    DeviceBuf<int32_t> d_m_nvidx;
+    DeviceBuf<int32_t> d_m_nvslot;
+    DeviceBuf<double> d_m_init;
+    DeviceBuf<int32_t> d_m_nodeoff;
+    DeviceBuf<int32_t> d_m_msgfirst;
+    DeviceBuf<double> d_m_state;    // [4 M + 4 N]: pi[2][M], lam[2][M], npi[2][N], nlam[2][N]
+    DeviceBuf<uint8_t> d_m_frz;
+    DeviceBuf<char> d_m_sync;       // per state slot kMidSyncBytes: the barrier counter, the three residual words, the group counters
     int32_t mid_slots = 0;          // state slots allocated (1 for single queries; batches run several sets per launch)
     int32_t n_cus = 0;
     // k = 4 networks with up to 5 parents per node (BASELINE configs[1]): child tiles with the CPT in registers + parent items on
@@ -273,31 +295,14 @@ struct bn_engine {
     int32_t dag_flow_pause = 0;     // runs left on the barrier form after a dataflow launch gave up a wait
     int32_t dag_flow_max_nbr = 0;
     int last_dag_flow = 0;
-    int32_t* d_g_nbr = nullptr;
-    DagFlowSync* d_g_flow = nullptr;
     bool dag_ready = false;         // full plan built, device tables and image uploaded (ensure_dag)
     int32_t dag_cap = 224;          // the block cap the plan was built for
     int dag_mode = 1;               // option "dag": 0 never, 1 where eligible and no other one-launch path takes the network, 2 wherever eligible
     int32_t dag_cooldown = 0, dag_aborts = 0;   // runs left on the tile kernels after a grid wait gave up; how often that happened
-    DagTile* d_g_tiles = nullptr;
-    int32_t* d_g_slotptr = nullptr;
-    DagChildLane* d_g_cnode = nullptr;      // (tiles, parent lanes and out-edges: with state records in place of CSR ids, build_dag_device_tables)
-    DagParentLaneDev* d_g_pitem = nullptr;
-    int32_t* d_g_oedge = nullptr;
-    int32_t* d_g_eperm = nullptr;           // CSR edge id -> message record, node id -> slot of its vectors
-    int32_t* d_g_nperm = nullptr;
     DagDeviceTables dag_tables;             // (host copy, built with the plan -- also on host-only engines, where the CPU sanitizer run walks it; bn_bp_messages reads eperm)
-    double* d_g_cpt = nullptr;
-    double* d_g_init = nullptr;
-    int32_t* d_g_k = nullptr;       // networks with arities below 4 (DagPlan::uniform4 == false): arity, in-edge CSR and marginal offsets for the padded form
-    int32_t* d_g_inptr = nullptr;
-    int32_t* d_g_inidx = nullptr;
-    int64_t* d_g_noff = nullptr;
-    double* d_g_state = nullptr;    // pi-/lambda-messages (CSR edge order), pi(v), lambda(v): two buffers each (bn_dag.hpp dag_off_*)
-    uint8_t* d_g_frz = nullptr;
-    uint8_t dag_mark = 0;           // mark value of the evidence set applied to d_g_state / d_g_frz
+    DagImage dag_img;
+    uint8_t dag_mark = 0;           // mark value of the evidence set applied to dag_img.state / frz
     bool dag_ev_applied = false;    // ... and whether that is the set in force
-    ResidentSync* d_g_sync = nullptr;
     bool dag_sync_dirty = true;
     uint32_t dag_gen_base = 0;
     bool ev_deferred = false;       // the evidence in force sits in the staging block only: the one-workgroup kernel reads it there
@@ -310,7 +315,7 @@ struct bn_engine {
                                     // >= kResidentMinTiles tiles), 2 wherever eligible (tests, experiments)
     int32_t last_path = 0;          // 0 per-sweep launches, 2 one launch for the whole run (resident tiles), 3 one workgroup, state in LDS (bn_small.hip)
     int32_t last_flow = 0;          // ... in its dataflow form
-    Ctl* h_ctl = nullptr;  // pinned
+    PinnedBuf<Ctl> h_ctl;  // pinned
     Ctl* h_ctl_dev = nullptr;  // the same memory as the device sees it
     // run state
     int32_t res_cap = 1 << 16;
@@ -342,17 +347,17 @@ namespace bn_eng __attribute__((visibility("hidden"))) {
 extern RcclApi g_rccl;
 int load_rccl();
 
+// (both free what `dst` held first; a failed allocation leaves it empty)
 template <class T, class A>
-inline int upload(T** dst, const std::vector<T, A>& src, hipStream_t s) {
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(dst), bytes));
-    if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
+inline int upload(DeviceBuf<T>& dst, const std::vector<T, A>& src, hipStream_t s) {
+    HIPCHK(dev_malloc(dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
+    if (!src.empty()) HIPCHK(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return BN_OK;
 }
 
 template <class T>
-inline int dalloc(T** dst, size_t count) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(dst), std::max<size_t>(count, 1) * sizeof(T)));
+inline int dalloc(DeviceBuf<T>& dst, size_t count) {
+    HIPCHK(dev_malloc(dst, std::max<size_t>(count, 1) * sizeof(T)));
     return BN_OK;
 }
 

@@ -95,9 +95,9 @@ extern "C" int bn_peer_export(bn_engine* e, void* blob, int64_t cap) {
     h.rec_bytes = e->plan.rec_total_doubles * 8;
     if (!e->host_only && e->shard_shapes_ok) {
         ON_DEVICE(e);
-        h.flow_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_flow));
-        h.rec0_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_rec[0]));
-        h.rec1_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_rec[1]));
+        h.flow_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_flow.get()));
+        h.rec0_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_rec[0].get()));
+        h.rec1_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_rec[1].get()));
         HIPCHK(hipIpcGetMemHandle(&h.h_flow, e->d_flow));
         HIPCHK(hipIpcGetMemHandle(&h.h_rec0, e->d_rec[0]));
         HIPCHK(hipIpcGetMemHandle(&h.h_rec1, e->d_rec[1]));
@@ -175,13 +175,10 @@ extern "C" int bn_peer_import(bn_engine* e, const void* const* blobs, const int6
             peers[r] = PeerTable{static_cast<FlowSync*>(q[0]), static_cast<double*>(q[1]), static_cast<double*>(q[2]), hd[r].g_base, hd[r].rec_bytes};
         }
     }
-    if (e->d_peers) { (void)hipFree(e->d_peers); e->d_peers = nullptr; }
-    if (e->d_pub_mask) { (void)hipFree(e->d_pub_mask); e->d_pub_mask = nullptr; }
-    if (e->d_nbr) { (void)hipFree(e->d_nbr); e->d_nbr = nullptr; }
-    int rc;
-    if ((rc = upload(&e->d_peers, peers, e->stream))) return rc;
-    if ((rc = upload(&e->d_pub_mask, e->pub_mask, e->stream))) return rc;
-    if ((rc = upload(&e->d_nbr, p.nbr, e->stream))) return rc;
+    int rc;   // (each upload frees the engine's earlier table first)
+    if ((rc = upload(e->d_peers, peers, e->stream))) return rc;
+    if ((rc = upload(e->d_pub_mask, e->pub_mask, e->stream))) return rc;
+    if ((rc = upload(e->d_nbr, p.nbr, e->stream))) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->shard_flow_ok = true;
     return BN_OK;

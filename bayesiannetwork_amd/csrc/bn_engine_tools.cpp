@@ -69,7 +69,7 @@ extern "C" int bn_dag_plan_get(bn_engine* e, int32_t* dims_out, int32_t* tiles, 
 // register image of the DAG path, the initial pi(v) of the roots -- from the new flat array and copies them over the old ones;
 // the sampler state is rebuilt at its next call.  No allocation changes size.
 template <class T, class A>
-static int reupload(T* dst, const std::vector<T, A>& src, size_t expect, hipStream_t s, const char* what) {
+static int reupload(const DeviceBuf<T>& dst, const std::vector<T, A>& src, size_t expect, hipStream_t s, const char* what) {
     if (src.size() != expect) return fail(BN_ERR_STATE, std::string("bn_reload_cpt: the ") + what + " changed size (structure changed?)");
     if (!src.empty()) HIPCHK(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return BN_OK;
@@ -150,12 +150,12 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
             if ((rc = reupload(e->d_m_init, e->mid.parts[0].npi_init, e->mid.parts[0].npi_init.size(), s, "initial pi"))) return rc;
         }
         if (e->dag_ready) {
-            if ((rc = reupload(e->d_g_cpt, e->dag.cpt_img, e->dag.cpt_img.size(), s, "register image"))) return rc;
-            if ((rc = reupload(e->d_g_init, e->dag.npi_init, e->dag.npi_init.size(), s, "initial pi"))) return rc;
+            if ((rc = reupload(e->dag_img.cpt, e->dag.cpt_img, e->dag.cpt_img.size(), s, "register image"))) return rc;
+            if ((rc = reupload(e->dag_img.init, e->dag.npi_init, e->dag.npi_init.size(), s, "initial pi"))) return rc;
         }
         HIPCHK(hipStreamSynchronize(s));
         BigVec().swap(p.cpt_striped);
-        lw_free(e->lw);   // the sampler uploads its copy of the tables at its next call
+        e->lw = LwState();   // the sampler uploads its copy of the tables at its next call
         e->poisoned = false;
     } catch (const std::bad_alloc&) {
         if (swapped_flat && !e->poisoned) p.cpt_flat.swap(old_flat);   // phase 1: nothing was committed
@@ -321,36 +321,31 @@ extern "C" int bn_fit_cpt(const bn_model_desc* desc, int64_t n_patterns, const u
     for (int32_t v = 0; v < n; ++v)
         for (int64_t o = cpt_off[v]; o < cpt_off[v + 1]; o += k[v]) { row_node.push_back(v); row_off.push_back(o); }
     const size_t entries = size_t(cpt_off[n]);
-    hipStream_t s = nullptr;
-    uint8_t* d_pat = nullptr; unsigned long long* d_w = nullptr; unsigned long long* d_cnt = nullptr;
-    int32_t *d_k = nullptr, *d_ptr = nullptr, *d_idx = nullptr, *d_rn = nullptr;
-    int64_t *d_off = nullptr, *d_ro = nullptr; double* d_out = nullptr;
-    int rc = [&]() -> int {
-        int r;
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        if ((r = upload(&d_pat, tr, s))) return r;
-        std::vector<unsigned long long> w(counts, counts + n_patterns);
-        if ((r = upload(&d_w, w, s))) return r;
-        if ((r = upload(&d_k, k, s))) return r;
-        if ((r = upload(&d_ptr, in_ptr, s))) return r;
-        if ((r = upload(&d_idx, in_idx, s))) return r;
-        if ((r = upload(&d_off, cpt_off, s))) return r;
-        if ((r = upload(&d_rn, row_node, s))) return r;
-        if ((r = upload(&d_ro, row_off, s))) return r;
-        if ((r = dalloc(&d_cnt, entries))) return r;
-        if ((r = dalloc(&d_out, entries))) return r;
-        HIPCHK(hipMemsetAsync(d_cnt, 0, std::max<size_t>(entries, 1) * 8, s));
-        FitArgs a{n, d_k, d_ptr, d_idx, d_off, n_patterns, d_pat, d_w, d_cnt, int64_t(row_node.size()), d_rn, d_ro, d_out};
-        if (launch_fit(a, s)) return fail(BN_ERR_HIP, "fit kernel launch failed");
-        if (entries) HIPCHK(hipMemcpyAsync(cpt_out, d_out, entries * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return BN_OK;
-    }();
-    void* ptrs[] = {d_pat, d_w, d_cnt, d_k, d_ptr, d_idx, d_rn, d_off, d_ro, d_out};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    const std::vector<unsigned long long> w(counts, counts + n_patterns);
+    StreamOwner s;   // (declared first: destroyed after the buffers)
+    DeviceBuf<uint8_t> d_pat;
+    DeviceBuf<unsigned long long> d_w, d_cnt;
+    DeviceBuf<int32_t> d_k, d_ptr, d_idx, d_rn;
+    DeviceBuf<int64_t> d_off, d_ro;
+    DeviceBuf<double> d_out;
+    int r;
+    HIPCHK(hipStreamCreateWithFlags(s.put(), hipStreamNonBlocking));
+    if ((r = upload(d_pat, tr, s))) return r;
+    if ((r = upload(d_w, w, s))) return r;
+    if ((r = upload(d_k, k, s))) return r;
+    if ((r = upload(d_ptr, in_ptr, s))) return r;
+    if ((r = upload(d_idx, in_idx, s))) return r;
+    if ((r = upload(d_off, cpt_off, s))) return r;
+    if ((r = upload(d_rn, row_node, s))) return r;
+    if ((r = upload(d_ro, row_off, s))) return r;
+    if ((r = dalloc(d_cnt, entries))) return r;
+    if ((r = dalloc(d_out, entries))) return r;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, std::max<size_t>(entries, 1) * 8, s));
+    FitArgs a{n, d_k, d_ptr, d_idx, d_off, n_patterns, d_pat, d_w, d_cnt, int64_t(row_node.size()), d_rn, d_ro, d_out};
+    if (launch_fit(a, s)) return fail(BN_ERR_HIP, "fit kernel launch failed");
+    if (entries) HIPCHK(hipMemcpyAsync(cpt_out, d_out, entries * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BN_OK;
 }
 
 extern "C" int bn_lw_states(bn_engine* e, uint64_t n, uint8_t* states_out, double* weights_out) {

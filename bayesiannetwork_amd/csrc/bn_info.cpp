@@ -15,18 +15,16 @@ struct bn_info_table {
     std::vector<int32_t> k;
     double Nd = 0.0;
     hipStream_t stream = nullptr;
-    uint8_t* d_T = nullptr;
-    unsigned long long* d_w = nullptr;
-    uint8_t* d_wd = nullptr;
+    DeviceBuf<uint8_t> d_T;
+    DeviceBuf<unsigned long long> d_w;
+    DeviceBuf<uint8_t> d_wd;
     float last_pairs_ms = 0.0f;
 
     InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
-    ~bn_info_table() {
+    ~bn_info_table() {   // (the members' own destructors would run after the guard's)
         DeviceGuard g;
         (void)g.enter(device);
-        void* ptrs[] = {d_T, d_w, d_wd};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
+        d_T.reset(); d_w.reset(); d_wd.reset();
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -116,32 +114,25 @@ extern "C" int bn_info_create(int64_t n_patterns, int32_t n_vars, const uint8_t*
     while (bits < 64 && (maxc >> bits)) ++bits;
     t->D = std::max(1, (bits + 6) / 7);
     HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    uint8_t* d_raw = nullptr;
-    int32_t* d_k = nullptr;
-    unsigned* d_bad = nullptr;
+    DeviceBuf<uint8_t> d_raw;
+    DeviceBuf<int32_t> d_k;
+    DeviceBuf<unsigned> d_bad;
     unsigned bad = 0;
-    int rc = [&]() -> int {
-        const size_t raw_bytes = size_t(n_patterns) * size_t(n_vars);
-        if (int r = dalloc(&d_raw, raw_bytes)) return r;
-        if (int r = dalloc(&t->d_T, size_t(n_vars) * size_t(t->Ppad))) return r;
-        if (int r = dalloc(&t->d_w, size_t(n_patterns))) return r;
-        if (int r = dalloc(&t->d_wd, size_t(t->D) * size_t(t->Ppad))) return r;
-        if (int r = upload(&d_k, t->k, t->stream)) return r;
-        if (int r = dalloc(&d_bad, 1)) return r;
-        HIPCHK(hipMemsetAsync(d_bad, 0, 4, t->stream));
-        if (raw_bytes) HIPCHK(hipMemcpyAsync(d_raw, patterns, raw_bytes, hipMemcpyHostToDevice, t->stream));
-        if (n_patterns) HIPCHK(hipMemcpyAsync(t->d_w, counts, size_t(n_patterns) * 8, hipMemcpyHostToDevice, t->stream));
-        int e = info_launch_transpose(d_raw, n_patterns, n_vars, t->Ppad, d_k, t->d_T, d_bad, t->stream);
-        if (!e) e = info_launch_digits(t->d_w, n_patterns, t->Ppad, t->D, t->d_wd, t->stream);
-        if (e) return fail(BN_ERR_HIP, std::string("table kernels: ") + hipGetErrorString(hipError_t(e)));
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->stream));
-        HIPCHK(hipStreamSynchronize(t->stream));
-        return BN_OK;
-    }();
-    void* ptrs[] = {d_raw, d_k, d_bad};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    if (rc) return rc;
+    const size_t raw_bytes = size_t(n_patterns) * size_t(n_vars);
+    if (int r = dalloc(d_raw, raw_bytes)) return r;
+    if (int r = dalloc(t->d_T, size_t(n_vars) * size_t(t->Ppad))) return r;
+    if (int r = dalloc(t->d_w, size_t(n_patterns))) return r;
+    if (int r = dalloc(t->d_wd, size_t(t->D) * size_t(t->Ppad))) return r;
+    if (int r = upload(d_k, t->k, t->stream)) return r;
+    if (int r = dalloc(d_bad, 1)) return r;
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, t->stream));
+    if (raw_bytes) HIPCHK(hipMemcpyAsync(d_raw, patterns, raw_bytes, hipMemcpyHostToDevice, t->stream));
+    if (n_patterns) HIPCHK(hipMemcpyAsync(t->d_w, counts, size_t(n_patterns) * 8, hipMemcpyHostToDevice, t->stream));
+    int e = info_launch_transpose(d_raw, n_patterns, n_vars, t->Ppad, d_k, t->d_T, d_bad, t->stream);
+    if (!e) e = info_launch_digits(t->d_w, n_patterns, t->Ppad, t->D, t->d_wd, t->stream);
+    if (e) return fail(BN_ERR_HIP, std::string("table kernels: ") + hipGetErrorString(hipError_t(e)));
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
     if (bad) return fail(BN_ERR_ARG, "pattern state out of range (a state >= its column's arity)");
     *out = t.release();
     return BN_OK;
@@ -195,46 +186,37 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
     for (size_t i = 0; i < size_t(m) * size_t(m); ++i) hxy[i] = 0.0;
     t->last_pairs_ms = 0.0f;
     if (Kpad > 0) {
-        int32_t *d_ci = nullptr, *d_cv = nullptr, *d_ss = nullptr, *d_sk = nullptr, *d_sc = nullptr, *d_su = nullptr;
-        double *d_hxy = nullptr, *d_h = nullptr;
-        int64_t* d_off = nullptr;
-        unsigned long long* d_dump = nullptr;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        int rc = [&]() -> int {
-            int r;
-            if ((r = upload(&d_ci, colinfo, t->stream)) || (r = upload(&d_cv, colvar, t->stream)) || (r = upload(&d_ss, sv_start, t->stream)) ||
-                (r = upload(&d_sk, sv_k, t->stream)) || (r = upload(&d_sc, sv_col, t->stream)) || (r = upload(&d_su, sv_user, t->stream)))
-                return r;
-            if ((r = dalloc(&d_hxy, size_t(m) * size_t(m))) || (r = dalloc(&d_h, size_t(m)))) return r;
-            HIPCHK(hipMemsetAsync(d_hxy, 0, size_t(m) * size_t(m) * 8, t->stream));
-            if (dump_off) {
-                if ((r = upload(&d_off, *dump_off, t->stream)) || (r = dalloc(&d_dump, dump_len))) return r;
-                HIPCHK(hipMemsetAsync(d_dump, 0, std::max<size_t>(dump_len, 1) * 8, t->stream));
-            }
-            HIPCHK(hipEventCreate(&ev0));
-            HIPCHK(hipEventCreate(&ev1));
-            PairArgs a{t->d_T, t->Ppad, t->d_wd, t->D, int32_t(Kpad / kInfoTile), d_ci, d_cv, d_ss, d_sk, d_sc, d_su, m, t->Nd,
-                       d_hxy, d_h, d_off, d_dump};
-            const bool flush = t->D > 1 || t->Ppad > kInfoSegment;
-            HIPCHK(hipEventRecord(ev0, t->stream));
-            if (int e = info_launch_pairs(a, flush, t->stream))
-                return fail(BN_ERR_HIP, std::string("all-pairs kernel: ") + hipGetErrorString(hipError_t(e)));
-            HIPCHK(hipEventRecord(ev1, t->stream));
-            HIPCHK(hipMemcpyAsync(hxy, d_hxy, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
-            std::vector<double> hs(static_cast<size_t>(m));
-            HIPCHK(hipMemcpyAsync(hs.data(), d_h, size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
-            if (dump_off) HIPCHK(hipMemcpyAsync(dump_host, d_dump, dump_len * 8, hipMemcpyDeviceToHost, t->stream));
-            HIPCHK(hipStreamSynchronize(t->stream));
-            HIPCHK(hipEventElapsedTime(&t->last_pairs_ms, ev0, ev1));
-            for (int32_t u : order) h[u] = hs[size_t(u)];
-            return BN_OK;
-        }();
-        void* ptrs[] = {d_ci, d_cv, d_ss, d_sk, d_sc, d_su, d_hxy, d_h, d_off, d_dump};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (rc) return rc;
+        EventOwner ev0, ev1;
+        DeviceBuf<int32_t> d_ci, d_cv, d_ss, d_sk, d_sc, d_su;
+        DeviceBuf<double> d_hxy, d_h;
+        DeviceBuf<int64_t> d_off;
+        DeviceBuf<unsigned long long> d_dump;
+        int r;
+        if ((r = upload(d_ci, colinfo, t->stream)) || (r = upload(d_cv, colvar, t->stream)) || (r = upload(d_ss, sv_start, t->stream)) ||
+            (r = upload(d_sk, sv_k, t->stream)) || (r = upload(d_sc, sv_col, t->stream)) || (r = upload(d_su, sv_user, t->stream)))
+            return r;
+        if ((r = dalloc(d_hxy, size_t(m) * size_t(m))) || (r = dalloc(d_h, size_t(m)))) return r;
+        HIPCHK(hipMemsetAsync(d_hxy, 0, size_t(m) * size_t(m) * 8, t->stream));
+        if (dump_off) {
+            if ((r = upload(d_off, *dump_off, t->stream)) || (r = dalloc(d_dump, dump_len))) return r;
+            HIPCHK(hipMemsetAsync(d_dump, 0, std::max<size_t>(dump_len, 1) * 8, t->stream));
+        }
+        HIPCHK(hipEventCreate(ev0.put()));
+        HIPCHK(hipEventCreate(ev1.put()));
+        PairArgs a{t->d_T, t->Ppad, t->d_wd, t->D, int32_t(Kpad / kInfoTile), d_ci, d_cv, d_ss, d_sk, d_sc, d_su, m, t->Nd,
+                   d_hxy, d_h, d_off, d_dump};
+        const bool flush = t->D > 1 || t->Ppad > kInfoSegment;
+        HIPCHK(hipEventRecord(ev0, t->stream));
+        if (int e = info_launch_pairs(a, flush, t->stream))
+            return fail(BN_ERR_HIP, std::string("all-pairs kernel: ") + hipGetErrorString(hipError_t(e)));
+        HIPCHK(hipEventRecord(ev1, t->stream));
+        HIPCHK(hipMemcpyAsync(hxy, d_hxy, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
+        std::vector<double> hs(static_cast<size_t>(m));
+        HIPCHK(hipMemcpyAsync(hs.data(), d_h, size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
+        if (dump_off) HIPCHK(hipMemcpyAsync(dump_host, d_dump, dump_len * 8, hipMemcpyDeviceToHost, t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+        HIPCHK(hipEventElapsedTime(&t->last_pairs_ms, ev0, ev1));
+        for (int32_t u : order) h[u] = hs[size_t(u)];
     }
     // pairs with a column of arity > 32: one dense joint table each (the single call's route, so its bits)
     for (int32_t x : wide)

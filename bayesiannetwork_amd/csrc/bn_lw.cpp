@@ -22,15 +22,6 @@ namespace bnmi {
         }                                                                      \
     } while (0)
 
-void lw_free(LwState& s) {
-    void* ptrs[] = {s.d_k, s.d_node_off, s.d_cpt, s.d_thr, s.d_thr32, s.d_thr16, s.d_steps, s.d_small_steps, s.d_parents, s.d_ev_topo, s.d_states, s.d_weights, s.d_hist};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (s.h_ev) (void)hipHostFree(s.h_ev);
-    if (s.h_hist) (void)hipHostFree(s.h_hist);
-    s = LwState();
-}
-
 // Kahn's algorithm with a min-heap on node id: deterministic, and the identity permutation when
 // every parent precedes its children.  Any topological order samples the reference's
 // distribution (its own order is a DFS from the last vertex, likelihood_weighting.hpp:162-170).
@@ -62,9 +53,9 @@ static bool topo_order(const Plan& p, std::vector<int32_t>& topo) {
 }
 
 template <class T>
-static int up(T** dst, const T* src, size_t count, hipStream_t st, std::string& err) {
-    LWCHK(hipMalloc(reinterpret_cast<void**>(dst), std::max<size_t>(count, 1) * sizeof(T)));
-    if (count) LWCHK(hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+static int up(DeviceBuf<T>& dst, const T* src, size_t count, hipStream_t st, std::string& err) {
+    LWCHK(dev_malloc(dst, std::max<size_t>(count, 1) * sizeof(T)));
+    if (count) LWCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -157,9 +148,9 @@ static int lw_prepare(LwState& s, const Plan& p, hipStream_t st, uint64_t want_s
         }
         for (int q = 0; q < 4; ++q) parents.push_back(LwParent{0, 1});
         int r;
-        if ((r = up(&s.d_k, p.k.data(), p.k.size(), st, err))) return r;
-        if ((r = up(&s.d_node_off, p.node_off.data(), p.node_off.size(), st, err))) return r;
-        if ((r = up(&s.d_cpt, p.cpt_flat.data(), p.cpt_flat.size(), st, err))) return r;
+        if ((r = up(s.d_k, p.k.data(), p.k.size(), st, err))) return r;
+        if ((r = up(s.d_node_off, p.node_off.data(), p.node_off.size(), st, err))) return r;
+        if ((r = up(s.d_cpt, p.cpt_flat.data(), p.cpt_flat.size(), st, err))) return r;
         {   // selection thresholds: the running totals of every row, added up left to right as make_random_by_weight does
             // (likelihood_weighting.hpp:177-193), as integers ceil(total * 2^53): "u >= total" for u = U * 2^-53 is "U >= threshold"
             std::vector<unsigned long long> thr(p.cpt_flat.size(), ~0ull);
@@ -188,19 +179,19 @@ static int lw_prepare(LwState& s, const Plan& p, hipStream_t st, uint64_t want_s
                     t16[q + 1] = e[2] | 0xffff0000u;
                 }
             }
-            if ((r = up(&s.d_thr16, t16.data(), t16.size(), st, err))) return r;
-            if ((r = up(&s.d_thr, thr.data(), thr.size(), st, err))) return r;
-            if ((r = up(&s.d_thr32, top.data(), top.size(), st, err))) return r;
+            if ((r = up(s.d_thr16, t16.data(), t16.size(), st, err))) return r;
+            if ((r = up(s.d_thr, thr.data(), thr.size(), st, err))) return r;
+            if ((r = up(s.d_thr32, top.data(), top.size(), st, err))) return r;
             LWCHK(hipStreamSynchronize(st));  // `thr`, `top` are locals
         }
-        if ((r = up(&s.d_steps, steps.data(), steps.size(), st, err))) return r;
-        if ((r = up(&s.d_parents, parents.data(), parents.size(), st, err))) return r;
+        if ((r = up(s.d_steps, steps.data(), steps.size(), st, err))) return r;
+        if ((r = up(s.d_parents, parents.data(), parents.size(), st, err))) return r;
         LWCHK(hipStreamSynchronize(st));  // steps / parents are locals
-        LWCHK(hipMalloc(reinterpret_cast<void**>(&s.d_ev_topo), (size_t(p.n) + 3) * sizeof(int32_t)));
+        LWCHK(dev_malloc(s.d_ev_topo, (size_t(p.n) + 3) * sizeof(int32_t)));
         LWCHK(hipMemsetAsync(s.d_ev_topo, 0xff, (size_t(p.n) + 3) * sizeof(int32_t), st));
-        LWCHK(hipMalloc(reinterpret_cast<void**>(&s.d_hist), std::max<size_t>(p.node_off[p.n], 1) * sizeof(double)));
-        LWCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_ev), (size_t(p.n) + 1) * sizeof(int32_t), hipHostMallocDefault));
-        LWCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_hist), std::max<size_t>(p.node_off[p.n], 1) * sizeof(double), hipHostMallocDefault));
+        LWCHK(dev_malloc(s.d_hist, std::max<size_t>(p.node_off[p.n], 1) * sizeof(double)));
+        LWCHK(host_malloc(s.h_ev, (size_t(p.n) + 1) * sizeof(int32_t), hipHostMallocDefault));
+        LWCHK(host_malloc(s.h_hist, std::max<size_t>(p.node_off[p.n], 1) * sizeof(double), hipHostMallocDefault));
         s.ready = true;
     }
     // batch: enough blocks to fill the chip, bounded so the [node][sample] state matrix stays
@@ -219,21 +210,19 @@ static int lw_prepare(LwState& s, const Plan& p, hipStream_t st, uint64_t want_s
     // batch -- were tried in round 5: 7.4 vs 7.5 ns per sample: waves of a half-empty second round simply run faster.)
     s.launch_samples = batch;   // (the state matrix may be larger, from an earlier call: its rows stay as long as they are)
     if (batch > s.batch) {
-        if (s.d_states) (void)hipFree(s.d_states);
-        if (s.d_weights) (void)hipFree(s.d_weights);
-        s.d_states = nullptr;
-        s.d_weights = nullptr;
+        s.d_states.reset();
+        s.d_weights.reset();
         s.batch = 0;    // (a failure below leaves nothing that claims to be allocated: the next call starts over)
         s.stride = 0;
         // Row stride = the row's bytes + 33 x 128: never a power of two.  With rows exactly 2^21 bytes apart the histogram pass, whose 64
         // lanes read 64 consecutive rows at the same offset, ran 48 % slower per sample (4.1 vs 2.7 ns) -- every lane's line in the
         // same cache set / memory channel.
         const uint64_t stride = batch / per_byte + 33 * 128;
-        LWCHK(hipMalloc(reinterpret_cast<void**>(&s.d_states), (uint64_t(p.n) + 1) * stride));
+        LWCHK(dev_malloc(s.d_states, (uint64_t(p.n) + 1) * stride));
         LWCHK(hipMemsetAsync(s.d_states + uint64_t(p.n) * stride, 0, stride, st));   // row n: all zero (the generic kernel's "parent" of nodes with fewer than four inline parents)
         if (s.small) {   // the descriptors hold ADDRESSES: of rows of this state matrix, of the tables in d_thr16
             std::vector<LwSmallStep> dev(s.h_small);
-            const uint64_t st_base = reinterpret_cast<uint64_t>(s.d_states), th_base = reinterpret_cast<uint64_t>(s.d_thr16);
+            const uint64_t st_base = reinterpret_cast<uint64_t>(s.d_states.get()), th_base = reinterpret_cast<uint64_t>(s.d_thr16.get());
             for (LwSmallStep& ss : dev) {
                 for (uint64_t& x : ss.par) x = st_base + x * stride;
                 ss.own = st_base + ss.own * stride;
@@ -244,12 +233,12 @@ static int lw_prepare(LwState& s, const Plan& p, hipStream_t st, uint64_t want_s
                 ss.tab[2] = bytes;
                 ss.tab[3] = 0x00020000u;                    // raw buffer, dword data format
             }
-            if (!s.d_small_steps) LWCHK(hipMalloc(reinterpret_cast<void**>(&s.d_small_steps), dev.size() * sizeof(LwSmallStep)));
+            if (!s.d_small_steps) LWCHK(dev_malloc(s.d_small_steps, dev.size() * sizeof(LwSmallStep)));
             LWCHK(hipMemcpyAsync(s.d_small_steps, dev.data(), dev.size() * sizeof(LwSmallStep), hipMemcpyHostToDevice, st));
             LWCHK(hipStreamSynchronize(st));   // `dev` is a local
         }
         s.stride = stride;
-        LWCHK(hipMalloc(reinterpret_cast<void**>(&s.d_weights), batch * sizeof(double)));
+        LWCHK(dev_malloc(s.d_weights, batch * sizeof(double)));
         s.batch = batch;
     }
     return 0;
@@ -341,13 +330,11 @@ int lw_states(LwState& s, const Plan& p, void* stream, uint64_t n, uint8_t* stat
     if (!s.ready || s.last_batch_samples == 0) { err = "no likelihood-weighting run yet"; return BN_ERR_STATE; }
     if (n > s.last_batch_samples) { err = "more samples requested than the last batch holds"; return BN_ERR_ARG; }
     if (states_out && n > 0) {   // transposed on the device (sample-major), then one copy
-        uint8_t* d_t = nullptr;
-        LWCHK(hipMalloc(reinterpret_cast<void**>(&d_t), n * uint64_t(p.n)));
-        int rc = launch_lw_transpose(s.d_states, d_t, p.n, s.stride, s.small, n, st);
-        hipError_t ce = rc ? hipSuccess : hipMemcpyAsync(states_out, d_t, n * uint64_t(p.n), hipMemcpyDeviceToHost, st);
-        if (!rc && ce == hipSuccess) ce = hipStreamSynchronize(st);
-        (void)hipFree(d_t);
-        if (rc) { err = "transpose kernel launch failed"; return BN_ERR_HIP; }
+        DeviceBuf<uint8_t> d_t;
+        LWCHK(dev_malloc(d_t, n * uint64_t(p.n)));
+        if (launch_lw_transpose(s.d_states, d_t, p.n, s.stride, s.small, n, st)) { err = "transpose kernel launch failed"; return BN_ERR_HIP; }
+        hipError_t ce = hipMemcpyAsync(states_out, d_t, n * uint64_t(p.n), hipMemcpyDeviceToHost, st);
+        if (ce == hipSuccess) ce = hipStreamSynchronize(st);
         if (ce != hipSuccess) { err = std::string("copying the sampled states: ") + hipGetErrorString(ce); return BN_ERR_HIP; }
     }
     if (weights_out) {

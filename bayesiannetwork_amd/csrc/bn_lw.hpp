@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "bn_buffer.hpp"
 #include "bn_plan.hpp"
 
 namespace bnmi {
@@ -49,30 +50,30 @@ struct LwParent {
 
 struct LwState {
     bool ready = false;
-    int32_t* d_k = nullptr;
-    int64_t* d_node_off = nullptr;
-    double* d_cpt = nullptr;       // flat, reference row order (row lookup = k contiguous doubles)
-    unsigned long long* d_thr = nullptr;  // same layout: entry i of a row = ceil(running total up to state i x 2^53), the selection thresholds (bn_lw_kernels.hip pick_states)
-    uint32_t* d_thr32 = nullptr;   // ... and their top halves (threshold >> 21): what a draw is compared with first, 4 bytes per entry
-    uint32_t* d_thr16 = nullptr;   // nodes with <= 256 rows (kLwStepPacked): per row 8 bytes {t0 | t1 << 16, t2 | 0xffff << 16}, t = threshold >> 37 -- the copy a wave stages in LDS
-    LwStep* d_steps = nullptr;
-    LwSmallStep* d_small_steps = nullptr;   // [n + 3] in topological order (LwState::small), written for the state matrix in use (d_states, batch)
+    DeviceBuf<int32_t> d_k;
+    DeviceBuf<int64_t> d_node_off;
+    DeviceBuf<double> d_cpt;       // flat, reference row order (row lookup = k contiguous doubles)
+    DeviceBuf<unsigned long long> d_thr;  // same layout: entry i of a row = ceil(running total up to state i x 2^53), the selection thresholds (bn_lw_kernels.hip pick_states)
+    DeviceBuf<uint32_t> d_thr32;   // ... and their top halves (threshold >> 21): what a draw is compared with first, 4 bytes per entry
+    DeviceBuf<uint32_t> d_thr16;   // nodes with <= 256 rows (kLwStepPacked): per row 8 bytes {t0 | t1 << 16, t2 | 0xffff << 16}, t = threshold >> 37 -- the copy a wave stages in LDS
+    DeviceBuf<LwStep> d_steps;
+    DeviceBuf<LwSmallStep> d_small_steps;   // [n + 3] in topological order (LwState::small), written for the state matrix in use (d_states, batch)
     std::vector<LwSmallStep> h_small;       // the same with NODE numbers in par / own and {first row in d_thr16, bytes} in tab[0..1]: what the device copy is made from
-    LwParent* d_parents = nullptr; // [E] grouped by position, first parent first
-    int32_t* d_ev_topo = nullptr;  // [n] clamped state or -1 of the node at each position
+    DeviceBuf<LwParent> d_parents; // [E] grouped by position, first parent first
+    DeviceBuf<int32_t> d_ev_topo;  // [n] clamped state or -1 of the node at each position
     int32_t kmax = 0;              // largest arity
     bool rows24 = false;           // every CPT has < 2^24 rows: 24-bit row arithmetic
     bool inline_parents = false;   // n <= 2^24: LwStep::par is filled
     bool small = false;            // every node has <= 4 parents, <= 256 CPT rows and <= 4 states (and n < 2^24 - 1): lw_sample_small_kernel; LwStep::par of a
                                    // missing parent then names the all-zero row n of the state matrix with arity 1
     bool small_pow2 = false;       // ... and every arity is a power of two: LwStep::par holds log2 of the arity in its top byte
-    uint8_t* d_states = nullptr;   // sampled states of the current batch, [n + 1] rows of `stride` bytes: one byte per sample, or -- LwState::small,
+    DeviceBuf<uint8_t> d_states;   // sampled states of the current batch, [n + 1] rows of `stride` bytes: one byte per sample, or -- LwState::small,
                                    // every arity <= 4 -- FOUR samples per byte, two bits each (sample s: bits 2 (s & 3) of byte s >> 2)
     uint64_t stride = 0;           // bytes per row of d_states: batch (or batch / 4) + 33 x 128
-    double* d_weights = nullptr;   // [batch]
-    double* d_hist = nullptr;      // [sum k]
-    int32_t* h_ev = nullptr;       // page-locked staging of d_ev_topo: the upload needs no synchronisation of its own
-    double* h_hist = nullptr;      // page-locked landing place of the histogram
+    DeviceBuf<double> d_weights;   // [batch]
+    DeviceBuf<double> d_hist;      // [sum k]
+    PinnedBuf<int32_t> h_ev;       // page-locked staging of d_ev_topo: the upload needs no synchronisation of its own
+    PinnedBuf<double> h_hist;      // page-locked landing place of the histogram
     uint64_t batch = 0;            // samples a row of d_states holds (multiple of kLwBlockSamples)
     uint64_t launch_samples = 0;   // samples per launch of the current call (<= batch, the row stride)
     uint64_t last_batch_samples = 0;
@@ -110,7 +111,6 @@ int launch_lw_sample(const LwArgs& a, int blocks, void* stream);
 int launch_lw_hist(const LwArgs& a, int blocks, void* stream);
 int launch_lw_transpose(const uint8_t* states, uint8_t* out, int32_t n, uint64_t stride, bool packed2, uint64_t n_samples, void* stream);
 
-void lw_free(LwState& s);
 // hist_out == nullptr: leave the histogram in s.d_hist (the caller reduces it across ranks first)
 int lw_run(LwState& s, const Plan& p, void* stream, int32_t ne, const int32_t* ev_node, const int32_t* ev_state,
            uint64_t sample_begin, uint64_t n_samples, uint64_t seed, double* hist_out, std::string& err);
