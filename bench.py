@@ -6,7 +6,9 @@ maximum_difference < eps, beliefs) on the 316x316 k=4 grid BN with 1 % hard evid
 evidence already resident in HBM.  value = 2E * sweeps * steps / wall time, whole job.
 One JSON line on stdout (rank 0).  See DESIGN.md "Measurement" for the definitions.
 
-The default single-GPU line also carries, as extra keys measured after the timed region,
+A plain single-GPU run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+With --full the line also carries the roofline record (HIP-event repeat of the steps, HBM stream yardstick), the
+cpu_baseline legs (--no-cpu skips them) and, as extra keys measured after the timed region (--no-extras skips them),
   value_host_to_host : SURVEY 8(d)'s definition -- evidence upload to beliefs on the host (PCIe inclusive)
   config1_alarm      : BASELINE configs[0]'s network on the GPU: the ALARM-shaped 37-node net (queries per second)
   mid_mixed300       : a 300-node network of mixed arities (2-5), <= 3 parents: beyond one workgroup's LDS (bn_mid.hip)
@@ -16,7 +18,7 @@ The default single-GPU line also carries, as extra keys measured after the timed
   grid2048           : the HBM-resident point (4.2 M nodes, 3.76 GB per sweep)
   batch              : 2 / 4 / 8 evidence sets per call on the headline grid (bn_bp_run_batch_device)
   dropin_cpp         : the class surface, bn::inference::belief_propagation::operator() / run(), timed in C++ (tests/cpp/bench_dropin.cpp)
-each with its own value / roofline / cpu_baseline (--no-extras skips them).
+each with its own value / roofline / cpu_baseline.
 """
 from __future__ import annotations
 
@@ -163,9 +165,10 @@ def measured_stream_gbs(torch, device=0):
     return out
 
 
-def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None, keep_last=False):
+def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None, keep_last=False, events=True):
     """`steps` runs to convergence on the staged evidence, bracketed by synchronize on both sides, with
-    nothing but the run itself in the timed region.  Two clocks give the sweep launch duration:
+    nothing but the run itself in the timed region.  With `events` (what roofline_of needs), two clocks give the sweep
+    launch duration:
       * the device's own 100 MHz clock, read by the kernels at the first sweep's start and the last
         sweep's end of every timed run (bn_bp_stats.sweep_devclock_ms; free, so it covers the timed region);
       * HIP events the library records on ITS stream around every batch of sweep launches ("timing"
@@ -193,7 +196,9 @@ def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None, keep_last=False
     # keep_last: what the last timed step gave its caller (beliefs copied off the device only now, outside the timed region;
     # the event repeats below overwrite them)
     last = {"beliefs": eng.bp_beliefs(), "sweeps": r["sweeps"], "residual": r["residual"]} if keep_last else None
-    path = eng.last_path()
+    t = {"dt": dt, "sweeps_total": sweeps_total, "msgs": g.messages_per_sweep() * sweeps_total, "path": eng.last_path(), "last": last}
+    if not events:
+        return t
     eng.set_option("timing", 1)
     ev_steps = event_steps if event_steps is not None else min(steps, 20)
     kern_ms, launches, ev_sweeps = 0.0, 0, 0
@@ -217,12 +222,12 @@ def time_bp(eng, g, eps, steps, warmup, torch, event_steps=None, keep_last=False
     if avg_sweep_s <= 0:
         avg_sweep_s = avg_dev_s
     achieved = st["algorithmic_bytes_per_sweep"] / avg_sweep_s / 1e9
-    return {"dt": dt, "sweeps_total": sweeps_total, "msgs": g.messages_per_sweep() * sweeps_total,
-            "avg_sweep_s": avg_sweep_s, "avg_launch_s": avg_launch_s, "sweeps_per_launch": ev_sweeps / max(launches, 1),
-            "avg_sweep_devclock_s": avg_dev_s, "achieved": achieved, "stats": st,
-            "path": path, "ms_per_step_with_events": dt_ev / max(ev_steps, 1) * 1e3, "event_steps": ev_steps, "last": last,
-            "n_tiles": eng.layout()["n_tiles"], "cpt_bytes": 8 * len(g.cpt),
-            "waves_per_block": {2: eng.info("resident_waves"), 5: 8}.get(path)}
+    t.update({"avg_sweep_s": avg_sweep_s, "avg_launch_s": avg_launch_s, "sweeps_per_launch": ev_sweeps / max(launches, 1),
+              "avg_sweep_devclock_s": avg_dev_s, "achieved": achieved, "stats": st,
+              "ms_per_step_with_events": dt_ev / max(ev_steps, 1) * 1e3, "event_steps": ev_steps,
+              "n_tiles": eng.layout()["n_tiles"], "cpt_bytes": 8 * len(g.cpt),
+              "waves_per_block": {2: eng.info("resident_waves"), 5: 8}.get(t["path"])})
+    return t
 
 
 PATH_KERNEL = {0: "bp_sweep_kernel", 2: "bp_resident_kernel", 3: "bp_small_kernel", 4: "bp_mid_kernel", 5: "bp_dag_kernel"}
@@ -871,9 +876,11 @@ def main():
     ap.add_argument("--cols", type=int, default=316)
     ap.add_argument("--eps", type=float, default=1e-3)
     ap.add_argument("--evidence", type=float, default=0.01)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: beside the headline, also the roofline record, the cpu_baseline legs and the extras (off: the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs")
     ap.add_argument("--no-extras", dest="no_extras", action="store_true",
-                    help="headline only: skip the config2_dag / config5_lw / grid2048 / host-to-host extras")
+                    help="with --full: skip the config2_dag / config5_lw / grid2048 / host-to-host extras")
     ap.add_argument("--no-weak", dest="no_weak", action="store_true", help="N>1: skip the weak-scaling extra")
     ap.add_argument("--no-replicas", dest="no_replicas", action="store_true", help="N>1: skip the replicated-queries extra")
     ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
@@ -881,6 +888,8 @@ def main():
     a = ap.parse_args()
     if a.dump_outputs and (a.workload not in ("grid", "dag") or a.gpus != 1):
         ap.error("--dump-outputs is implemented for --workload grid / dag with --gpus 1")
+    if not a.full:
+        a.no_cpu = a.no_extras = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -973,21 +982,9 @@ def main():
     ev = synth.random_evidence(g, a.evidence, seed=7)
     eng = Engine(g, device=local_rank)
     eng.bp_set_evidence(ev)  # inputs resident in HBM before the timed region
-    t = time_bp(eng, g, a.eps, a.steps, a.warmup, torch, keep_last=bool(a.dump_outputs))
+    t = time_bp(eng, g, a.eps, a.steps, a.warmup, torch, keep_last=bool(a.dump_outputs), events=a.full)
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, t["last"])
-    if label == "grid316" and t["path"] == 0:
-        label = "grid316_launch"  # the profile of the same grid with one launch per sweep (BN_MULTISWEEP=0)
-    if label == "dag10k" and t["path"] == 0:
-        label = "dag10k_launch"   # ... of the DAG with one launch per sweep (BN_DAG=0)
-    roof = roofline_of(t, label)
-    stream = measured_stream_gbs(torch, local_rank)
-    # the yardstick beside the nominal 8 TB/s: the better of the library's copy and triad kernels; torch's copy_ beside it
-    roof["hbm_stream_gbs_measured"] = max([v for v in (stream["copy"], stream["triad"]) if v] or [0.0]) or None
-    roof["hbm_stream_gbs_copy"], roof["hbm_stream_gbs_triad"] = stream["copy"], stream["triad"]
-    roof["hbm_stream_gbs_torch_copy"] = stream["torch_copy"]
-    if roof["hbm_stream_gbs_measured"] and roof.get("traffic_gbs"):
-        roof["frac_of_measured_stream"] = roof["traffic_gbs"] / roof["hbm_stream_gbs_measured"]   # counter traffic per second over what a pure stream reaches
     out = {
         "metric": "edge-messages/sec to BP convergence", "value": t["msgs"] / t["dt"], "unit": "edge-messages/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": t["dt"] / a.steps * 1e3,
@@ -996,9 +993,22 @@ def main():
         "config": {"workload": f"{wname}, {ev.ne} evidence nodes, eps={a.eps:g}",
                    "sweeps_per_step": t["sweeps_total"] / a.steps, "messages_per_sweep": g.messages_per_sweep(),
                    "parallelism": "1 GPU", "run_path": PATH_NAME.get(t["path"], "?")},
-        "roofline": roof,
-        "sweep_only_msgs_per_s": g.messages_per_sweep() / t["avg_sweep_s"],
     }
+    if a.full:
+        if label == "grid316" and t["path"] == 0:
+            label = "grid316_launch"  # the profile of the same grid with one launch per sweep (BN_MULTISWEEP=0)
+        if label == "dag10k" and t["path"] == 0:
+            label = "dag10k_launch"   # ... of the DAG with one launch per sweep (BN_DAG=0)
+        roof = roofline_of(t, label)
+        stream = measured_stream_gbs(torch, local_rank)
+        # the yardstick beside the nominal 8 TB/s: the better of the library's copy and triad kernels; torch's copy_ beside it
+        roof["hbm_stream_gbs_measured"] = max([v for v in (stream["copy"], stream["triad"]) if v] or [0.0]) or None
+        roof["hbm_stream_gbs_copy"], roof["hbm_stream_gbs_triad"] = stream["copy"], stream["triad"]
+        roof["hbm_stream_gbs_torch_copy"] = stream["torch_copy"]
+        if roof["hbm_stream_gbs_measured"] and roof.get("traffic_gbs"):
+            roof["frac_of_measured_stream"] = roof["traffic_gbs"] / roof["hbm_stream_gbs_measured"]   # counter traffic per second over what a pure stream reaches
+        out["roofline"] = roof
+        out["sweep_only_msgs_per_s"] = g.messages_per_sweep() / t["avg_sweep_s"]
     if not a.no_extras:
         h2h = time_host_to_host(eng, g, evidence_cycle(g, a.evidence), a.eps, max(min(a.steps, 40), 16))
         out["cycled_evidence"] = time_cycled(eng, g, evidence_cycle(g, a.evidence), a.eps, max(min(a.steps, 40), 16))

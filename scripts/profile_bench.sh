@@ -23,7 +23,7 @@ pass() {  # name, then the rocprofv3 arguments
 trace() { pass $1 --kernel-trace --stats --output-format csv -d $OUT/$1 -o t -- python3 bench.py "${@:2}"; }
 pmc() { pass $1 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -o c -- python3 bench.py "${@:3}"; }
 
-B="--no-extras --no-cpu"
+B="--full --no-extras --no-cpu"   # the roofline record (its sweeps_per_launch) is what summarize_profile.py reads
 # headline: 316x316 grid, default path (resident tiles, one launch per run)
 export BN_MULTISWEEP=1
 trace trace_grid316 $B --steps 20 --warmup 3

@@ -151,9 +151,9 @@ def test_bench_multi_gpu_code_path_on_one_rank():
 
 
 def test_bench_default_line_is_the_contract_and_small():
-    """`python bench.py --gpus 1` as the driver types it (reduced steps, no CPU legs, headline only): the last stdout line is
-    the contract line -- every contract key, scalar roofline with frac and frac_survey_8d, config.workload = configs[2],
-    dtype f64 -- in at most 4 KB, with the full records on the lines before it."""
+    """`python bench.py --gpus 1 --full --no-extras` (reduced steps, headline with its roofline and CPU baseline): the last
+    stdout line is the contract line -- every contract key, scalar roofline with frac and frac_survey_8d, config.workload =
+    configs[2], dtype f64 -- in at most 4 KB, with the full records on the lines before it."""
     import os
     import subprocess
     import sys
@@ -161,8 +161,8 @@ def test_bench_default_line_is_the_contract_and_small():
     from helpers import parse_bench_output
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BN_FORCE_MULTI")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full",
+                        "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     last = p.stdout.strip().splitlines()[-1]
     assert len(last.encode()) <= benchline.MAX_LINE_BYTES
@@ -178,3 +178,26 @@ def test_bench_default_line_is_the_contract_and_small():
     assert all(not isinstance(v, (dict, list)) for v in roof.values())
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] == 1 and line["cpu_baseline"]["value"] > 0
     assert "roofline_full" in extras
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and the
+    contract line, nothing else -- no extras before the line, no roofline and no CPU baseline in it."""
+    import os
+    import subprocess
+    import sys
+    from bayesiannetwork_amd import benchline
+    from helpers import parse_bench_output
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BN_FORCE_MULTI")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    line, extras = parse_bench_output(p.stdout)
+    assert extras == {} and "roofline" not in line and "cpu_baseline" not in line
+    assert list(line.keys()) == [k for k in benchline.CONTRACT_KEYS if k in line]
+    assert line["metric"] == "edge-messages/sec to BP convergence" and line["unit"] == "edge-messages/s" and line["value"] > 1e9
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["steps"] == 5 and line["warmup"] == 2
+    assert line["ms_per_step"] > 0 and "configs[2]" in line["config"]["workload"]
+    bel, sweeps = np.load(tmp_path / "beliefs.npy"), np.load(tmp_path / "sweeps.npy")
+    assert bel.shape == (316 * 316 * 4,) and sweeps[0] == line["config"]["sweeps_per_step"]
