@@ -414,7 +414,8 @@ __global__ __launch_bounds__(kLwThreads) __attribute__((amdgpu_waves_per_eu(BN_L
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 const uint2* tab = reinterpret_cast<const uint2*>(my_tab);
-                switch (kv) {
+                switch (kv) {   // (a one-state node has no threshold: as KV 4 its tie re-draw would read three of the next table's)
+                    case 1: pick_states16<1, S, PAR>(tab, tbase, row, out, rng, st); break;
                     case 2: pick_states16<2, S, PAR>(tab, tbase, row, out, rng, st); break;
                     case 3: pick_states16<3, S, PAR>(tab, tbase, row, out, rng, st); break;
                     default: pick_states16<4, S, PAR>(tab, tbase, row, out, rng, st); break;
