@@ -7,4 +7,13 @@ first use and its absence is a hard error: there is no CPU fallback in this pack
 from .flat import Evidence, FlatModel, from_parent_lists  # noqa: F401
 from . import synth  # noqa: F401
 
-__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth"]
+_EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters")
+__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION]
+
+
+def __getattr__(name):
+    # the scores of evaluation.py, resolved at first use: importing the package alone loads neither the ctypes loader nor the library
+    if name in _EVALUATION:
+        from . import evaluation
+        return getattr(evaluation, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -116,6 +116,9 @@ SYMBOLS = [
     ("bn_info_pair_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, ctypes.POINTER(ctypes.c_uint64)]),
     ("bn_info_last_pairs_ms", ctypes.c_int, [ctypes.c_void_p, f64p]),
     ("bn_info_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, i64p]),
+    ("bn_score_log_cpt", ctypes.c_int, [ctypes.c_void_p, f64p]),
+    ("bn_score_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, i32p, f64p]),
+    ("bn_score_nodes", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, f64p, ctypes.POINTER(ctypes.c_uint64)]),
 ]
 
 

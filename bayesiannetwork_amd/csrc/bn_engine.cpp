@@ -1409,6 +1409,7 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
     if (std::strcmp(name, "small") == 0) { e->small_mode = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
     if (std::strcmp(name, "poll_sleep") == 0) { e->poll_sleep = std::max(0, std::min(value, 64)); return BN_OK; }
     if (std::strcmp(name, "multisweep") == 0) { e->multisweep = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
+    if (std::strcmp(name, "score_splits") == 0) { e->score.splits = std::max(0, std::min(value, 65535)); return BN_OK; }
     return fail(BN_ERR_ARG, std::string("unknown option ") + name);
 }
 // Introspection for tests and tools: a named integer property of the engine / its last run.
@@ -1432,6 +1433,18 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
         return n;
     }
     if (std::strcmp(name, "n_boundary_nodes") == 0) return int64_t(e->plan.boundary_node.size());
+    if (std::strcmp(name, "parameters") == 0) {   // basic_info_criteria::calc_parameters (basic_info_criteria.hpp:100-117): sum (k - 1) x prod k[parent]
+        int64_t total = 0;
+        for (int32_t v = 0; v < e->plan.n; ++v) {
+            int64_t rows = e->plan.k[v] - 1;
+            for (int32_t j = e->plan.in_ptr[v]; j < e->plan.in_ptr[v + 1]; ++j) rows *= e->plan.k[e->plan.in_idx[j]];
+            total += rows;
+        }
+        return total;
+    }
+    if (std::strcmp(name, "score_rows_ns") == 0) return int64_t(double(e->score.last_rows_ms) * 1e6);     // device-event times of the last
+    if (std::strcmp(name, "score_count_ns") == 0) return int64_t(double(e->score.last_count_ms) * 1e6);   // bn_score_rows / bn_score_nodes
+    if (std::strcmp(name, "score_nodes_ns") == 0) return int64_t(double(e->score.last_nodes_ms) * 1e6);   // kernels (counting, node sums)
     if (std::strcmp(name, "resident_blocks") == 0) return e->grid_resident;
     if (std::strcmp(name, "resident_waves") == 0) return e->resident_waves;
     if (std::strcmp(name, "resident_aborts") == 0) return e->resident_aborts;

@@ -104,6 +104,19 @@ struct DagImage {
     DeviceBuf<DagFlowSync> flow;
 };
 
+// Scoring (bn_score.cpp): the log of the flat CPT and the model's structure as the scoring kernels read them, made at the
+// first bn_score_* call; bn_reload_cpt clears `ready`, so the next call takes the logarithms of the new tables.
+struct ScoreState {
+    bool ready = false;
+    std::vector<double> h_L;            // [entries] std::log(cpt_flat[q]) (fp64, libm)
+    bool wide = false;                  // some node's table has >= 2^32 entries
+    int32_t splits = 0;                 // option "score_splits": workgroups per node of the counting pass (0: chosen from the shapes)
+    DeviceBuf<double> d_L;
+    DeviceBuf<int32_t> d_k, d_in_ptr, d_in_idx;
+    DeviceBuf<int64_t> d_cpt_off;
+    float last_rows_ms = 0.0f, last_count_ms = 0.0f, last_nodes_ms = 0.0f;   // device-event times of the last calls' kernels
+};
+
 struct bn_engine {
     Plan plan;
     bool host_only = true;
@@ -326,6 +339,7 @@ struct bn_engine {
     std::vector<hipEvent_t> events;  // (begin, end) per sweep batch
     int grid_tiles = 0;              // blocks for one-wave-per-tile kernels without remap
     LwState lw;
+    ScoreState score;
 };
 
 

@@ -132,6 +132,7 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
         if (e->mid.ok) e->mid = std::move(n_mid);
         if (e->dag.ok) e->dag = std::move(n_dag);
         if (e->dense) { free_engine(e->dense); e->dense = nullptr; e->batch_on_dense = false; }   // (rebuilt from the new tables on demand)
+        e->score.ready = false;   // (the log table of bn_score_*: taken again from the new values at the next call)
         if (e->host_only) return BN_OK;
         e->poisoned = true;   // until every image has arrived
         ON_DEVICE(e);
@@ -341,7 +342,7 @@ extern "C" int bn_fit_cpt(const bn_model_desc* desc, int64_t n_patterns, const u
     if ((r = dalloc(d_cnt, entries))) return r;
     if ((r = dalloc(d_out, entries))) return r;
     HIPCHK(hipMemsetAsync(d_cnt, 0, std::max<size_t>(entries, 1) * 8, s));
-    FitArgs a{n, d_k, d_ptr, d_idx, d_off, n_patterns, d_pat, d_w, d_cnt, int64_t(row_node.size()), d_rn, d_ro, d_out};
+    FitArgs a{n, d_k, d_ptr, d_idx, d_off, n_patterns, d_pat, d_w, d_cnt, int64_t(row_node.size()), d_rn, d_ro, d_out, n_patterns};
     if (launch_fit(a, s)) return fail(BN_ERR_HIP, "fit kernel launch failed");
     if (entries) HIPCHK(hipMemcpyAsync(cpt_out, d_out, entries * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

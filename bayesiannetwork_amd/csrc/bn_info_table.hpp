@@ -1,0 +1,28 @@
+// bn_info_table.hpp -- the object behind bn_info_table (include/bn_mi355x.h): a pattern table resident on the device.  Host code
+// only; shared by bn_info.cpp (entropies) and bn_score.cpp (log-likelihood under an engine's network).
+#pragma once
+
+#include "bn_engine_internal.hpp"
+#include "bn_info.hpp"
+
+struct bn_info_table {
+    int device = 0;
+    int32_t n = 0;
+    int64_t P = 0, Ppad = 0;
+    int32_t D = 1;
+    std::vector<int32_t> k;
+    double Nd = 0.0;
+    hipStream_t stream = nullptr;
+    DeviceBuf<uint8_t> d_T;
+    DeviceBuf<unsigned long long> d_w;
+    DeviceBuf<uint8_t> d_wd;
+    float last_pairs_ms = 0.0f;
+
+    InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
+    ~bn_info_table() {   // (the members' own destructors would run after the guard's)
+        DeviceGuard g;
+        (void)g.enter(device);
+        d_T.reset(); d_w.reset(); d_wd.reset();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};

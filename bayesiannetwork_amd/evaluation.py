@@ -6,10 +6,16 @@ information of the columns of a sample table, on the GPU (bn_info_* of include/b
 whose table is keyed by full-node pattern tuples.  For a Sampler only the requested columns are
 marshalled; a column's arity is `k[v]` when `k` is given, else its largest sampled state + 1 (the value
 of H does not depend on states no sample has).  An empty sampler gives 0.0 without a device call, the
-reference's value.  Not in the reference: InfoTable itself and mutual_information_matrix."""
+reference's value.  Not in the reference: InfoTable itself and mutual_information_matrix.
+
+Also the mirror of bn::evaluation::aic / mdl (reference bayesian/evaluation/aic.hpp, mdl.hpp over
+basic_info_criteria.hpp:44-117): `AIC(sampling)` / `MDL(sampling)` score a network against a table through
+bn_score_nodes.  Not in the reference: `log_likelihood_rows` (per distinct pattern), `log_likelihood_nodes`
+(per node, optionally with the family counts), `log_cpt` and `parameters` as functions of their own."""
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -30,6 +36,8 @@ class InfoTable:
         if counts.shape[0] != patterns.shape[0]:
             raise ValueError("one count per pattern")
         self.n, self.k = len(k), k
+        self.n_patterns, self.total = patterns.shape[0], int(counts.sum(dtype=np.uint64))
+        self.device = device
         h = ctypes.c_void_p()
         _lib.check(_lib.lib().bn_info_create(patterns.shape[0], len(k), _p(patterns, ctypes.c_uint8),
                                              _p(counts, ctypes.c_uint64), _p(k, ctypes.c_int32), device, ctypes.byref(h)))
@@ -168,3 +176,101 @@ def mutual_information_matrix(sampler_or_table, variables=None, k=None) -> dict:
     uniq, pos = _columns(vs)
     with table_from_sampler(sampler_or_table, uniq, k) as t:
         return t.pair_entropies(pos)
+
+
+# ---- log-likelihood, AIC, MDL (bn_score_* of include/bn_mi355x.h) ---------------------------------
+
+def log_cpt(engine) -> np.ndarray:
+    """L[q] = log(cpt[q]) as the engine holds it (fp64 libm log on the host; -inf where the CPT has 0)."""
+    out = np.zeros(int(engine.model.cpt_off[-1]))
+    _lib.check(_lib.lib().bn_score_log_cpt(engine._h, _p(out, ctypes.c_double)))
+    return out
+
+
+def log_likelihood_rows(engine, table: InfoTable, nodes=None) -> np.ndarray:
+    """Per distinct pattern of `table`: the sum over `nodes` (None: every node; any order, no duplicates) of
+    log P(state | parents' states) under the engine's network.  The order of additions is the header's, so
+    the value of a pattern depends on the model, the selection and that pattern only."""
+    out = np.zeros(table.n_patterns)
+    if nodes is None:
+        m, vp = 0, None
+    else:
+        v = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        m, vp = len(v), _p(v, ctypes.c_int32)
+    _lib.check(_lib.lib().bn_score_rows(engine._h, table._h, m, vp, _p(out, ctypes.c_double)))
+    return out
+
+
+def log_likelihood_nodes(engine, table: InfoTable, counts: bool = False):
+    """Per node v: sum over its CPT entries q seen in the table of N[q] * log(cpt[q]) (N: samples showing that
+    parent assignment and state).  counts=True: (ll_node, N) with N [n_entries] uint64."""
+    out = np.zeros(engine.model.n)
+    N = np.zeros(int(engine.model.cpt_off[-1]), dtype=np.uint64) if counts else None
+    _lib.check(_lib.lib().bn_score_nodes(engine._h, table._h, _p(out, ctypes.c_double),
+                                         _p(N, ctypes.c_uint64) if counts else None))
+    return (out, N) if counts else out
+
+
+def parameters(engine_or_model) -> int:
+    """basic_info_criteria::calc_parameters (:100-117): sum over the nodes of (k - 1) x product of the parents' arities."""
+    if hasattr(engine_or_model, "_h"):
+        return engine_or_model.info("parameters")
+    m = engine_or_model
+    return sum((int(m.k[v]) - 1) * math.prod(int(m.k[u]) for u in m.parents(v)) for v in range(m.n))
+
+
+class _InfoCriterion:
+    """basic_info_criteria (basic_info_criteria.hpp:13-42): `sampling` is an InfoTable over every node in node
+    order, or an engine.Sampler (marshalled at the first call, over all nodes in node order, arities from the
+    model, and kept: a sampler reloaded afterwards needs a new functor)."""
+
+    def __init__(self, sampling, device: int = _lib.BN_DEVICE_CURRENT):
+        self._sampling, self._device = sampling, device
+        self._table = sampling if isinstance(sampling, InfoTable) else None
+
+    def sampling_size(self) -> int:
+        return self._sampling.total if isinstance(self._sampling, InfoTable) else self._sampling.sampling_size()
+
+    def _ensure_table(self, model) -> InfoTable:
+        if self._table is None:
+            self._table = table_from_sampler(self._sampling, range(model.n), model.k, self._device)
+        return self._table
+
+    def calc_likelihood(self, engine_or_model, nodes=None) -> float:
+        """-log P(D | network) over `nodes` in the given order (:44-78): likelihood = 0.0; likelihood -= ll_node[v]."""
+        if self.sampling_size() == 0:   # an empty table: no statistics, no term (the reference's loops run zero times)
+            return 0.0
+        if hasattr(engine_or_model, "_h"):
+            ll = log_likelihood_nodes(engine_or_model, self._ensure_table(engine_or_model.model))
+        else:
+            from .engine import Engine
+            table = self._ensure_table(engine_or_model)
+            with Engine(engine_or_model, device=table.device) as eng:
+                ll = log_likelihood_nodes(eng, table)
+        likelihood = 0.0
+        for v in (range(len(ll)) if nodes is None else nodes):
+            likelihood -= float(ll[int(v)])
+        return likelihood
+
+    def _terms(self, engine_or_model, nodes):
+        # parameters: ALWAYS over the whole graph, also for a node subset (aic.hpp:23-24, mdl.hpp:24-25)
+        return self.calc_likelihood(engine_or_model, nodes), float(parameters(engine_or_model))
+
+
+class AIC(_InfoCriterion):
+    """bn::evaluation::aic (aic.hpp): score(engine_or_model, nodes=None) = likelihood + parameters."""
+
+    def __call__(self, engine_or_model, nodes=None) -> float:
+        likelihood, params = self._terms(engine_or_model, nodes)
+        return likelihood + params
+
+
+class MDL(_InfoCriterion):
+    """bn::evaluation::mdl (mdl.hpp): likelihood + parameters * (log2(N) / 2), N the table's total count; an empty
+    sampling raises RuntimeError("Sampling is not finished yet.") (:28-36)."""
+
+    def __call__(self, engine_or_model, nodes=None) -> float:
+        if self.sampling_size() == 0:
+            raise RuntimeError("Sampling is not finished yet.")
+        likelihood, params = self._terms(engine_or_model, nodes)
+        return likelihood + params * (math.log2(float(self.sampling_size())) / 2)

@@ -43,7 +43,9 @@ public:
         std::vector<double> mi;     // [m][m] = h[x] + h[y] - hxy[x][y]
     };
 
-    information_table(sampler const& sampling, std::vector<vertex_type> const& variables, int device = BN_DEVICE_CURRENT)
+    // rows_out (may be null): the distinct patterns in the order they were uploaded (row i of the device table)
+    information_table(sampler const& sampling, std::vector<vertex_type> const& variables, int device = BN_DEVICE_CURRENT,
+                      std::vector<condition_t>* rows_out = nullptr)
         : vars_(unique(variables))
     {
         if(sampling.sampling_size() == 0) return;
@@ -58,6 +60,7 @@ public:
         {
             for(auto const& v : vars_) patterns.push_back(static_cast<std::uint8_t>(sample.first.at(v)));
             counts.push_back(static_cast<std::uint64_t>(sample.second));
+            if(rows_out) rows_out->push_back(sample.first);
         }
         mi355x::engine_handle::check(bn_info_create(static_cast<std::int64_t>(counts.size()), static_cast<std::int32_t>(vars_.size()),
                                                     patterns.data(), counts.data(), k.data(), device, &table_));
@@ -67,6 +70,8 @@ public:
     information_table& operator=(information_table const&) = delete;
 
     std::vector<vertex_type> const& variables() const { return vars_; }
+    // the C handle (null for an empty sampler): what bn_score_* of include/bn_mi355x.h take
+    bn_info_table* handle() const { return table_; }
 
     double entropy(std::vector<vertex_type> const& variables) const
     {

@@ -370,6 +370,42 @@ int bn_info_pair_counts(bn_info_table *table, int32_t n_pairs, const int32_t *pa
 int bn_info_last_pairs_ms(const bn_info_table *table, double *ms_out);
 int bn_info_get(const bn_info_table *table, const char *name, int64_t *value_out);
 
+/* ---- log-likelihood of a pattern table under the engine's network ----
+ * Replaces: basic_info_criteria::calc_likelihood (bayesian/evaluation/basic_info_criteria.hpp:44-78), the term of
+ * bn::evaluation::aic / mdl that depends on the data; calc_parameters (:100-117) is bn_get_info(eng, "parameters")
+ * = sum over the nodes of (k[v] - 1) x product of the parents' arities (int64, exact).
+ *   The log table.  L[q] = log(cpt[q]) for every flat CPT entry q (layout of bn_model_desc.cpt), taken on the HOST
+ *   with libm's log in fp64 (log(0) = -inf), at the first bn_score_* call and again after bn_reload_cpt.  The device
+ *   never evaluates a logarithm: every result below is a function of L, the table and the stated order of additions.
+ *   bn_score_log_cpt: L [n_entries] (also on a BN_DEVICE_HOST_ONLY engine).
+ *   bn_score_rows: ll_out [n_patterns], ll_out[p] = sum over the selected nodes v of
+ *   L[cpt_off[v] + row_v(p) * k[v] + state_v(p)], row_v the parent assignment with the first parent most significant
+ *   (the rule of bn_fit_cpt).  nodes == NULL selects every node (n_sel is not read); else `nodes` lists n_sel node ids
+ *   in any order; a duplicate or an id out of range: BN_ERR_ARG; n_sel == 0: every sum is +0.0.  Order of additions:
+ *   the nodes are grouped by node id >> 8 (segments of 256 consecutive ids, whatever the selection); inside a segment
+ *   the selected nodes are added in increasing id starting from +0.0; the segment sums are then added in increasing
+ *   segment order starting from +0.0; a segment without a selected node is skipped.  ll_out[p] therefore depends on
+ *   the model, the selection and pattern p alone -- not on the other patterns, on p's position or on the launch
+ *   shape.  A pattern that shows a zero-probability entry scores -inf.  The counts are not used.
+ *   bn_score_nodes: ll_node_out [n_nodes], ll_node_out[v] = sum over the entries q of node v's table with N[q] != 0 of
+ *   double(N[q]) * L[q]; N[q] the exact number of samples (patterns weighted by their counts) showing that parent
+ *   assignment and state -- the counts bn_fit_cpt normalises.  An entry no sample shows is skipped (an unseen
+ *   zero-probability entry adds nothing, not 0 * -inf).  Order of additions, with r = q - cpt_off[v]: 256 partial sums,
+ *   partial t taking the terms r = t, t + 256, t + 512, ... in increasing r starting from +0.0; then the partial sums are
+ *   folded by halves, for s = 128, 64, ..., 1: partial[t] += partial[t + s] for every t < s; the result is partial[0].
+ *   It does not depend on the order of the patterns, on how a pattern's count is spread over equal rows or on the launch
+ *   shape.  family_counts_out may be NULL; else it receives N [n_entries].
+ *   Errors.  BN_ERR_ARG: a null pointer, n_vars != n_nodes, an arity that differs between engine and table, engine and
+ *   table on different devices (the agreement of the arities is also what keeps every gather inside L: the table's
+ *   states were checked against them at bn_info_create).  BN_ERR_NO_DEVICE: a BN_DEVICE_HOST_ONLY engine.
+ *   BN_ERR_STATE: a sharded engine (a shard holds only its own nodes).
+ *   bn_get_info "score_rows_ns", "score_count_ns", "score_nodes_ns": device time of the last call's row kernel(s),
+ *   counting kernel and node-sum kernel; bn_set_option "score_splits": workgroups per node of the counting kernel
+ *   (0, the default: chosen from the shapes; the counts are integers and do not depend on it). */
+int bn_score_log_cpt(bn_engine *eng, double *out);
+int bn_score_rows(bn_engine *eng, bn_info_table *table, int32_t n_sel, const int32_t *nodes, double *ll_out);
+int bn_score_nodes(bn_engine *eng, bn_info_table *table, double *ll_node_out, uint64_t *family_counts_out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
