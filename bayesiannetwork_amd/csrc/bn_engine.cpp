@@ -1458,6 +1458,8 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strcmp(name, "dag_tiles") == 0) return e->dag.ok ? int64_t(e->dag.tiles.size()) : 0;
     if (std::strcmp(name, "dag_stream") == 0) return e->dag.ok && e->dag.stream ? 1 : 0;
     if (std::strcmp(name, "lw_small") == 0) return e->lw.ready && e->lw.small ? 1 : 0;   // (known after the first sampler call)
+    if (std::strcmp(name, "lw_last_sample_kernel") == 0) return e->lw.last_sample_kernel;   // (bn_lw.hpp launch_lw_sample: which instantiation)
+    if (std::strcmp(name, "lw_last_hist_kernel") == 0) return e->lw.last_hist_kernel;
     if (std::strcmp(name, "dag_aborts") == 0) return e->dag_aborts;
     if (std::strcmp(name, "batch_dense_refused") == 0) return e->dense_refused ? 1 : 0;   // (known after the first batch of >= 2 sets)
     if (std::strcmp(name, "batch_on_dense") == 0) return e->batch_on_dense ? 1 : 0;

@@ -270,7 +270,7 @@ int lw_run(LwState& s, const Plan& p, void* stream, int32_t ne, const int32_t* e
         LwArgs a{p.n, s.kmax, s.rows24, s.inline_parents, s.small, s.small_pow2, s.d_steps, s.d_small_steps, s.d_parents, s.d_ev_topo, s.d_k, s.d_node_off, s.d_cpt, s.d_thr, s.d_thr32, s.d_thr16,
                  s.d_states, s.d_weights, s.d_hist, s.stride, s.small, sample_begin + done, cnt, seed, 0};
         const int blocks = int((cnt + kLwBlockSamples - 1) / kLwBlockSamples);
-        if (launch_lw_sample(a, blocks, st) || launch_lw_hist(a, blocks, st)) { err = "lw kernel launch failed"; return BN_ERR_HIP; }
+        if (launch_lw_sample(a, blocks, st, &s.last_sample_kernel) || launch_lw_hist(a, blocks, st, &s.last_hist_kernel)) { err = "lw kernel launch failed"; return BN_ERR_HIP; }
         s.last_batch_samples = cnt;
         done += cnt;
     }
@@ -306,14 +306,14 @@ int rs_run(LwState& s, const Plan& p, void* stream, int32_t ne, const int32_t* e
         LwArgs a{p.n, s.kmax, s.rows24, s.inline_parents, s.small, s.small_pow2, s.d_steps, s.d_small_steps, s.d_parents, s.d_ev_topo, s.d_k, s.d_node_off, s.d_cpt, s.d_thr, s.d_thr32, s.d_thr16,
                  s.d_states, s.d_weights, s.d_hist, s.stride, s.small, sample_begin + drawn, cnt, seed, 1};
         const int blocks = int((cnt + kLwBlockSamples - 1) / kLwBlockSamples);
-        if (launch_lw_sample(a, blocks, st)) { err = "sampling kernel launch failed"; return BN_ERR_HIP; }
+        if (launch_lw_sample(a, blocks, st, &s.last_sample_kernel)) { err = "sampling kernel launch failed"; return BN_ERR_HIP; }
         LWCHK(hipMemcpyAsync(w.data(), s.d_weights, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
         LWCHK(hipStreamSynchronize(st));
         // samples count in index order until n_accept of them were accepted (rejection_sampling.hpp:93-111)
         uint64_t use = 0;
         while (use < cnt && accepted < n_accept) accepted += (w[use++] != 0.0);
         a.n_valid = use;
-        if (launch_lw_hist(a, blocks, st)) { err = "histogram kernel launch failed"; return BN_ERR_HIP; }
+        if (launch_lw_hist(a, blocks, st, &s.last_hist_kernel)) { err = "histogram kernel launch failed"; return BN_ERR_HIP; }
         s.last_batch_samples = cnt;
         drawn += use;
     }

@@ -77,6 +77,8 @@ struct LwState {
     uint64_t batch = 0;            // samples a row of d_states holds (multiple of kLwBlockSamples)
     uint64_t launch_samples = 0;   // samples per launch of the current call (<= batch, the row stride)
     uint64_t last_batch_samples = 0;
+    int32_t last_sample_kernel = 0;   // what launch_lw_sample launched last (bn_get_info "lw_last_sample_kernel"); 0: nothing yet
+    int32_t last_hist_kernel = 0;     // ... and launch_lw_hist ("lw_last_hist_kernel")
     std::vector<int32_t> topo;
 };
 
@@ -107,8 +109,11 @@ struct LwArgs {
     int32_t mode;          // 0 likelihood weighting, 1 rejection (logic) sampling
 };
 
-int launch_lw_sample(const LwArgs& a, int blocks, void* stream);
-int launch_lw_hist(const LwArgs& a, int blocks, void* stream);
+// `which` (optional) receives the instantiation that was launched:
+//   launch_lw_sample: 16 + 4 ROWS24 + 2 INLINE + REJECT for lw_sample_kernel, 32 + 2 POW2 + REJECT for lw_sample_small_kernel
+//   launch_lw_hist:   KMAX (2, 4, 8) for lw_hist_kernel, 32 + KMAX (34, 36) for lw_hist2_kernel, 64 for lw_hist_wide_kernel
+int launch_lw_sample(const LwArgs& a, int blocks, void* stream, int32_t* which = nullptr);
+int launch_lw_hist(const LwArgs& a, int blocks, void* stream, int32_t* which = nullptr);
 int launch_lw_transpose(const uint8_t* states, uint8_t* out, int32_t n, uint64_t stride, bool packed2, uint64_t n_samples, void* stream);
 
 // hist_out == nullptr: leave the histogram in s.d_hist (the caller reduces it across ranks first)

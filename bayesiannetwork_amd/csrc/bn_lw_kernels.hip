@@ -889,21 +889,27 @@ int launch_lw_transpose(const uint8_t* states, uint8_t* out, int32_t n, uint64_t
     return e == hipSuccess ? 0 : int(e);
 }
 
-int launch_lw_sample(const LwArgs& a, int blocks, void* stream) {
+int launch_lw_sample(const LwArgs& a, int blocks, void* stream, int32_t* which) {
     (void)hipGetLastError();  // drop any stale error of this thread
-#define BN_LW_LAUNCH3(R24, INL, REJ)                                                                              \
-    hipLaunchKernelGGL((lw_sample_kernel<R24, INL, REJ>), dim3(blocks), dim3(kLwThreads), 0, (hipStream_t)stream,  \
-                       reinterpret_cast<const LwStepWords*>(a.steps), reinterpret_cast<const uint4*>(a.parents),   \
-                       a.ev_topo, a.cpt, a.thr, a.thr32, reinterpret_cast<const uint4*>(a.thr16), a.states, a.weights, a.n, a.batch, a.sample_base, a.seed)
+#define BN_LW_LAUNCH3(R24, INL, REJ)                                                                                  \
+    do {                                                                                                              \
+        if (which) *which = 16 + 4 * int(R24) + 2 * int(INL) + int(REJ);                                              \
+        hipLaunchKernelGGL((lw_sample_kernel<R24, INL, REJ>), dim3(blocks), dim3(kLwThreads), 0, (hipStream_t)stream,  \
+                           reinterpret_cast<const LwStepWords*>(a.steps), reinterpret_cast<const uint4*>(a.parents),   \
+                           a.ev_topo, a.cpt, a.thr, a.thr32, reinterpret_cast<const uint4*>(a.thr16), a.states, a.weights, a.n, a.batch, a.sample_base, a.seed); \
+    } while (0)
 #define BN_LW_LAUNCH(R24, INL)                                \
     do {                                                      \
         if (a.mode == 1) BN_LW_LAUNCH3(R24, INL, true);       \
         else BN_LW_LAUNCH3(R24, INL, false);                  \
     } while (0)
-#define BN_LW_SMALL(P2, REJ)                                                                                           \
-    hipLaunchKernelGGL((lw_sample_small_kernel<P2, REJ>), dim3(blocks), dim3(kLwThreads), 0, (hipStream_t)stream,       \
-                       reinterpret_cast<const LwSmallWords*>(a.small_steps), a.ev_topo, a.cpt, a.thr,                   \
-                       reinterpret_cast<const uint4*>(a.thr16), a.states, a.weights, a.n, a.sample_base, a.seed)
+#define BN_LW_SMALL(P2, REJ)                                                                                               \
+    do {                                                                                                                   \
+        if (which) *which = 32 + 2 * int(P2) + int(REJ);                                                                   \
+        hipLaunchKernelGGL((lw_sample_small_kernel<P2, REJ>), dim3(blocks), dim3(kLwThreads), 0, (hipStream_t)stream,       \
+                           reinterpret_cast<const LwSmallWords*>(a.small_steps), a.ev_topo, a.cpt, a.thr,                   \
+                           reinterpret_cast<const uint4*>(a.thr16), a.states, a.weights, a.n, a.sample_base, a.seed);       \
+    } while (0)
     if (a.small) {
         if (a.small_pow2 && a.mode == 1) BN_LW_SMALL(true, true);
         else if (a.small_pow2) BN_LW_SMALL(true, false);
@@ -920,10 +926,11 @@ int launch_lw_sample(const LwArgs& a, int blocks, void* stream) {
     return e == hipSuccess ? 0 : int(e);
 }
 
-int launch_lw_hist(const LwArgs& a, int blocks, void* stream) {
+int launch_lw_hist(const LwArgs& a, int blocks, void* stream, int32_t* which) {
     (void)hipGetLastError();  // drop any stale error of this thread
     hipStream_t st = (hipStream_t)stream;
     if (a.kmax > 8) {
+        if (which) *which = 64;
         hipLaunchKernelGGL(lw_hist_wide_kernel, dim3(blocks), dim3(kLwThreads), 0, st, a.states, a.weights, a.k,
                            a.node_off, a.hist, a.n, a.batch, a.n_valid);
     } else if (a.n_valid > 0) {
@@ -938,21 +945,18 @@ int launch_lw_hist(const LwArgs& a, int blocks, void* stream) {
         range = (range + gran - 1) / gran * gran;
         const unsigned yb = unsigned((a.n_valid + range - 1) / range);
         const dim3 grid(xb, yb);
-        if (a.packed2 && a.kmax <= 2)
-            hipLaunchKernelGGL(lw_hist2_kernel<2>, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off,
-                               a.hist, a.n, a.batch, a.n_valid, range);
-        else if (a.packed2)
-            hipLaunchKernelGGL(lw_hist2_kernel<4>, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off,
-                               a.hist, a.n, a.batch, a.n_valid, range);
-        else if (a.kmax <= 2)
-            hipLaunchKernelGGL(lw_hist_kernel<2>, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off,
-                               a.hist, a.n, a.batch, a.n_valid, range);
-        else if (a.kmax <= 4)
-            hipLaunchKernelGGL(lw_hist_kernel<4>, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off,
-                               a.hist, a.n, a.batch, a.n_valid, range);
-        else
-            hipLaunchKernelGGL(lw_hist_kernel<8>, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off,
-                               a.hist, a.n, a.batch, a.n_valid, range);
+#define BN_LW_HIST(KERNEL, CODE)                                                                                      \
+    do {                                                                                                              \
+        if (which) *which = CODE;                                                                                     \
+        hipLaunchKernelGGL(KERNEL, grid, dim3(kLwThreads), 0, st, a.states, a.weights, a.k, a.node_off, a.hist, a.n,  \
+                           a.batch, a.n_valid, range);                                                                \
+    } while (0)
+        if (a.packed2 && a.kmax <= 2) BN_LW_HIST(lw_hist2_kernel<2>, 32 + 2);
+        else if (a.packed2) BN_LW_HIST(lw_hist2_kernel<4>, 32 + 4);
+        else if (a.kmax <= 2) BN_LW_HIST(lw_hist_kernel<2>, 2);
+        else if (a.kmax <= 4) BN_LW_HIST(lw_hist_kernel<4>, 4);
+        else BN_LW_HIST(lw_hist_kernel<8>, 8);
+#undef BN_LW_HIST
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : int(e);

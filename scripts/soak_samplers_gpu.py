@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity soak of the sampler family on the GPU box (not part of the test suite):  python scripts/soak_samplers_gpu.py [seconds] [seed]
-Random DAGs (arities 2 ... 7, up to 6 parents: both sampling kernels) x random hard evidence x random sample counts, seeds and sample
+Random DAGs (arities 1 ... 8, up to 6 parents: both sampling kernels) x random hard evidence x random sample counts, seeds and sample
 offsets; per network: the sampled STATES bit-equal to the oracle's (likelihood_weighting.hpp:122-193 on the repository's stream), weights
 <= 1e-12, the weighted histogram <= 1e-9 (fp64 atomics order); rejection sampling: counts, draws and acceptances exact; CPT fitting
 from the sampled patterns bit-equal to the restatement."""
@@ -26,7 +26,7 @@ while time.time() < t_end:
     if rng.random() < 0.4:
         arities = [int(x) for x in rng.choice([2, 3, 4], size=int(rng.integers(1, 4)))]     # the straight-line kernel's domain (if tables <= 256 rows, <= 4 parents)
     else:
-        arities = [int(x) for x in rng.choice([2, 3, 4, 5, 7], size=int(rng.integers(1, 4)))]
+        arities = [int(x) for x in rng.choice([1, 2, 3, 4, 5, 7, 8], size=int(rng.integers(1, 4)))]
     g = synth.random_dag(n, mp, int(rng.choice([4, 16, 64])), arities if len(arities) > 1 else arities[0], seed=int(rng.integers(1, 1 << 30)))
     st = synth.random_evidence(g, float(rng.choice([0.0, 0.03, 0.15])), seed=int(rng.integers(1, 1 << 30))).hard_states(g)
     ns = int(rng.choice([64, 1000, 4096, 20000])) if n <= 2500 else int(rng.choice([64, 1000]))

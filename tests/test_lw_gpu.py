@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import load_golden
+from sampler_cases import kahn_min_order as _kahn_min_order
 
 pytestmark = pytest.mark.gpu
 
@@ -321,27 +322,6 @@ def test_sampler_mirror_make_cpt(Engine, oracle_mod):
     assert smp.make_cpt(m) is True
     assert np.array_equal(m.cpt, oracle_mod.make_cpt(m, pats, cnts))
     assert np.abs(m.cpt - truth).max() < 0.02
-
-
-def _kahn_min_order(model):
-    """The sampler's visiting order (csrc/bn_lw.cpp: Kahn's algorithm, smallest ready node first)."""
-    import heapq
-    indeg = np.diff(model.in_ptr).astype(int)
-    children = [[] for _ in range(model.n)]
-    for v in range(model.n):
-        for p in model.parents(v):
-            children[int(p)].append(v)
-    ready = [v for v in range(model.n) if indeg[v] == 0]
-    heapq.heapify(ready)
-    order = []
-    while ready:
-        v = heapq.heappop(ready)
-        order.append(v)
-        for c in children[v]:
-            indeg[c] -= 1
-            if indeg[c] == 0:
-                heapq.heappush(ready, c)
-    return np.asarray(order, np.int32)
 
 
 @pytest.mark.parametrize("case", ["pearl", "dag12", "reversed_chain"])
