@@ -8,7 +8,8 @@ from .flat import Evidence, FlatModel, from_parent_lists  # noqa: F401
 from . import synth  # noqa: F401
 
 _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters")
-__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION]
+_LEARNING = ("Greedy", "K2", "Learner", "score_groups")
+__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING]
 
 
 def __getattr__(name):
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)
+    if name in _LEARNING:
+        from . import learning
+        return getattr(learning, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -119,6 +119,14 @@ SYMBOLS = [
     ("bn_score_log_cpt", ctypes.c_int, [ctypes.c_void_p, f64p]),
     ("bn_score_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, i32p, f64p]),
     ("bn_score_nodes", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, f64p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_learn_score_groups", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, i32p, i32p, f64p,
+                                             ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_learn_create", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bn_learn_try_parents", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, u8p]),
+    ("bn_learn_score", ctypes.c_int, [ctypes.c_void_p, f64p]),
+    ("bn_learn_structure", ctypes.c_int, [ctypes.c_void_p, i32p, i32p]),
+    ("bn_learn_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, i64p]),
+    ("bn_learn_destroy", None, [ctypes.c_void_p]),
 ]
 
 

@@ -38,6 +38,7 @@ class InfoTable:
         self.n, self.k = len(k), k
         self.n_patterns, self.total = patterns.shape[0], int(counts.sum(dtype=np.uint64))
         self.device = device
+        self.patterns, self.counts = patterns, counts   # (host copies: learning.py fits the learned structure's CPTs to them)
         h = ctypes.c_void_p()
         _lib.check(_lib.lib().bn_info_create(patterns.shape[0], len(k), _p(patterns, ctypes.c_uint8),
                                              _p(counts, ctypes.c_uint64), _p(k, ctypes.c_int32), device, ctypes.byref(h)))

@@ -1,0 +1,201 @@
+// bayesian/learning/greedy.hpp -- drop-in for the reference's bn::learning::greedy<Eval> (bayesian/learning/greedy.hpp), the
+// search running on the MI355X through bn_learn_* (include/bn_mi355x.h) when Eval is bn::evaluation::aic or mdl.  C++14, no Boost.
+//
+// Same class, same members: greedy(sampler const&), operator()(graph), operator()(graph, vertexes),
+// learn_with_hint(graph, parent_nodes, child_nodes); the shuffles are the reference's (std::shuffle with a std::mt19937).
+//
+// How it runs.  AIC and MDL are decomposable, so for Eval = aic / mdl (exactly those types) the candidates of a child are scored
+// as families of that child in one pass over the device-resident table per ACCEPTED edge (bn_learn_try_parents), instead of one
+// make_cpt and one evaluation of the whole graph per candidate.  The table is an information_table over graph.vertex_list(),
+// marshalled at each call; accepted edges are applied to the caller's graph with add_edge; one sampling_.make_cpt(graph) at the end.
+// Any other Eval (a subclass of aic included) runs the reference's literal loop: make_cpt + eval_ per candidate.
+//
+// Differences from the reference (aic / mdl path):
+//   - the score is the learner's: the family terms take the device's fp64 logarithm (bn_mi355x.h states the function), so the
+//     returned value agrees with eval_(graph) to a few ulp per term, not bit for bit;
+//   - the graph ends with CPTs fitted to the FINAL structure (the reference leaves the CPTs of the last rejected candidate);
+//   - a family is limited to 16 parents and 2^20 table entries: a candidate beyond them is not added;
+//   - an empty sampler takes the literal loop (and behaves as there).
+// Not in the reference (labelled so below): the constructor taking a seed, last_visits().
+#ifndef BNI_LEARNING_GREEDY_HPP
+#define BNI_LEARNING_GREEDY_HPP
+
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <random>
+#include <stdexcept>
+#include <type_traits>
+#include <vector>
+
+#include <bayesian/graph.hpp>
+#include <bayesian/sampler.hpp>
+#include <bayesian/evaluation/aic.hpp>
+#include <bayesian/evaluation/mdl.hpp>
+#include <bayesian/evaluation/transinformation.hpp>
+
+namespace bn {
+namespace learning {
+
+// NOT IN THE REFERENCE: a child and the candidates it was offered, in order (what a run visited; tests replay it)
+struct visit_t {
+    vertex_type child;
+    std::vector<vertex_type> candidates;
+};
+
+namespace detail {
+
+// 0 AIC, 1 MDL, -1: any other evaluation (the literal loop)
+template<class Eval> struct criterion_of : std::integral_constant<int, -1> {};
+template<> struct criterion_of<evaluation::aic> : std::integral_constant<int, 0> {};
+template<> struct criterion_of<evaluation::mdl> : std::integral_constant<int, 1> {};
+
+// (reference bayesian/utility.hpp: make_engine)
+inline std::mt19937 make_engine()
+{
+    std::random_device rd;
+    return std::mt19937(rd());
+}
+
+// a bn_learner over the graph's vertex_list(), starting from the graph's edges
+class learner_session {
+public:
+    learner_session(sampler const& sampling, graph_t const& graph, int criterion, int max_parents = 16)
+        : nodes_(graph.vertex_list()), table_(sampling, nodes_)
+    {
+        std::vector<std::int32_t> in_ptr(1, 0), in_idx;
+        for(auto const& node : nodes_)
+        {
+            for(auto const& parent : graph.in_vertexes(node)) in_idx.push_back(index_of(parent));
+            in_ptr.push_back(static_cast<std::int32_t>(in_idx.size()));
+        }
+        mi355x::engine_handle::check(bn_learn_create(table_.handle(), in_ptr.data(), in_idx.data(), criterion, max_parents, &learner_));
+    }
+    ~learner_session() { bn_learn_destroy(learner_); }
+    learner_session(learner_session const&) = delete;
+    learner_session& operator=(learner_session const&) = delete;
+
+    // the reference's inner loop for one child; accepted edges are added to `graph`
+    void try_parents(graph_t& graph, vertex_type const& child, std::vector<vertex_type> const& candidates)
+    {
+        std::vector<std::int32_t> cand;
+        for(auto const& c : candidates) cand.push_back(index_of(c));
+        std::vector<std::uint8_t> accepted(cand.size() + 1, 0);
+        mi355x::engine_handle::check(bn_learn_try_parents(learner_, index_of(child), static_cast<std::int32_t>(cand.size()), cand.data(),
+                                                          accepted.data()));
+        for(std::size_t i = 0; i < cand.size(); ++i)
+            if(accepted[i] && !graph.add_edge(candidates[i], child))
+                throw std::logic_error("bn::learning: the graph refused an edge the learner accepted");
+    }
+
+    double score() const
+    {
+        double s = 0.0;
+        mi355x::engine_handle::check(bn_learn_score(learner_, &s));
+        return s;
+    }
+
+private:
+    std::int32_t index_of(vertex_type const& v) const
+    {
+        auto const it = std::find(nodes_.begin(), nodes_.end(), v);
+        if(it == nodes_.end()) throw std::out_of_range("bn::learning: vertex not in the graph");
+        return static_cast<std::int32_t>(it - nodes_.begin());
+    }
+
+    std::vector<vertex_type> nodes_;
+    evaluation::information_table table_;
+    bn_learner* learner_ = nullptr;
+};
+
+} // namespace detail
+
+template<class Eval>
+class greedy {
+public:
+    greedy(bn::sampler const& sampling)
+        : sampling_(sampling), eval_(sampling_), engine_(detail::make_engine())
+    {
+    }
+
+    // NOT IN THE REFERENCE: a reproducible run
+    greedy(bn::sampler const& sampling, std::uint32_t seed)
+        : sampling_(sampling), eval_(sampling_), engine_(seed)
+    {
+    }
+
+    double operator()(graph_t& graph)
+    {
+        return (*this)(graph, graph.vertex_list());
+    }
+
+    double operator()(graph_t& graph, std::vector<vertex_type> vertexes)
+    {
+        std::shuffle(vertexes.begin(), vertexes.end(), engine_);
+        visits_.clear();
+        for(auto it = vertexes.begin(); it != vertexes.end();)
+        {
+            auto const child_iter = it;
+            std::shuffle(++it, vertexes.end(), engine_);
+            visits_.push_back(visit_t{*child_iter, std::vector<vertex_type>(it, vertexes.end())});
+        }
+        return run(graph);
+    }
+
+    // only edges from a node of parent_nodes to a node of child_nodes
+    double learn_with_hint(graph_t& graph, std::vector<vertex_type> parent_nodes, std::vector<vertex_type> child_nodes)
+    {
+        std::shuffle(std::begin(child_nodes), std::end(child_nodes), engine_);
+        visits_.clear();
+        for(auto const& child : child_nodes)
+        {
+            std::shuffle(std::begin(parent_nodes), std::end(parent_nodes), engine_);
+            visits_.push_back(visit_t{child, parent_nodes});
+        }
+        return run(graph);
+    }
+
+    // NOT IN THE REFERENCE: the children of the last run and the candidates each was offered, in order
+    std::vector<visit_t> const& last_visits() const { return visits_; }
+
+private:
+    // The shuffles draw from the engine only, never from the scores, so drawing them all first leaves every order as the
+    // reference's interleaved loop has it.
+    double run(graph_t& graph)
+    {
+        if(detail::criterion_of<Eval>::value >= 0 && sampling_.sampling_size() != 0)
+        {
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            for(auto const& visit : visits_) session.try_parents(graph, visit.child, visit.candidates);
+            sampling_.make_cpt(graph);
+            return session.score();
+        }
+        // the reference's loop (greedy.hpp:31-61, :73-100)
+        sampling_.make_cpt(graph);
+        double eval_now = eval_(graph);
+        for(auto const& visit : visits_)
+        {
+            for(auto const& parent : visit.candidates)
+            {
+                if(auto edge = graph.add_edge(parent, visit.child))
+                {
+                    sampling_.make_cpt(graph);
+                    auto const eval_next = eval_(graph);
+                    if(eval_next < eval_now) eval_now = eval_next;
+                    else graph.erase_edge(edge);
+                }
+            }
+        }
+        return eval_now;
+    }
+
+    sampler const& sampling_;
+    Eval const eval_;
+    std::mt19937 engine_;
+    std::vector<visit_t> visits_;
+};
+
+} // namespace learning
+} // namespace bn
+
+#endif // BNI_LEARNING_GREEDY_HPP

@@ -406,6 +406,52 @@ int bn_score_log_cpt(bn_engine *eng, double *out);
 int bn_score_rows(bn_engine *eng, bn_info_table *table, int32_t n_sel, const int32_t *nodes, double *ll_out);
 int bn_score_nodes(bn_engine *eng, bn_info_table *table, double *ll_node_out, uint64_t *family_counts_out);
 
+/* ---- structure learning: batched family scores, and the scan of greedy / K2 (reference bayesian/learning/greedy.hpp,
+ *      k2_algorithm.hpp).  AIC and MDL are decomposable: adding u -> c changes the family term of c and the parameter count. ----
+ *
+ *   A GROUP is a child c, a base parent list (strictly increasing node ids, c not among them) and candidates u_0 .. u_{m-1} (not
+ *   in the base, not c, no duplicates; m may be 0).  It stands for m + 1 families: the base (index 0) and base + {u_j} (index
+ *   1 + j).  Groups are given in CSR form: child [n_groups], base_ptr / cand_ptr [n_groups + 1], base_idx, cand_idx.
+ *   bn_learn_score_groups: one counting launch and one scoring launch for the whole batch (several such passes when the count
+ *   scratch would pass 256 MiB).  Per family, over the entries r of the table the fitted model would have (parents in increasing
+ *   node id, first parent most significant, state least -- bn_fit_cpt's layout):
+ *     N[r]   exact uint64 count of the samples showing entry r (integer atomics: independent of grouping, chunking, split, order);
+ *     ll     = sum over the entries with N[r] != 0 of double(N[r]) * log(double(N[r]) / double(row total)) -- the division is
+ *              bn_fit_cpt's, so the argument of the logarithm has the bits of the fitted CPT entry; log is the DEVICE's fp64 log
+ *              (not libm's: ll is within a few ulp per term of bn_score_nodes on the fitted model, not bit-equal to it); the order of
+ *              additions is bn_score_nodes': 256 partial sums (partial t takes r = t, t + 256, ... from +0.0), folded by halves.
+ *   ll is a function of the family's counts alone: the same family scored alone, as a base, as a candidate, anywhere in any
+ *   batch, has the same bits.  ll_out [n_groups + candidates] is group-major, base first; counts_out is NULL or receives every
+ *   family's N back to back in that order.  The environment variable BN_LEARN_SPLITS (> 0) fixes the number of workgroups the
+ *   patterns are split over (default: chosen from the shapes; no result depends on it).
+ *   Limits (BN_ERR_ARG, the text names the group): at most 16 parents per family, family table <= 2^20 entries.
+ *
+ *   bn_learner holds a graph over the table's columns, every node's family term ll[v], the exact parameter count and the score:
+ *     likelihood = 0.0; for v = 0 .. n - 1: likelihood -= ll[v];
+ *     AIC (criterion 0) = likelihood + double(params); MDL (1) = likelihood + double(params) * (log2(double(total)) / 2).
+ *   bn_learn_try_parents is the inner loop of greedy.hpp:39-58 / :82-97 and k2_algorithm.hpp:47-61 for one child: it walks cand in
+ *   the given order; a candidate that is the child, already a parent, reachable from the child (the edge would close a cycle,
+ *   graph.hpp:268-275), or whose family would exceed max_parents or the limits above is not added (accepted_out 0; the last is
+ *   a difference from the reference, which has no limits); any other is accepted iff the score with it is strictly smaller than
+ *   the current score.  All remaining candidates are scored against the current parents as one group; the first in order that
+ *   improves is accepted and the rest re-scored: device passes per call = acceptances + 1 at most.  The starting graph may have
+ *   edges (in_ptr / in_idx, any parent order); BN_ERR_ARG if it has a cycle, a duplicate edge or a family over the limits.
+ *   bn_learn_structure: in_ptr_out [n + 1], in_idx_out [edges] ("edges" of bn_learn_get), parents increasing per node.
+ *   bn_learn_get names: "families_scored", "passes", "count_ns", "score_ns" (device time of the two kernels, summed), "count_bytes"
+ *   (what the counting kernel had to read, from the shapes: per chunk of G candidates P * (8 + base parents + 1 + G)), "edges",
+ *   "parameters".  The learner borrows the table: destroy the learner first.  Work runs on the table's stream. */
+int bn_learn_score_groups(bn_info_table *table, int32_t n_groups, const int32_t *child, const int32_t *base_ptr,
+                          const int32_t *base_idx, const int32_t *cand_ptr, const int32_t *cand_idx, double *ll_out,
+                          uint64_t *counts_out);
+typedef struct bn_learner bn_learner;
+int bn_learn_create(bn_info_table *table, const int32_t *in_ptr, const int32_t *in_idx, int32_t criterion, int32_t max_parents,
+                    bn_learner **out);
+int bn_learn_try_parents(bn_learner *L, int32_t child, int32_t n_cand, const int32_t *cand, uint8_t *accepted_out);
+int bn_learn_score(const bn_learner *L, double *score_out);
+int bn_learn_structure(const bn_learner *L, int32_t *in_ptr_out, int32_t *in_idx_out);
+int bn_learn_get(const bn_learner *L, const char *name, int64_t *out);
+void bn_learn_destroy(bn_learner *L);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
