@@ -8,7 +8,7 @@ from .flat import Evidence, FlatModel, from_parent_lists  # noqa: F401
 from . import synth  # noqa: F401
 
 _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters")
-_LEARNING = ("Greedy", "K2", "Learner", "score_groups")
+_LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure")
 __all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING]
 
 

@@ -127,6 +127,12 @@ SYMBOLS = [
     ("bn_learn_structure", ctypes.c_int, [ctypes.c_void_p, i32p, i32p]),
     ("bn_learn_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, i64p]),
     ("bn_learn_destroy", None, [ctypes.c_void_p]),
+    ("bn_learn_score_subsets", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, ctypes.c_int32, i32p, f64p,
+                                              ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_learn_best_parents", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, u8p]),
+    ("bn_learn_terms", ctypes.c_int, [ctypes.c_void_p, f64p, i64p]),
+    ("bn_learn_brute_force_hint", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, ctypes.c_int32, i32p]),
+    ("bn_learn_brute_force", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, f64p]),
 ]
 
 

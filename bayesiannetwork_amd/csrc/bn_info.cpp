@@ -295,6 +295,9 @@ extern "C" int bn_info_get(const bn_info_table* t, const char* name, int64_t* va
     if (s == "n_vars") *value_out = t->n;
     else if (s == "n_patterns") *value_out = t->P;
     else if (s == "digit_passes") *value_out = t->D;
-    else return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes)");
+    else if (s == "learn_count_ns") *value_out = int64_t(t->learn_count_ns);
+    else if (s == "learn_lattice_ns") *value_out = int64_t(t->learn_lattice_ns);
+    else if (s == "learn_score_ns") *value_out = int64_t(t->learn_score_ns);
+    else return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes, learn_count_ns, learn_lattice_ns, learn_score_ns)");
     return BN_OK;
 }

@@ -17,6 +17,8 @@ struct bn_info_table {
     DeviceBuf<unsigned long long> d_w;
     DeviceBuf<uint8_t> d_wd;
     float last_pairs_ms = 0.0f;
+    // device time of the kernels of the last bn_learn_score_groups / bn_learn_score_subsets call (bn_info_get "learn_*_ns")
+    double learn_count_ns = 0.0, learn_lattice_ns = 0.0, learn_score_ns = 0.0;
 
     InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
     ~bn_info_table() {   // (the members' own destructors would run after the guard's)

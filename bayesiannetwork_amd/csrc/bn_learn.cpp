@@ -3,6 +3,8 @@
 // device-resident pattern table; bn_learner holds a graph, every node's family term and the score, and bn_learn_try_parents is the
 // reference's inner loop for one child with one device pass per ACCEPTED edge (plus one) instead of one fit and one score of the whole
 // graph per candidate.  The logarithm is the device's fp64 log: the learner's score is its own stated function of the counts.
+// bn_learn_score_subsets scores EVERY subset of a candidate parent set from one count of the top family (bn_learn_lattice.hip);
+// bn_learn_best_parents, bn_learn_brute_force_hint and bn_learn_brute_force are the reference's bayesian/learning/brute_force.hpp on it.
 #include <cmath>
 #include <memory>
 
@@ -25,6 +27,8 @@ struct LearnTimes {
     double count_ns = 0.0, score_ns = 0.0;
     int64_t families = 0, passes = 0;
     int64_t count_bytes = 0;   // what the counting kernel has to read, from the shapes: per chunk P * (8 + base + 1 + candidates)
+    double lattice_ns = 0.0;   // the subset lattice's kernel(s)
+    int64_t subsets = 0;       // families made by the lattice (the top family included)
 };
 
 std::string gname(size_t g) { return "group " + std::to_string(g) + ": "; }
@@ -191,6 +195,7 @@ int run_groups(bn_info_table* t, const std::vector<GroupIn>& groups, double* ll_
     const LearnArgs a{t->d_T, t->d_w, t->P, t->Ppad, d_chunks, d_par_id, d_par_k, d_cand_id, d_cand_k, d_cand_cell, d_N, d_fams, d_ll,
                       counts_out ? d_out.get() : nullptr};
     size_t fam_at = 0;
+    double call_count_ns = 0.0, call_score_ns = 0.0;
     for (size_t pi = 0; pi < passes.size(); ++pi) {
         const Pass& p = passes[pi];
         const int32_t n_chunks = p.chunk1 - p.chunk0;
@@ -214,12 +219,12 @@ int run_groups(bn_info_table* t, const std::vector<GroupIn>& groups, double* ll_
             return fail(BN_ERR_HIP, std::string("family score kernel: ") + hipGetErrorString(hipError_t(err)));
         HIPCHK(hipEventRecord(ev2, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (times) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-            times->count_ns += double(ms) * 1e6;
-            HIPCHK(hipEventElapsedTime(&ms, ev1, ev2));
-            times->score_ns += double(ms) * 1e6;
+        {
+            float ms_count = 0.0f, ms_score = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms_count, ev0, ev1));
+            HIPCHK(hipEventElapsedTime(&ms_score, ev1, ev2));
+            call_count_ns += double(ms_count) * 1e6;
+            call_score_ns += double(ms_score) * 1e6;
         }
         fam_at = fam_end;
     }
@@ -228,10 +233,178 @@ int run_groups(bn_info_table* t, const std::vector<GroupIn>& groups, double* ll_
     if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, d_out, size_t(out_cells) * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (size_t i = 0; i < n_fams; ++i) ll_out[size_t(order[i])] = ll[i];
+    t->learn_count_ns = call_count_ns;
+    t->learn_lattice_ns = 0.0;
+    t->learn_score_ns = call_score_ns;
     if (times) {
+        times->count_ns += call_count_ns;
+        times->score_ns += call_score_ns;
         times->families += int64_t(n_fams);
         times->passes += 1;
         for (const LearnChunk& c : chunks) times->count_bytes += t->P * int64_t(8 + c.n_base + 1 + c.n_cand);
+    }
+    return BN_OK;
+}
+
+// ---- the subset lattice: base + every subset of the candidates, from ONE count of the top family (bn_learn_lattice.hip) ----------
+
+struct SubsetShape {
+    std::vector<int32_t> id, k, bit;   // the top family's variables in increasing id; bit: the candidate's index, -1 for a base parent
+    int32_t kc = 1;
+    int64_t top_cells = 0, all_cells = 0;
+};
+
+int check_subsets(const bn_info_table* t, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand, SubsetShape& sh) {
+    const int32_t n = t->n;
+    if (child < 0 || child >= n) return fail(BN_ERR_ARG, "subsets: child id " + std::to_string(child) + " out of range");
+    if (n_base < 0 || m < 0 || (n_base > 0 && !base) || (m > 0 && !cand)) return fail(BN_ERR_ARG, "subsets: bad parent or candidate list");
+    if (int64_t(n_base) + m > kLearnMaxParents)
+        return fail(BN_ERR_ARG, "subsets: the top family has " + std::to_string(int64_t(n_base) + m) + " parents (n_base + m at most " +
+                                    std::to_string(kLearnMaxParents) + ")");
+    std::vector<std::pair<int32_t, int32_t>> vars;
+    for (int32_t j = 0; j < n_base + m; ++j) {
+        const int32_t u = j < n_base ? base[j] : cand[j - n_base];
+        const char* what = j < n_base ? "parent" : "candidate";
+        if (u < 0 || u >= n) return fail(BN_ERR_ARG, std::string("subsets: ") + what + " id " + std::to_string(u) + " out of range");
+        if (u == child) return fail(BN_ERR_ARG, std::string("subsets: the child is among its ") + what + "s");
+        for (const auto& v : vars)
+            if (v.first == u) return fail(BN_ERR_ARG, std::string("subsets: ") + what + " " + std::to_string(u) + " listed twice");
+        vars.emplace_back(u, j < n_base ? -1 : j - n_base);
+    }
+    std::sort(vars.begin(), vars.end());
+    sh.kc = t->k[size_t(child)];
+    sh.top_cells = sh.kc;
+    sh.all_cells = sh.kc;
+    for (const auto& v : vars) {
+        const int64_t ku = t->k[size_t(v.first)];
+        sh.id.push_back(v.first);
+        sh.k.push_back(int32_t(ku));
+        sh.bit.push_back(v.second);
+        sh.top_cells *= ku;                               // (<= 2^20 * 255 before the check below)
+        sh.all_cells *= v.second < 0 ? ku : ku + 1;       // (<= 2^20 * 2^16 once the top family has passed)
+        if (sh.top_cells > kLearnMaxEntries)
+            return fail(BN_ERR_ARG, "subsets: the top family's table has more than 2^20 (" + std::to_string(kLearnMaxEntries) + ") entries");
+    }
+    if (sh.all_cells > kLearnMaxScratchCells)
+        return fail(BN_ERR_ARG, "subsets: the 2^" + std::to_string(m) + " count tables need " + std::to_string(sh.all_cells) + " cells (at most 2^25 = " +
+                                    std::to_string(kLearnMaxScratchCells) + " in the single pass)");
+    return BN_OK;
+}
+
+// ll_out [2^m] in mask order (bit j: cand[j] is a parent); counts_out: null, or every family's counts in the fitted layout, mask order
+int run_subsets(bn_info_table* t, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand, double* ll_out,
+                uint64_t* counts_out, LearnTimes* times) {
+    SubsetShape sh;
+    if (int r = check_subsets(t, child, n_base, base, m, cand, sh)) return r;
+    const int32_t nv = n_base + m, n_fams = int32_t(1) << m, full = n_fams - 1;
+    std::vector<LearnFamily> fams(static_cast<size_t>(n_fams));
+    {
+        int64_t at = 0;
+        for (int32_t mask = 0; mask < n_fams; ++mask) {
+            int64_t cells = sh.kc;
+            for (int32_t p = 0; p < nv; ++p)
+                if (sh.bit[size_t(p)] < 0 || ((mask >> sh.bit[size_t(p)]) & 1)) cells *= sh.k[size_t(p)];
+            fams[size_t(mask)] = LearnFamily{at, at, int32_t(cells), sh.kc, 1, 1};
+            at += cells;
+        }
+    }
+    const bool lds = sh.top_cells <= kLearnLdsCells;
+    // the per-level form: family `mask` from mask + x, x the absent candidate with the smallest id (the longest contiguous runs)
+    std::vector<LatticeStep> steps;
+    std::vector<int32_t> level_at(size_t(m) + 2, 0), level_max(size_t(m) + 1, 0);
+    if (!lds) {
+        std::vector<std::vector<LatticeStep>> by_level(size_t(m) + 1);
+        for (int32_t mask = 0; mask < full; ++mask) {
+            int32_t px = -1, absent = 0;
+            for (int32_t p = 0; p < nv; ++p)
+                if (sh.bit[size_t(p)] >= 0 && !((mask >> sh.bit[size_t(p)]) & 1)) {
+                    if (px < 0) px = p;
+                    ++absent;
+                }
+            int64_t inner = sh.kc;
+            for (int32_t p = px + 1; p < nv; ++p)
+                if (sh.bit[size_t(p)] < 0 || ((mask >> sh.bit[size_t(p)]) & 1)) inner *= sh.k[size_t(p)];
+            const int32_t sup = mask | (int32_t(1) << sh.bit[size_t(px)]);
+            by_level[size_t(absent)].push_back(LatticeStep{fams[size_t(sup)].count_at, fams[size_t(mask)].count_at, fams[size_t(mask)].entries,
+                                                           int32_t(inner), sh.k[size_t(px)], 0});
+            level_max[size_t(absent)] = std::max(level_max[size_t(absent)], fams[size_t(mask)].entries);
+        }
+        for (int32_t l = 1; l <= m; ++l) {
+            level_at[size_t(l)] = int32_t(steps.size());
+            steps.insert(steps.end(), by_level[size_t(l)].begin(), by_level[size_t(l)].end());
+        }
+        level_at[size_t(m) + 1] = int32_t(steps.size());
+    }
+    const std::vector<LearnChunk> chunks{LearnChunk{fams[size_t(full)].count_at, child, sh.kc, 0, nv, 0, 0, 0, int32_t(sh.top_cells), lds ? 1 : 0, 0}};
+
+    ON_DEVICE(t);
+    hipStream_t s = t->stream;
+    DeviceBuf<LearnChunk> d_chunks;
+    DeviceBuf<LearnFamily> d_fams;
+    DeviceBuf<LatticeStep> d_steps;
+    DeviceBuf<int32_t> d_par_id, d_par_k;
+    DeviceBuf<unsigned long long> d_N, d_out;
+    DeviceBuf<double> d_ll;
+    EventOwner ev0, ev1, ev2, ev3;
+    int r;
+    if ((r = upload(d_chunks, chunks, s)) || (r = upload(d_fams, fams, s)) || (r = upload(d_steps, steps, s)) || (r = upload(d_par_id, sh.id, s)) ||
+        (r = upload(d_par_k, sh.k, s)) || (r = dalloc(d_N, size_t(sh.all_cells))) || (r = dalloc(d_ll, size_t(n_fams))))
+        return r;
+    if (counts_out && (r = dalloc(d_out, size_t(sh.all_cells)))) return r;
+    HIPCHK(hipEventCreate(ev0.put()));
+    HIPCHK(hipEventCreate(ev1.put()));
+    HIPCHK(hipEventCreate(ev2.put()));
+    HIPCHK(hipEventCreate(ev3.put()));
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus <= 0) cus = 256;
+    int splits = 0;
+    if (const char* env = std::getenv("BN_LEARN_SPLITS")) splits = std::atoi(env);
+    if (splits <= 0) splits = int(std::min<int64_t>(int64_t(4) * cus, (t->P + 2 * kLearnTile - 1) / (2 * kLearnTile)));   // (run_groups' rule, one chunk)
+    splits = std::max(1, std::min(splits, 65535));
+    const LearnArgs a{t->d_T, t->d_w, t->P, t->Ppad, d_chunks, d_par_id, d_par_k, nullptr, nullptr, nullptr, d_N, d_fams, d_ll,
+                      counts_out ? d_out.get() : nullptr};
+    HIPCHK(hipEventRecord(ev0, s));
+    HIPCHK(hipMemsetAsync(d_N.get() + fams[size_t(full)].count_at, 0, size_t(sh.top_cells) * 8, s));   // (the lattice writes every other cell)
+    if (int err = learn_launch_count(a, 0, 1, splits, s))
+        return fail(BN_ERR_HIP, std::string("top-family count kernel: ") + hipGetErrorString(hipError_t(err)));
+    HIPCHK(hipEventRecord(ev1, s));
+    if (lds) {
+        LatticeLds la{d_N, d_fams, n_fams, nv, int32_t(sh.top_cells), 0, {}, {}};
+        for (int32_t p = 0; p < nv; ++p) {
+            la.k[p] = sh.k[size_t(p)];
+            la.bit[p] = sh.bit[size_t(p)];
+        }
+        // 56 KiB of LDS per workgroup: two per CU
+        if (int err = learn_launch_lattice_lds(la, std::min(full, 2 * cus), s))
+            return fail(BN_ERR_HIP, std::string("subset lattice kernel: ") + hipGetErrorString(hipError_t(err)));
+    } else {
+        for (int32_t l = 1; l <= m; ++l)
+            if (int err = learn_launch_lattice_level(d_N, d_steps, level_at[size_t(l)], level_at[size_t(l) + 1] - level_at[size_t(l)],
+                                                     level_max[size_t(l)], s))
+                return fail(BN_ERR_HIP, std::string("subset lattice level kernel: ") + hipGetErrorString(hipError_t(err)));
+    }
+    HIPCHK(hipEventRecord(ev2, s));
+    if (int err = learn_launch_score(a, 0, n_fams, s))
+        return fail(BN_ERR_HIP, std::string("family score kernel: ") + hipGetErrorString(hipError_t(err)));
+    HIPCHK(hipEventRecord(ev3, s));
+    HIPCHK(hipMemcpyAsync(ll_out, d_ll, size_t(n_fams) * 8, hipMemcpyDeviceToHost, s));
+    if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, d_out, size_t(sh.all_cells) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float ms_count = 0.0f, ms_lattice = 0.0f, ms_score = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms_count, ev0, ev1));
+    HIPCHK(hipEventElapsedTime(&ms_lattice, ev1, ev2));
+    HIPCHK(hipEventElapsedTime(&ms_score, ev2, ev3));
+    t->learn_count_ns = double(ms_count) * 1e6;
+    t->learn_lattice_ns = double(ms_lattice) * 1e6;
+    t->learn_score_ns = double(ms_score) * 1e6;
+    if (times) {
+        times->count_ns += t->learn_count_ns;
+        times->lattice_ns += t->learn_lattice_ns;
+        times->score_ns += t->learn_score_ns;
+        times->families += n_fams;
+        times->subsets += n_fams;
+        times->passes += 1;
+        times->count_bytes += t->P * int64_t(8 + nv + 1);
     }
     return BN_OK;
 }
@@ -424,10 +597,358 @@ extern "C" int bn_learn_get(const bn_learner* L, const char* name, int64_t* out)
     else if (s == "count_ns") *out = int64_t(L->times.count_ns);
     else if (s == "score_ns") *out = int64_t(L->times.score_ns);
     else if (s == "count_bytes") *out = L->times.count_bytes;
+    else if (s == "lattice_ns") *out = int64_t(L->times.lattice_ns);
+    else if (s == "subsets_scored") *out = L->times.subsets;
     else if (s == "edges") {
         *out = 0;
         for (const auto& p : L->parents) *out += int64_t(p.size());
     } else if (s == "parameters") *out = L->params;
-    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, edges, parameters)");
+    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, edges, parameters)");
+    return BN_OK;
+}
+
+// ---- exhaustive search: the subset lattice per child (reference bayesian/learning/brute_force.hpp) ----------------------------------
+
+extern "C" int bn_learn_score_subsets(bn_info_table* t, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand,
+                                      double* ll_out, uint64_t* counts_out) {
+    if (!t || !ll_out) return fail(BN_ERR_ARG, "null argument");
+    return run_subsets(t, child, n_base, base, m, cand, ll_out, counts_out, nullptr);
+}
+
+namespace {
+
+// every node with a path from `from` in the learner's graph, `from` included (graph.hpp:270, is_able_trace)
+std::vector<uint8_t> reached_from(const bn_learner* L, int32_t from) {
+    std::vector<uint8_t> reached(size_t(L->n), 0);
+    std::vector<int32_t> stack{from};
+    reached[size_t(from)] = 1;
+    while (!stack.empty()) {
+        const int32_t v = stack.back();
+        stack.pop_back();
+        for (int32_t c : L->children[size_t(v)])
+            if (!reached[size_t(c)]) { reached[size_t(c)] = 1; stack.push_back(c); }
+    }
+    return reached;
+}
+
+int check_ids(const bn_learner* L, const char* what, int32_t count, const int32_t* ids) {
+    if (count < 0 || (count > 0 && !ids)) return fail(BN_ERR_ARG, std::string("null argument or negative count: ") + what);
+    for (int32_t i = 0; i < count; ++i)
+        if (ids[i] < 0 || ids[i] >= L->n) return fail(BN_ERR_ARG, std::string(what) + " id " + std::to_string(ids[i]) + " out of range");
+    return BN_OK;
+}
+
+// One node whose parent set an enumeration varies: its candidates (nodes that are neither the node nor a parent of it in the
+// starting graph, each once), the family term of every subset of them on top of the starting parents, and the subset in hand.
+struct Slot {
+    int32_t node = 0, mask = 0, best_mask = 0;
+    std::vector<int32_t> cand;
+    std::vector<double> ll;   // [2^cand.size()], mask order
+    int32_t bit_of(int32_t u) const {
+        for (size_t j = 0; j < cand.size(); ++j)
+            if (cand[j] == u) return int32_t(j);
+        return -1;
+    }
+};
+
+// The graph an enumeration walks: the learner's, plus the candidate edges in hand.  add_edge's refusals (graph.hpp:268-275: the
+// edge exists or closes a cycle) and the library's limit on the number of parents.
+struct Walk {
+    bn_learner* L;
+    std::vector<Slot> slots;
+    std::vector<int32_t> slot_of;                  // per node, or -1
+    std::vector<std::vector<int32_t>> children;    // the learner's, plus the edges in hand (added and removed last in, first out)
+    std::vector<int32_t> n_par;
+    std::vector<double> ll;                        // family term of every node in the graph in hand
+    std::vector<int32_t> stamp, stack;
+    int32_t now = 0;
+    int64_t params = 0;
+
+    explicit Walk(bn_learner* learner)
+        : L(learner), slot_of(size_t(learner->n), -1), children(learner->children), n_par(size_t(learner->n)), ll(learner->ll),
+          stamp(size_t(learner->n), 0), params(learner->params) {
+        for (int32_t v = 0; v < L->n; ++v) n_par[size_t(v)] = int32_t(L->parents[size_t(v)].size());
+    }
+
+    // a slot for `node` with the nodes of `from` as candidates; one lattice call
+    int add_slot(int32_t node, int32_t count, const int32_t* from) {
+        if (slot_of[size_t(node)] >= 0) return BN_OK;
+        Slot sl;
+        sl.node = node;
+        const std::vector<int32_t>& par = L->parents[size_t(node)];
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t u = from[i];
+            if (u == node || std::binary_search(par.begin(), par.end(), u) || sl.bit_of(u) >= 0) continue;
+            sl.cand.push_back(u);
+        }
+        if (sl.cand.size() > size_t(kLearnMaxParents))
+            return fail(BN_ERR_ARG, "node " + std::to_string(node) + ": " + std::to_string(sl.cand.size()) + " candidate parents (at most " +
+                                        std::to_string(kLearnMaxParents) + " minus its parents)");
+        sl.ll.assign(size_t(1) << sl.cand.size(), 0.0);
+        if (int r = run_subsets(L->t, node, int32_t(par.size()), par.data(), int32_t(sl.cand.size()), sl.cand.data(), sl.ll.data(), nullptr, &L->times))
+            return r;
+        slot_of[size_t(node)] = int32_t(slots.size());
+        slots.push_back(std::move(sl));
+        return BN_OK;
+    }
+
+    bool reaches(int32_t from, int32_t to) {
+        ++now;
+        stack.assign(1, from);
+        stamp[size_t(from)] = now;
+        while (!stack.empty()) {
+            const int32_t v = stack.back();
+            stack.pop_back();
+            if (v == to) return true;
+            for (int32_t c : children[size_t(v)])
+                if (stamp[size_t(c)] != now) { stamp[size_t(c)] = now; stack.push_back(c); }
+        }
+        return false;
+    }
+
+    // graph.add_edge(u, c): false when refused
+    bool add(int32_t u, int32_t c) {
+        const int32_t si = slot_of[size_t(c)];
+        if (si < 0) return false;
+        Slot& sl = slots[size_t(si)];
+        const int32_t b = sl.bit_of(u);   // (-1: the node itself, or a parent in the starting graph)
+        if (b < 0 || ((sl.mask >> b) & 1)) return false;
+        if (n_par[size_t(c)] >= std::min(L->max_parents, kLearnMaxParents)) return false;
+        if (reaches(c, u)) return false;
+        flip(sl, b, u, c, true);
+        return true;
+    }
+    void erase(int32_t u, int32_t c) {
+        Slot& sl = slots[size_t(slot_of[size_t(c)])];
+        flip(sl, sl.bit_of(u), u, c, false);
+    }
+    void flip(Slot& sl, int32_t b, int32_t u, int32_t c, bool on) {
+        int64_t rows = 1;   // the family's rows without u
+        for (int32_t x : L->parents[size_t(c)]) rows *= L->t->k[size_t(x)];
+        for (size_t j = 0; j < sl.cand.size(); ++j)
+            if (int32_t(j) != b && ((sl.mask >> j) & 1)) rows *= L->t->k[size_t(sl.cand[j])];
+        const int64_t with = L->family_params(c, rows * L->t->k[size_t(u)]), without = L->family_params(c, rows);
+        if (on) {
+            sl.mask |= int32_t(1) << b;
+            children[size_t(u)].push_back(c);
+            ++n_par[size_t(c)];
+            params += with - without;
+        } else {
+            sl.mask &= ~(int32_t(1) << b);
+            children[size_t(u)].pop_back();
+            --n_par[size_t(c)];
+            params -= with - without;
+        }
+        ll[size_t(c)] = sl.ll[size_t(sl.mask)];
+    }
+    double penalised(double likelihood) const {
+        return L->criterion == 0 ? likelihood + double(params) : likelihood + double(params) * L->penalty;
+    }
+    void keep() {
+        for (Slot& sl : slots) sl.best_mask = sl.mask;
+    }
+    // the best graph becomes the learner's
+    void commit() {
+        for (const Slot& sl : slots) {
+            const int32_t c = sl.node;
+            std::vector<int32_t>& par = L->parents[size_t(c)];
+            const int64_t before = L->family_params(c, L->rows_of(c));
+            for (size_t j = 0; j < sl.cand.size(); ++j)
+                if ((sl.best_mask >> j) & 1) {
+                    par.insert(std::lower_bound(par.begin(), par.end(), sl.cand[j]), sl.cand[j]);
+                    L->children[size_t(sl.cand[j])].push_back(c);
+                }
+            L->ll[size_t(c)] = sl.ll[size_t(sl.best_mask)];
+            L->params += L->family_params(c, L->rows_of(c)) - before;
+        }
+        L->score = L->score_with(-1, 0.0, L->params);
+    }
+};
+
+}  // namespace
+
+extern "C" int bn_learn_best_parents(bn_learner* L, int32_t child, int32_t n_cand, const int32_t* cand, uint8_t* taken_out) {
+    if (!L || n_cand < 0 || (n_cand > 0 && (!cand || !taken_out))) return fail(BN_ERR_ARG, "null argument or n_cand < 0");
+    if (child < 0 || child >= L->n) return fail(BN_ERR_ARG, "child id " + std::to_string(child) + " out of range");
+    if (int r = check_ids(L, "candidate", n_cand, cand)) return r;
+    std::fill(taken_out, taken_out + n_cand, uint8_t(0));
+    const std::vector<uint8_t> reached = reached_from(L, child);
+    std::vector<int32_t>& par = L->parents[size_t(child)];
+    const int32_t kc = L->t->k[size_t(child)];
+    const int64_t rows = L->rows_of(child);
+    const int32_t room = std::min(L->max_parents, kLearnMaxParents) - int32_t(par.size());
+    // bn_learn_try_parents' filter: the child and what it reaches, a parent, a second listing, no room, a family over the size limit
+    std::vector<int32_t> surv, surv_at;
+    std::vector<uint8_t> listed(size_t(L->n), 0);
+    for (int32_t i = 0; i < n_cand && room > 0; ++i) {
+        const int32_t u = cand[i];
+        if (reached[size_t(u)] || listed[size_t(u)] || std::binary_search(par.begin(), par.end(), u)) continue;
+        if (rows * L->t->k[size_t(u)] * kc > kLearnMaxEntries) continue;
+        listed[size_t(u)] = 1;
+        surv.push_back(u);
+        surv_at.push_back(i);
+    }
+    const int32_t m = int32_t(surv.size());
+    if (m == 0) return BN_OK;
+    if (m > kLearnMaxParents)
+        return fail(BN_ERR_ARG, std::to_string(m) + " candidates may be added (at most " + std::to_string(kLearnMaxParents) + " minus the parents)");
+    std::vector<double> ll(size_t(1) << m);
+    if (int r = run_subsets(L->t, child, int32_t(par.size()), par.data(), m, surv.data(), ll.data(), nullptr, &L->times)) return r;
+    // the reference's visiting order (brute_force.hpp:104-111): "not added" before "added", cand[0] outermost
+    int32_t best_mask = 0;
+    int64_t best_params = L->params;
+    double best = L->score_with(child, ll[0], L->params);
+    for (int32_t r = 1; r < (int32_t(1) << m); ++r) {
+        int32_t mask = 0, size = 0;
+        int64_t rows_r = rows;
+        for (int32_t j = 0; j < m; ++j)
+            if ((r >> (m - 1 - j)) & 1) {
+                mask |= int32_t(1) << j;
+                ++size;
+                rows_r *= L->t->k[size_t(surv[size_t(j)])];
+            }
+        if (size > room) continue;
+        const int64_t params_r = L->params - L->family_params(child, rows) + L->family_params(child, rows_r);
+        const double score_r = L->score_with(child, ll[size_t(mask)], params_r);
+        if (score_r < best) {
+            best = score_r;
+            best_mask = mask;
+            best_params = params_r;
+        }
+    }
+    if (best_mask == 0) return BN_OK;   // the empty subset keeps the graph
+    for (int32_t j = 0; j < m; ++j)
+        if ((best_mask >> j) & 1) {
+            par.insert(std::lower_bound(par.begin(), par.end(), surv[size_t(j)]), surv[size_t(j)]);
+            L->children[size_t(surv[size_t(j)])].push_back(child);
+            taken_out[surv_at[size_t(j)]] = 1;
+        }
+    L->ll[size_t(child)] = ll[size_t(best_mask)];
+    L->params = best_params;
+    L->score = best;
+    return BN_OK;
+}
+
+extern "C" int bn_learn_terms(const bn_learner* L, double* ll_out, int64_t* params_out) {
+    if (!L || !ll_out) return fail(BN_ERR_ARG, "null argument");
+    std::copy(L->ll.begin(), L->ll.end(), ll_out);
+    if (params_out) *params_out = L->params;
+    return BN_OK;
+}
+
+extern "C" int bn_learn_brute_force_hint(bn_learner* L, int32_t n_par, const int32_t* par, int32_t n_child, const int32_t* child) {
+    if (!L) return fail(BN_ERR_ARG, "null argument");
+    if (int r = check_ids(L, "parent", n_par, par)) return r;
+    if (int r = check_ids(L, "child", n_child, child)) return r;
+    // no add_edge can be refused for a cycle when no child reaches a parent node (a child itself included): every new edge starts
+    // at a parent node, so a path from a child to a parent node would have to exist already
+    std::vector<uint8_t> is_par(size_t(L->n), 0);
+    for (int32_t i = 0; i < n_par; ++i) is_par[size_t(par[i])] = 1;
+    bool decomposed = true;
+    for (int32_t i = 0; i < n_child && decomposed; ++i) {
+        const std::vector<uint8_t> reached = reached_from(L, child[i]);
+        for (int32_t v = 0; v < L->n && decomposed; ++v)
+            if (reached[size_t(v)] && is_par[size_t(v)]) decomposed = false;
+    }
+    if (decomposed) {
+        // per child the other children's edges are fixed terms of the sum, so the depth-first search is one search per child; a
+        // child listed again finds its best subset in place
+        std::vector<uint8_t> taken(size_t(std::max(n_par, 1)));
+        std::vector<uint8_t> done(size_t(L->n), 0);
+        for (int32_t i = 0; i < n_child; ++i) {
+            if (done[size_t(child[i])]) continue;
+            done[size_t(child[i])] = 1;
+            if (int r = bn_learn_best_parents(L, child[i], n_par, par, taken.data())) return r;
+        }
+        return BN_OK;
+    }
+    const int64_t edges = int64_t(n_par) * n_child;
+    if (edges > 20)
+        return fail(BN_ERR_ARG, std::to_string(edges) + " possible edges with a child that reaches a parent node: the literal enumeration takes at most 20");
+    Walk w(L);
+    for (int32_t i = 0; i < n_child; ++i)
+        if (int r = w.add_slot(child[i], n_par, par)) return r;
+    double best = L->score;
+    // brute_force.hpp:85-113, the possible edges parent-major (:61-67)
+    struct Rec {
+        Walk& w;
+        const int32_t *par, *child;
+        int32_t n_child;
+        int64_t edges;
+        double& best;
+        void run(int64_t e) {
+            if (e == edges) {
+                double likelihood = 0.0;
+                for (double x : w.ll) likelihood -= x;
+                const double now = w.penalised(likelihood);
+                if (now < best) {
+                    best = now;
+                    w.keep();
+                }
+                return;
+            }
+            run(e + 1);
+            const int32_t u = par[e / n_child], c = child[e % n_child];
+            if (w.add(u, c)) {
+                run(e + 1);
+                w.erase(u, c);
+            }
+        }
+    } rec{w, par, child, n_child, edges, best};
+    rec.run(0);
+    w.commit();
+    return BN_OK;
+}
+
+extern "C" int bn_learn_brute_force(bn_learner* L, int32_t n_v, const int32_t* vertexes, double* eval_out) {
+    if (!L) return fail(BN_ERR_ARG, "null argument");
+    if (int r = check_ids(L, "vertex", n_v, vertexes)) return r;
+    if (n_v > 8) return fail(BN_ERR_ARG, std::to_string(n_v) + " vertexes (at most 8: 2 027 025 graphs)");
+    for (int32_t i = 0; i < n_v; ++i)
+        for (int32_t j = 0; j < i; ++j)
+            if (vertexes[i] == vertexes[j]) return fail(BN_ERR_ARG, "vertex " + std::to_string(vertexes[i]) + " listed twice");
+    Walk w(L);
+    for (int32_t i = 0; i < n_v; ++i)
+        if (int r = w.add_slot(vertexes[i], n_v, vertexes)) return r;
+    // eval_(graph, vertexes): the likelihood over `vertexes` in the given order, the parameters of the whole graph
+    auto eval = [&]() {
+        double likelihood = 0.0;
+        for (int32_t i = 0; i < n_v; ++i) likelihood -= w.ll[size_t(vertexes[i])];
+        return w.penalised(likelihood);
+    };
+    double best = eval();
+    // brute_force.hpp:116-156.  Level t tries per later vertex: no edge, v_t -> v_i, v_i -> v_t.  "No edge" gives the same graph for
+    // every i, so it is walked for the first i only: a graph seen again cannot win under <.
+    struct Rec {
+        Walk& w;
+        const int32_t* v;
+        int32_t n_v;
+        double& best;
+        decltype(eval)& eval_;
+        void run(int32_t t) {
+            if (t == n_v - 1) {
+                const double now = eval_();
+                if (now < best) {
+                    best = now;
+                    w.keep();
+                }
+                return;
+            }
+            for (int32_t i = t + 1; i < n_v; ++i) {
+                if (i == t + 1) run(t + 1);
+                if (w.add(v[t], v[i])) {
+                    run(t + 1);
+                    w.erase(v[t], v[i]);
+                }
+                if (w.add(v[i], v[t])) {
+                    run(t + 1);
+                    w.erase(v[i], v[t]);
+                }
+            }
+        }
+    } rec{w, vertexes, n_v, best, eval};
+    if (n_v > 0) rec.run(0);
+    w.commit();
+    if (eval_out) *eval_out = best;
     return BN_OK;
 }

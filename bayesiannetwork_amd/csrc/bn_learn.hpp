@@ -1,6 +1,6 @@
 // bn_learn.hpp -- scoring many candidate families of a child in one pass over a pattern table (the primitive under the reference's
 // bayesian/learning/greedy.hpp and k2_algorithm.hpp: AIC / MDL are decomposable, so a candidate edge u -> c changes one family term).
-// Host-side view of the kernels in bn_learn_kernels.hip; the C ABI (bn_learn_* of include/bn_mi355x.h) is in bn_learn.cpp.
+// Host-side view of the kernels in bn_learn_kernels.hip and bn_learn_lattice.hip; the C ABI (bn_learn_* of include/bn_mi355x.h) is in bn_learn.cpp.
 #pragma once
 
 #include <cstdint>
@@ -62,5 +62,29 @@ struct LearnArgs {
 // each returns a hipError_t value (0: success).  chunk0 / fam0: first chunk / family of the pass; N is the pass's own scratch.
 int learn_launch_count(const LearnArgs& a, int32_t chunk0, int32_t n_chunks, int splits, void* stream);
 int learn_launch_score(const LearnArgs& a, int32_t fam0, int32_t n_fams, void* stream);
+
+// ---- the subset lattice (bn_learn_lattice.hip): the counts of base + every subset of the candidates, from the counts of the TOP
+// family base + all candidates.  The top family's variables are held in increasing id (position 0 most significant); family `mask`
+// (bit j: candidate j is a parent) keeps the positions whose variable is a base parent or a candidate with its bit set.  Every
+// family is written in the fitted layout, so the scoring kernel reads it with ku = low = 1.
+
+// The one-launch form (top family <= kLearnLdsCells cells): everything a workgroup needs to sum a family out of the top table.
+struct LatticeLds {
+    unsigned long long* N;        // the count scratch; the top family is at fams[n_fams - 1].count_at
+    const LearnFamily* fams;      // [n_fams = 2^m] in mask order; count_at: where the family's counts go
+    int32_t n_fams, nv, top_cells, pad_;
+    int32_t k[kLearnMaxParents];      // arity of the variable at position p
+    int32_t bit[kLearnMaxParents];    // candidate index of position p, or -1: a base parent
+};
+
+// The per-level form: family `out` = the family `in` with the variable of arity kx summed out, `inner` cells below it.
+//   out[h * inner + l] = sum over s < kx of in[(h * kx + s) * inner + l],  h * inner + l < cells
+struct LatticeStep {
+    int64_t in_at, out_at;
+    int32_t cells, inner, kx, pad_;
+};
+
+int learn_launch_lattice_lds(const LatticeLds& a, int blocks, void* stream);
+int learn_launch_lattice_level(unsigned long long* N, const LatticeStep* steps, int32_t step0, int32_t n_steps, int32_t max_cells, void* stream);
 
 }  // namespace bnmi

@@ -26,6 +26,7 @@
 #include <random>
 #include <stdexcept>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <bayesian/graph.hpp>
@@ -88,6 +89,27 @@ public:
                 throw std::logic_error("bn::learning: the graph refused an edge the learner accepted");
     }
 
+    // brute_force::operator()(graph, vertexes) on the learner; the best graph's new edges are added to `graph`.  Returns the
+    // reference's evaluated quantity (the likelihood over `vertexes`, the penalty of the whole graph).
+    double brute_force(graph_t& graph, std::vector<vertex_type> const& vertexes)
+    {
+        auto const vs = indexes_of(vertexes);
+        double eval = 0.0;
+        mi355x::engine_handle::check(bn_learn_brute_force(learner_, static_cast<std::int32_t>(vs.size()), vs.data(), &eval));
+        apply_structure(graph);
+        return eval;
+    }
+
+    // brute_force::learn_with_hint on the learner; returns the score
+    double brute_force_hint(graph_t& graph, std::vector<vertex_type> const& parent_nodes, std::vector<vertex_type> const& child_nodes)
+    {
+        auto const ps = indexes_of(parent_nodes), cs = indexes_of(child_nodes);
+        mi355x::engine_handle::check(bn_learn_brute_force_hint(learner_, static_cast<std::int32_t>(ps.size()), ps.data(),
+                                                               static_cast<std::int32_t>(cs.size()), cs.data()));
+        apply_structure(graph);
+        return score();
+    }
+
     double score() const
     {
         double s = 0.0;
@@ -96,6 +118,34 @@ public:
     }
 
 private:
+    std::vector<std::int32_t> indexes_of(std::vector<vertex_type> const& vs) const
+    {
+        std::vector<std::int32_t> out;
+        for(auto const& v : vs) out.push_back(index_of(v));
+        return out;
+    }
+
+    // every edge of the learner's graph that `graph` lacks is added (the searches only add edges; a subset of a DAG's edges
+    // closes no cycle, so the order does not matter)
+    void apply_structure(graph_t& graph)
+    {
+        std::int64_t edges = 0;
+        mi355x::engine_handle::check(bn_learn_get(learner_, "edges", &edges));
+        std::vector<std::int32_t> in_ptr(nodes_.size() + 1, 0), in_idx(static_cast<std::size_t>(edges) + 1, 0);
+        mi355x::engine_handle::check(bn_learn_structure(learner_, in_ptr.data(), in_idx.data()));
+        for(std::size_t v = 0; v < nodes_.size(); ++v)
+        {
+            auto const have = graph.in_vertexes(nodes_[v]);
+            for(std::int32_t e = in_ptr[v]; e < in_ptr[v + 1]; ++e)
+            {
+                auto const& parent = nodes_[static_cast<std::size_t>(in_idx[static_cast<std::size_t>(e)])];
+                if(std::find(have.begin(), have.end(), parent) != have.end()) continue;
+                if(!graph.add_edge(parent, nodes_[v]))
+                    throw std::logic_error("bn::learning: the graph refused an edge the learner added");
+            }
+        }
+    }
+
     std::int32_t index_of(vertex_type const& v) const
     {
         auto const it = std::find(nodes_.begin(), nodes_.end(), v);
@@ -131,6 +181,39 @@ public:
 
     double operator()(graph_t& graph, std::vector<vertex_type> vertexes)
     {
+        draw_visits(std::move(vertexes));
+        return run(graph);
+    }
+
+    // only edges from a node of parent_nodes to a node of child_nodes
+    double learn_with_hint(graph_t& graph, std::vector<vertex_type> parent_nodes, std::vector<vertex_type> child_nodes)
+    {
+        draw_hint_visits(std::move(parent_nodes), std::move(child_nodes));
+        return run(graph);
+    }
+
+    // NOT IN THE REFERENCE: the same two searches on a learner session that is already open (stepwise_structure.hpp runs every
+    // step of a run on one); the CPTs are left to the caller.  Each returns the session's score.
+    double learn_on(detail::learner_session& session, graph_t& graph, std::vector<vertex_type> vertexes)
+    {
+        draw_visits(std::move(vertexes));
+        for(auto const& visit : visits_) session.try_parents(graph, visit.child, visit.candidates);
+        return session.score();
+    }
+
+    double hint_on(detail::learner_session& session, graph_t& graph, std::vector<vertex_type> parent_nodes, std::vector<vertex_type> child_nodes)
+    {
+        draw_hint_visits(std::move(parent_nodes), std::move(child_nodes));
+        for(auto const& visit : visits_) session.try_parents(graph, visit.child, visit.candidates);
+        return session.score();
+    }
+
+    // NOT IN THE REFERENCE: the children of the last run and the candidates each was offered, in order
+    std::vector<visit_t> const& last_visits() const { return visits_; }
+
+private:
+    void draw_visits(std::vector<vertex_type> vertexes)
+    {
         std::shuffle(vertexes.begin(), vertexes.end(), engine_);
         visits_.clear();
         for(auto it = vertexes.begin(); it != vertexes.end();)
@@ -139,11 +222,9 @@ public:
             std::shuffle(++it, vertexes.end(), engine_);
             visits_.push_back(visit_t{*child_iter, std::vector<vertex_type>(it, vertexes.end())});
         }
-        return run(graph);
     }
 
-    // only edges from a node of parent_nodes to a node of child_nodes
-    double learn_with_hint(graph_t& graph, std::vector<vertex_type> parent_nodes, std::vector<vertex_type> child_nodes)
+    void draw_hint_visits(std::vector<vertex_type> parent_nodes, std::vector<vertex_type> child_nodes)
     {
         std::shuffle(std::begin(child_nodes), std::end(child_nodes), engine_);
         visits_.clear();
@@ -152,13 +233,8 @@ public:
             std::shuffle(std::begin(parent_nodes), std::end(parent_nodes), engine_);
             visits_.push_back(visit_t{child, parent_nodes});
         }
-        return run(graph);
     }
 
-    // NOT IN THE REFERENCE: the children of the last run and the candidates each was offered, in order
-    std::vector<visit_t> const& last_visits() const { return visits_; }
-
-private:
     // The shuffles draw from the engine only, never from the scores, so drawing them all first leaves every order as the
     // reference's interleaved loop has it.
     double run(graph_t& graph)

@@ -358,7 +358,8 @@ int bn_lw_states(bn_engine *eng, uint64_t n, uint8_t *states_out, double *weight
  *   bn_info_pair_counts: the exact joint counts of n_pairs pairs (pairs [n_pairs][2]) as the all-pairs
  *   computation made them: for pair i a k_x x k_y block, x the row, blocks back to back in counts_out.
  *   bn_info_last_pairs_ms: device time of the all-pairs kernel of the last pair call (0 if none ran).
- *   bn_info_get: "n_vars", "n_patterns", "digit_passes" (7-bit passes over the counts). */
+ *   bn_info_get: "n_vars", "n_patterns", "digit_passes" (7-bit passes over the counts); "learn_count_ns", "learn_lattice_ns",
+ *   "learn_score_ns": device time of the kernels of the last bn_learn_score_groups / bn_learn_score_subsets call on the table. */
 typedef struct bn_info_table bn_info_table;
 int bn_info_create(int64_t n_patterns, int32_t n_vars, const uint8_t *patterns, const uint64_t *counts,
                    const int32_t *k, int32_t device, bn_info_table **out);
@@ -451,6 +452,48 @@ int bn_learn_score(const bn_learner *L, double *score_out);
 int bn_learn_structure(const bn_learner *L, int32_t *in_ptr_out, int32_t *in_idx_out);
 int bn_learn_get(const bn_learner *L, const char *name, int64_t *out);
 void bn_learn_destroy(bn_learner *L);
+
+/* ---- exhaustive parent-set search: the subset lattice of one child, and the reference's brute_force on top of it (reference
+ *      bayesian/learning/brute_force.hpp; the between-cluster step of stepwise_structure.hpp). ----
+ *
+ *   bn_learn_score_subsets scores the 2^m families  base + {cand[j] : bit j of mask}  of one child: ll_out [2^m] by mask;
+ *   counts_out is NULL or receives every family's N in the fitted layout, family after family in mask order.  The TOP family
+ *   base + all candidates is counted once from the table; every other family's counts are made on the device by summing absent
+ *   candidates out of it (uint64 adds: exact), directly in the fitted layout, and scored by the kernel bn_learn_score_groups uses.
+ *   N and ll of a family are therefore, bit for bit, what bn_learn_score_groups gives for it.  base may come in any order; m = 0
+ *   gives the one family.  Limits (BN_ERR_ARG, the text names the number): n_base + m <= 16; the top family <= 2^20 entries; all 2^m
+ *   tables together <= 2^25 cells (one pass; there is no multi-pass lattice); ids distinct, in range, not the child.
+ *
+ *   bn_learn_best_parents: the best subset of cand to ADD to the child's parents.  cand is filtered as bn_learn_try_parents filters
+ *   it (the child, a parent, a node the child reaches, a second listing, a family over the size limit; nothing passes when the
+ *   child has max_parents parents); the m survivors are scored through the lattice -- survivors beyond its limits are an error,
+ *   not a silent cut.  A subset's score is the learner's stated function with the child's ll and the parameter count replaced;
+ *   subsets that would pass max_parents are not eligible.  The winner is the strictly smallest score, among equal values the
+ *   first in the reference's visiting order (brute_force.hpp:104-111: "not added" before "added", cand[0] outermost -- mask order
+ *   with the bit significance reversed).  The empty subset keeps the graph.  taken_out [n_cand]: 1 where the edge was added.
+ *   bn_learn_terms: ll_out [n] the family terms the score is the sum of; params_out (may be NULL) the parameter count.
+ *
+ *   bn_learn_brute_force_hint is brute_force::learn_with_hint (:51-113): every subset of the possible edges par[i] -> child[j].
+ *   When no node of child reaches a node of par in the starting graph (which also makes the two sets disjoint) no add_edge can be
+ *   refused for a cycle and the edges into different children do not interact: the search is bn_learn_best_parents(child[j], par)
+ *   for each distinct child in the order given.  Otherwise the literal depth-first enumeration runs on the host over the possible
+ *   edges parent-major, with add_edge's refusals (an existing edge, a cycle) and max_parents, over family terms fetched once per
+ *   child through the lattice; more than 20 possible edges is then BN_ERR_ARG.  A graph replaces the best on strictly smaller only.
+ *
+ *   bn_learn_brute_force is brute_force::operator()(graph, vertexes) (:32-44, :116-156), literally: level t tries, for each later
+ *   vertex v_i, no edge / v_t -> v_i / v_i -> v_t and recurses to level t + 1 (so a graph gets at most one new edge per level).
+ *   The evaluated quantity is the reference's eval_(graph, vertexes): likelihood = 0.0; likelihood -= ll[v] over vertexes IN THE
+ *   GIVEN ORDER; plus the penalty on the WHOLE graph's parameters; a graph replaces the best on strictly smaller only (a graph
+ *   met again is skipped: it cannot win).  One lattice call per vertex over the other vertexes.  n_v <= 8 (2 027 025 distinct
+ *   graphs) and distinct vertexes, else BN_ERR_ARG.  eval_out (may be NULL) receives the best evaluated quantity;
+ *   bn_learn_score afterwards gives the whole graph's score.  Both searches leave the best graph in the learner.
+ *   bn_learn_get also names "lattice_ns" (device time of the lattice kernels, summed) and "subsets_scored". */
+int bn_learn_score_subsets(bn_info_table *table, int32_t child, int32_t n_base, const int32_t *base, int32_t m, const int32_t *cand,
+                           double *ll_out, uint64_t *counts_out);
+int bn_learn_best_parents(bn_learner *L, int32_t child, int32_t n_cand, const int32_t *cand, uint8_t *taken_out);
+int bn_learn_terms(const bn_learner *L, double *ll_out, int64_t *params_out);
+int bn_learn_brute_force_hint(bn_learner *L, int32_t n_par, const int32_t *par, int32_t n_child, const int32_t *child);
+int bn_learn_brute_force(bn_learner *L, int32_t n_v, const int32_t *vertexes, double *eval_out);
 
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
