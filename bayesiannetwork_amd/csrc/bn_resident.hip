@@ -50,8 +50,18 @@ namespace bnmi {
     do {                                                                                           \
         if ((iter) == 5 && (lane_) == 0) g_tile_clock[blockIdx.x * kResidentWaves + (wave_)][k] = wall_clock64(); \
     } while (0)
+// ... and the fixed cost of the RUN, per wave (scripts/experiments/resident_clock.py): 0 kernel entry, 1 CPT loads issued,
+// 2 CPT resident (registers waited for, LDS part staged), 3 granules of the launch's first sweep published, 4 verdict of the
+// last sweep known, 5 finalize's last store issued
+constexpr int kRunClockStamps = 8;
+static __device__ unsigned long long g_run_clock[kTileClockTiles][kRunClockStamps];
+#define RUNSTAMP(k, lane_, wave_)                                                                   \
+    do {                                                                                           \
+        if ((lane_) == 0) g_run_clock[blockIdx.x * kResidentWaves + (wave_)][k] = wall_clock64();   \
+    } while (0)
 #else
 #define RSTAMP(k, iter, lane_, wave_) ((void)0)
+#define RUNSTAMP(k, lane_, wave_) ((void)0)
 #endif
 
 // Message records are exchanged between CUs / XCDs inside the launch: every record access is a
@@ -397,7 +407,9 @@ __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShare
             RSTAMP(1, it, lane, wave);  // verdict of the previous iteration known
             if (v != kGoOn || it == a.budget) {
                 const int done = v != kGoOn ? v : 0;
+                RUNSTAMP(4, lane, wave);  // verdict of the last sweep known
                 finalize(set, s, done, true);
+                RUNSTAMP(5, lane, wave);  // finalize's last store issued
                 if (blockIdx.x == 0 && wave == 0) {  // report: residual history (final since each barrier), outcome
                     const ResidentSync* sy = a.sync + set;
                     double* hist = a.b.res_hist + int64_t(set) * a.res_hist_stride;
@@ -421,6 +433,7 @@ __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShare
             if (BATCH && a.direct == 0) arrive_batch(a, sh, set, it, s, wres, lane, wave);
             else arrive(a, sh, set, it, s, wres, lane, wave);
             RSTAMP(6, it, lane, wave);  // granules published
+            if (it == 0) RUNSTAMP(3, lane, wave);
         }
         if (active == 0) break;
     }
@@ -546,7 +559,9 @@ __device__ __forceinline__ bool flow_drive(const ResidentArgs& a, int tile, int 
         RSTAMP(1, it, lane, wave);  // neighbours ready, verdict of it - 2 known
         if (v == kFlowAbort) return false;
         if (v != kFlowGoOn) {  // the run consists of n_it iterations of this launch; this wave has executed `it` (n_it or n_it + 1)
+            RUNSTAMP(4, lane, wave);
             finalize(0, a.sweep_begin + n_it, v == kFlowBudget ? 0 : int(v), n_it == it);
+            RUNSTAMP(5, lane, wave);
             return true;
         }
         const double wres = phase(0, a.sweep_begin + it);
@@ -568,6 +583,7 @@ __device__ __forceinline__ bool flow_drive(const ResidentArgs& a, int tile, int 
             }
         }
         RSTAMP(6, it, lane, wave);  // granules published
+        if (it == 0) RUNSTAMP(3, lane, wave);
     }
 }
 
@@ -700,7 +716,9 @@ __device__ __forceinline__ void flow_service(const ResidentArgs& a, BlockShared&
 // BIG: the block runs at most four waves, one per SIMD, and its kernel may use the whole register file: the CPT stays in
 // registers entirely (no LDS slots) and the contraction is left to the scheduler (no pins) -- a wave alone on its SIMD
 // has nobody to fill its dependency stalls, so instruction-level parallelism is what it runs on.
-template <int K, int M, int RC, bool BATCH, bool FLOW, bool SHARD = false, bool BIG = false>
+// UNI: every node of the network has arity K (the LEAN instantiations), so a node's beliefs start at K * node: for even K they
+// are 16-byte aligned and finalize writes them as 16-byte stores.
+template <int K, int M, int RC, bool BATCH, bool FLOW, bool SHARD = false, bool BIG = false, bool UNI = false>
 __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared& sh, const TileDesc& td, int tile, int lane, int wave,
                                               double2_t* cpt_lds) {
     static_assert(!(BATCH && FLOW), "the dataflow form runs one evidence set");
@@ -726,10 +744,15 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
         cpt[2 * q] = x.x;
         cpt[2 * q + 1] = x.y;
     }
+    RUNSTAMP(1, lane, wave);  // CPT loads issued (register part)
     if constexpr (SR < SP) {
 #pragma unroll
         for (int q = SR / 2; q < S / 2; ++q) cpt_lds[(q - SR / 2) * kWave + lane] = cp[q * kWave];
     }
+#ifdef BN_TILE_CLOCK
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    RUNSTAMP(2, lane, wave);  // CPT resident
+#endif
     bool frozen = false;  // evidence mark of this lane's node for the set in hand
     const int64_t rbase = td.rec_base / 2 + lc;  // this lane's slot in the tile's record block (double2 units)
     const MsgRef* orf = b.out_refs + td.out_base + lc;
@@ -997,6 +1020,23 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
 #pragma unroll
                             for (int ct = 0; ct < K; ++ct) PIN(out[jt][ct]);
                     }
+                    if constexpr (M == 2 && !SHARD) {
+                        // Two parents: step rr is row u0 = rr of the own state's K x K table, and all three accumulations walk it
+                        // once -- the pi-sum in cond order, out[0][u0] over u1, out[1][u1] over u0 -- from ONE read of each entry
+                        // and ONE lambda(v) * cpt product.  Every product keeps its association ((cpt pi0) pi1, (lambda cpt) pi_other)
+                        // and every accumulator its order of terms: the same bits as the general form below.
+#pragma unroll
+                        for (int x = 0; x < K; ++x) {
+                            const double r = ROW(rr * K + x);
+                            double value = r * pim[0][rr];
+                            value *= pim[1][x];
+                            acc += value;
+                            const double t = lav[ib] * r;
+                            out[0][rr] += t * pim[1][x];
+                            out[1][x] += t * pim[0][rr];
+                        }
+                        continue;
+                    }
 #pragma unroll
                     for (int x = 0; x < K; ++x) {
                         const int cond = rr * K + x;
@@ -1090,8 +1130,19 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
                 bel[i] = piv[i] * lav[i];
                 sum += bel[i];
             }
+            if constexpr (UNI && K % 2 == 0) {  // every node of the network has this (even) arity: boff = K * node, 16-byte stores
+                double2_t* b2 = reinterpret_cast<double2_t*>(beliefs + boff);
 #pragma unroll
-            for (int i = 0; i < K; ++i) beliefs[boff + i] = bel[i] / sum;
+                for (int h = 0; h < K / 2; ++h) {
+                    double2_t y;
+                    y.x = bel[2 * h] / sum;
+                    y.y = bel[2 * h + 1] / sum;
+                    b2[h] = y;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < K; ++i) beliefs[boff + i] = bel[i] / sum;
+            }
         }
     };
     if constexpr (FLOW) return flow_drive<SHARD>(a, tile, lane, wave, phase, finalize);
@@ -1109,7 +1160,7 @@ __device__ __forceinline__ bool resident_dispatch(const ResidentArgs& a, BlockSh
 #ifdef BN_RES_ONLY_RC  // experiments: one instantiation only
     return resident_tile<K, M, BN_RES_ONLY_RC, BATCH, FLOW, SHARD, BIG>(a, sh, td, tile, lane, wave, cpt_lds);
 #else
-    if constexpr (LEAN != 0) return resident_tile<K, M, 2, BATCH, FLOW, SHARD, BIG>(a, sh, td, tile, lane, wave, cpt_lds);
+    if constexpr (LEAN != 0) return resident_tile<K, M, 2, BATCH, FLOW, SHARD, BIG, true>(a, sh, td, tile, lane, wave, cpt_lds);
     if (td.cmax <= 2) return resident_tile<K, M, 2, BATCH, FLOW, SHARD, BIG>(a, sh, td, tile, lane, wave, cpt_lds);
     if (td.cmax <= 4) return resident_tile<K, M, 4, BATCH, FLOW, SHARD, BIG>(a, sh, td, tile, lane, wave, cpt_lds);
     return resident_tile<K, M, 8, BATCH, FLOW, SHARD, BIG>(a, sh, td, tile, lane, wave, cpt_lds);  // the host admits <= 8 children per node
@@ -1142,6 +1193,7 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
             for (int set = 0; set < a.n_sets; ++set) a.host_ctl[set].t_first = t_first;
         }
     }
+    if (int(blockIdx.x) < a.n_tile_blocks) RUNSTAMP(0, lane, wave);
     // blocks past the tile blocks serve the barrier / collect the residuals
     const int nb = a.n_tile_blocks;
     if (int(blockIdx.x) >= nb) {
@@ -1235,6 +1287,10 @@ int launch_bp_resident(const ResidentArgs& a, int grid_blocks, int lean_k, void*
 }  // namespace bnmi
 
 #ifdef BN_TILE_CLOCK
+extern "C" int bn_debug_run_clock_resident(unsigned long long* out, int n_waves) {
+    if (n_waves > bnmi::kTileClockTiles) n_waves = bnmi::kTileClockTiles;
+    return int(hipMemcpyFromSymbol(out, HIP_SYMBOL(bnmi::g_run_clock), sizeof(unsigned long long) * bnmi::kRunClockStamps * n_waves));
+}
 extern "C" int bn_debug_tile_clock_resident(unsigned long long* out, int n_tiles) {
     if (n_tiles > bnmi::kTileClockTiles) n_tiles = bnmi::kTileClockTiles;
     return int(hipMemcpyFromSymbol(out, HIP_SYMBOL(bnmi::g_tile_clock), sizeof(unsigned long long) * bnmi::kTileClockStamps * n_tiles));

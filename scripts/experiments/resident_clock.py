@@ -1,4 +1,5 @@
-# Phase stamps of one iteration (the sixth) of the resident kernel, every wave: needs the diagnostic library
+# Phase stamps of one iteration (the sixth) of the resident kernel and of the run's fixed cost (kernel entry, CPT image,
+# first sweep, last verdict, finalize), every wave: needs the diagnostic library
 #   (cd build/dbg_csrc && make EXTRA=-DBN_TILE_CLOCK OUT=../libbn_dbg.so)   and   BN_MI355X_LIB=build/libbn_dbg.so
 import ctypes
 import os
@@ -42,3 +43,20 @@ with Engine(g) as e:
     print(f"  {'iteration (start->published)':26s} {np.median(tot):8.0f} {np.percentile(tot, 90):8.0f} {tot.max():8.0f}")
     print("  spread of iteration starts over waves (ns):", (st[:, 0].max() - st[:, 0].min()) * 10, " of verdict arrival:", (st[:, 1].max() - st[:, 1].min()) * 10)
     print("  first start -> last publish (ns):", (st[:, 6].max() - t0) * 10)
+    # ---- the run's fixed cost: what is not sweeps (stamps of the LAST run above)
+    run = np.zeros((n, 8), dtype=np.uint64)
+    assert L.bn_debug_run_clock_resident(run.ctypes.data_as(ctypes.c_void_p), n) == 0
+    rs = run[run[:, 0] != 0].astype(np.int64)
+    e0 = rs[:, 0].min()
+    rows_ = [("entry -> CPT loads issued", rs[:, 1] - rs[:, 0]), ("entry -> CPT resident", rs[:, 2] - rs[:, 0]),
+             ("CPT resident -> sweep 0 published", rs[:, 3] - rs[:, 2]), ("entry -> sweep 0 published", rs[:, 3] - rs[:, 0]),
+             ("last verdict -> finalize stored", rs[:, 5] - rs[:, 4]), ("entry -> finalize stored", rs[:, 5] - rs[:, 0])]
+    print(f"run-level stamps, {rs.shape[0]} waves, ns: median / p90 / slowest wave")
+    for nm, v in rows_:
+        v = v * 10
+        print(f"  {nm:34s} {np.median(v):8.0f} {np.percentile(v, 90):8.0f} {v.max():8.0f}")
+    print("  spread of kernel entries over waves (ns):", (rs[:, 0].max() - e0) * 10)
+    print("  first entry -> last wave's CPT resident / sweep 0 published / last verdict / finalize stored (ns):",
+          (rs[:, 2].max() - e0) * 10, (rs[:, 3].max() - e0) * 10, (rs[:, 4].max() - e0) * 10, (rs[:, 5].max() - e0) * 10)
+    print("  sweeps 1.. : last sweep-0 publication -> last verdict (ns):", (rs[:, 4].max() - rs[:, 3].max()) * 10,
+          f" = {(rs[:, 4].max() - rs[:, 3].max()) * 10 / max(r['sweeps'] - 1, 1):.0f} per sweep")
