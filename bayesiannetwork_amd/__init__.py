@@ -8,7 +8,8 @@ from .flat import Evidence, FlatModel, from_parent_lists  # noqa: F401
 from . import synth  # noqa: F401
 
 _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters")
-_LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure")
+_LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure", "TermTable",
+             "SimulatedAnnealing")
 __all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING]
 
 

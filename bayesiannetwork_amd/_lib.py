@@ -35,6 +35,12 @@ class BpStats(ctypes.Structure):
                 ("sweep_devclock_ms", ctypes.c_float), ("resident_aborts", ctypes.c_int32)]
 
 
+class AnnealParams(ctypes.Structure):
+    _fields_ = [("initial_temp", ctypes.c_double), ("final_temp", ctypes.c_double), ("decreasing_rate", ctypes.c_double),
+                ("boltzmann", ctypes.c_double), ("same_state_max", ctypes.c_uint32), ("max_proposals", ctypes.c_uint32),
+                ("rule", ctypes.c_int32), ("trace_chain", ctypes.c_int32), ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
 class LayoutInfo(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_classes", ctypes.c_int32),
                 ("n_tiles", ctypes.c_int32), ("lanes_per_node_max", ctypes.c_int32),
@@ -133,6 +139,13 @@ SYMBOLS = [
     ("bn_learn_terms", ctypes.c_int, [ctypes.c_void_p, f64p, i64p]),
     ("bn_learn_brute_force_hint", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, ctypes.c_int32, i32p]),
     ("bn_learn_brute_force", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, f64p]),
+    ("bn_terms_create", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bn_terms_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, i64p]),
+    ("bn_terms_fetch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p]),
+    ("bn_terms_destroy", None, [ctypes.c_void_p]),
+    ("bn_learn_anneal", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(AnnealParams), ctypes.c_int32, ctypes.c_uint64, f64p,
+                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), i32p, ctypes.POINTER(ctypes.c_uint16),
+                                       ctypes.c_void_p, i32p]),
 ]
 
 

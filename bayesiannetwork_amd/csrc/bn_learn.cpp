@@ -5,12 +5,16 @@
 // graph per candidate.  The logarithm is the device's fp64 log: the learner's score is its own stated function of the counts.
 // bn_learn_score_subsets scores EVERY subset of a candidate parent set from one count of the top family (bn_learn_lattice.hip);
 // bn_learn_best_parents, bn_learn_brute_force_hint and bn_learn_brute_force are the reference's bayesian/learning/brute_force.hpp on it.
+// bn_term_table holds the family term of EVERY parent set of at most q nodes per child, made by one batch of run_groups;
+// bn_learn_anneal runs the reference's simulated_annealing.hpp as many device-resident chains over it (bn_learn_anneal.hip).
 #include <cmath>
+#include <limits>
 #include <memory>
 
 #include "bn_engine_internal.hpp"
 #include "bn_info_table.hpp"
 #include "bn_learn.hpp"
+#include "bn_learn_anneal.hpp"
 #include "../../include/bn_mi355x.h"
 
 namespace {
@@ -29,6 +33,8 @@ struct LearnTimes {
     int64_t count_bytes = 0;   // what the counting kernel has to read, from the shapes: per chunk P * (8 + base + 1 + candidates)
     double lattice_ns = 0.0;   // the subset lattice's kernel(s)
     int64_t subsets = 0;       // families made by the lattice (the top family included)
+    double anneal_ns = 0.0;    // the annealing kernel
+    int64_t anneal_chains = 0, anneal_steps = 0;
 };
 
 std::string gname(size_t g) { return "group " + std::to_string(g) + ": "; }
@@ -599,11 +605,14 @@ extern "C" int bn_learn_get(const bn_learner* L, const char* name, int64_t* out)
     else if (s == "count_bytes") *out = L->times.count_bytes;
     else if (s == "lattice_ns") *out = int64_t(L->times.lattice_ns);
     else if (s == "subsets_scored") *out = L->times.subsets;
+    else if (s == "anneal_ns") *out = int64_t(L->times.anneal_ns);
+    else if (s == "anneal_chains") *out = L->times.anneal_chains;
+    else if (s == "anneal_steps") *out = L->times.anneal_steps;
     else if (s == "edges") {
         *out = 0;
         for (const auto& p : L->parents) *out += int64_t(p.size());
     } else if (s == "parameters") *out = L->params;
-    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, edges, parameters)");
+    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, edges, parameters)");
     return BN_OK;
 }
 
@@ -950,5 +959,326 @@ extern "C" int bn_learn_brute_force(bn_learner* L, int32_t n_v, const int32_t* v
     if (n_v > 0) rec.run(0);
     w.commit();
     if (eval_out) *eval_out = best;
+    return BN_OK;
+}
+
+// ---- simulated annealing: the term table and the chains (reference bayesian/learning/simulated_annealing.hpp) ----------------------
+
+struct bn_term_table {
+    bn_info_table* t = nullptr;
+    int device = 0;
+    int32_t n = 0, q = 0;
+    int64_t T = 0;                       // entries per child
+    std::vector<uint32_t> tab;           // the rank tables (bn_learn_anneal.hpp)
+    DeviceBuf<double> d_terms;
+    DeviceBuf<uint32_t> d_tab;
+    DeviceBuf<int32_t> d_k;
+    int64_t ineligible = 0;
+    LearnTimes times;
+
+    // sorted parents, none of them c
+    int64_t rank(int32_t c, const int32_t* par, int32_t j) const {
+        int64_t r = tab[size_t(j)];
+        for (int32_t i = 0; i < j; ++i) r += tab[size_t(kAnnealTabBinom + (i + 1) * 64 + (par[i] - (par[i] > c ? 1 : 0)))];
+        return r;
+    }
+    ~bn_term_table() {
+        DeviceGuard g;
+        (void)g.enter(device);
+        d_terms.reset(); d_tab.reset(); d_k.reset();
+    }
+};
+
+extern "C" int bn_terms_create(bn_info_table* t, int32_t max_parents, bn_term_table** out) {
+    if (!out) return fail(BN_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!t) return fail(BN_ERR_ARG, "null argument");
+    if (max_parents < 1 || max_parents > kLearnMaxParents) return fail(BN_ERR_ARG, "term table: max_parents must be in 1..16");
+    const int32_t n = t->n, q = max_parents;
+    if (n > kAnnealMaxNodes)
+        return fail(BN_ERR_ARG, "term table: " + std::to_string(n) + " nodes (at most " + std::to_string(kAnnealMaxNodes) + ": a node has a lane)");
+    // C(a, i) for a <= 63, i <= 16 (C(63, 16) < 2^49)
+    std::vector<std::vector<uint64_t>> C(64, std::vector<uint64_t>(18, 0));
+    for (int a = 0; a < 64; ++a) {
+        C[size_t(a)][0] = 1;
+        for (int i = 1; i <= 17 && i <= a; ++i) C[size_t(a)][size_t(i)] = C[size_t(a - 1)][size_t(i - 1)] + (i <= a - 1 ? C[size_t(a - 1)][size_t(i)] : 0);
+    }
+    std::vector<int64_t> offset(size_t(q) + 2, 0);
+    for (int32_t j = 0; j <= q; ++j) {
+        offset[size_t(j) + 1] = offset[size_t(j)] + int64_t(n >= 1 ? C[size_t(n - 1)][size_t(j)] : 0);
+        if (offset[size_t(j) + 1] * n > kAnnealMaxEntries) {
+            // (the sum only grows: name the whole table's size, in 128-bit-free arithmetic -- every term is below 2^49 and q <= 16)
+            int64_t total = 0;
+            for (int32_t u = 0; u <= q; ++u) total += int64_t(C[size_t(n - 1)][size_t(u)]);
+            return fail(BN_ERR_ARG, "term table: " + std::to_string(n) + " nodes x " + std::to_string(total) + " parent sets of at most " +
+                                        std::to_string(q) + " = " + std::to_string(total * n) + " entries (at most 2^22 = " +
+                                        std::to_string(kAnnealMaxEntries) + ")");
+        }
+    }
+    std::unique_ptr<bn_term_table> tt(new (std::nothrow) bn_term_table);
+    if (!tt) return fail(BN_ERR_ALLOC, "host allocation failed");
+    tt->t = t;
+    tt->device = t->device;
+    tt->n = n;
+    tt->q = q;
+    tt->T = offset[size_t(q) + 1];
+    tt->tab.assign(size_t(kAnnealTabWords), 0u);
+    for (int32_t j = 0; j <= q; ++j) tt->tab[size_t(j)] = uint32_t(offset[size_t(j)]);
+    for (int32_t i = 0; i <= q; ++i)
+        for (int32_t a = 0; a + 1 < n; ++a) tt->tab[size_t(kAnnealTabBinom + i * 64 + a)] = uint32_t(C[size_t(a)][size_t(i)]);   // (<= C(n - 1, q) <= T)
+
+    // every family once: the groups (c, B, candidates above max(B)) for every B of fewer than q nodes; a family over the per-family
+    // limit is left out of the batch (its supersets too) and keeps its NaN
+    std::vector<int32_t> g_child, g_base_at, g_nbase, g_cand_at, g_ncand, base_store, cand_store;
+    std::vector<int32_t> B;
+    for (int32_t c = 0; c < n; ++c) {
+        const int64_t kc = t->k[size_t(c)];
+        B.clear();
+        // the subsets of the other nodes of size < q in lexicographic order, by a stack of node ids
+        for (;;) {
+            int64_t rows = 1;
+            for (int32_t u : B) rows *= t->k[size_t(u)];
+            const bool base_ok = rows * kc <= kLearnMaxEntries;
+            if (base_ok) {
+                const int32_t cand_at = int32_t(cand_store.size());
+                for (int32_t u = B.empty() ? 0 : B.back() + 1; u < n; ++u)
+                    if (u != c && rows * t->k[size_t(u)] * kc <= kLearnMaxEntries) cand_store.push_back(u);
+                const int32_t n_cand = int32_t(cand_store.size()) - cand_at;
+                if (B.empty() || n_cand > 0) {
+                    g_child.push_back(c);
+                    g_base_at.push_back(int32_t(base_store.size()));
+                    g_nbase.push_back(int32_t(B.size()));
+                    g_cand_at.push_back(cand_at);
+                    g_ncand.push_back(n_cand);
+                    base_store.insert(base_store.end(), B.begin(), B.end());
+                }
+            }
+            // next: extend by the smallest node above the last (when the base may still grow), else advance the last, else pop
+            auto next_above = [&](int32_t u) {
+                ++u;
+                if (u == c) ++u;
+                return u;
+            };
+            bool moved = false;
+            if (base_ok && int32_t(B.size()) + 1 < q) {
+                const int32_t u = next_above(B.empty() ? -1 : B.back());
+                if (u < n) {
+                    B.push_back(u);
+                    moved = true;
+                }
+            }
+            while (!moved && !B.empty()) {
+                const int32_t u = next_above(B.back());
+                if (u < n) {
+                    B.back() = u;
+                    moved = true;
+                } else {
+                    B.pop_back();
+                }
+            }
+            if (!moved) break;
+        }
+    }
+    std::vector<GroupIn> groups(g_child.size());
+    size_t n_fams = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        groups[g] = GroupIn{g_child[g], base_store.data() + g_base_at[g], g_nbase[g], cand_store.data() + g_cand_at[g], g_ncand[g]};
+        n_fams += size_t(1 + g_ncand[g]);
+    }
+    std::vector<double> ll(std::max<size_t>(n_fams, 1), 0.0);
+    if (int r = run_groups(t, groups, ll.data(), nullptr, &tt->times)) return r;
+    std::vector<double> terms(size_t(tt->T) * size_t(n), std::numeric_limits<double>::quiet_NaN());
+    {
+        size_t at = 0;
+        std::vector<int32_t> S;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const GroupIn& in = groups[g];
+            if (in.n_base == 0) terms[size_t(in.child) * size_t(tt->T)] = ll[at];
+            S.assign(in.base, in.base + in.n_base);
+            S.push_back(0);
+            for (int32_t j = 0; j < in.n_cand; ++j) {
+                S.back() = in.cand[j];   // (above every base parent)
+                terms[size_t(in.child) * size_t(tt->T) + size_t(tt->rank(in.child, S.data(), in.n_base + 1))] = ll[at + 1 + size_t(j)];
+            }
+            at += size_t(1 + in.n_cand);
+        }
+    }
+    for (double x : terms)
+        if (x != x) ++tt->ineligible;
+    ON_DEVICE(t);
+    int r;
+    if ((r = upload(tt->d_terms, terms, t->stream)) || (r = upload(tt->d_tab, tt->tab, t->stream)) || (r = upload(tt->d_k, t->k, t->stream))) return r;
+    HIPCHK(hipStreamSynchronize(t->stream));
+    *out = tt.release();
+    return BN_OK;
+}
+
+extern "C" void bn_terms_destroy(bn_term_table* tt) { delete tt; }
+
+extern "C" int bn_terms_get(const bn_term_table* tt, const char* name, int64_t* out) {
+    if (!tt || !name || !out) return fail(BN_ERR_ARG, "null argument");
+    const std::string s(name);
+    if (s == "entries") *out = tt->T * tt->n;
+    else if (s == "row_entries") *out = tt->T;
+    else if (s == "nodes") *out = tt->n;
+    else if (s == "max_parents") *out = tt->q;
+    else if (s == "ineligible") *out = tt->ineligible;
+    else if (s == "families_scored") *out = tt->times.families;
+    else if (s == "passes") *out = tt->times.passes;
+    else if (s == "build_ns") *out = int64_t(tt->times.count_ns + tt->times.score_ns);
+    else return fail(BN_ERR_ARG, "unknown name (entries, row_entries, nodes, max_parents, ineligible, families_scored, passes, build_ns)");
+    return BN_OK;
+}
+
+extern "C" int bn_terms_fetch(const bn_term_table* tt, int32_t child, double* ll_out) {
+    if (!tt || !ll_out) return fail(BN_ERR_ARG, "null argument");
+    if (child < 0 || child >= tt->n) return fail(BN_ERR_ARG, "child id " + std::to_string(child) + " out of range");
+    ON_DEVICE(tt);
+    HIPCHK(hipMemcpyAsync(ll_out, tt->d_terms.get() + size_t(child) * size_t(tt->T), size_t(tt->T) * 8, hipMemcpyDeviceToHost, tt->t->stream));
+    HIPCHK(hipStreamSynchronize(tt->t->stream));
+    return BN_OK;
+}
+
+static_assert(sizeof(bn_anneal_trace) == sizeof(AnnealTrace) && sizeof(AnnealTrace) == 16, "the trace record is the ABI's");
+static_assert(sizeof(AnnealRecord) == 32, "one record per chain");
+
+extern "C" int bn_learn_anneal(bn_learner* L, bn_term_table* tt, const bn_anneal_params* p, int32_t chains, uint64_t seed, double* eval_out,
+                               uint32_t* counts_out, uint64_t* masks_out, int32_t* n_edges_out, uint16_t* edges_out,
+                               bn_anneal_trace* trace_out, int32_t* winner_out) {
+    if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
+    if (tt->t != L->t) return fail(BN_ERR_ARG, "anneal: the term table was built from another table than the learner's");
+    auto positive = [](double x) { return std::isfinite(x) && x > 0.0; };
+    if (!positive(p->initial_temp) || !positive(p->final_temp)) return fail(BN_ERR_ARG, "anneal: the temperatures must be finite and positive");
+    if (!(p->decreasing_rate > 0.0 && p->decreasing_rate < 1.0)) return fail(BN_ERR_ARG, "anneal: decreasing_rate must be in (0, 1)");
+    if (!positive(p->boltzmann)) return fail(BN_ERR_ARG, "anneal: boltzmann must be finite and positive");
+    if (p->rule != 0 && p->rule != 1) return fail(BN_ERR_ARG, "anneal: rule 0 (the reference's) or 1 (Metropolis)");
+    if (chains < 1 || chains > kAnnealMaxChains) return fail(BN_ERR_ARG, "anneal: " + std::to_string(chains) + " chains (1 .. 65536)");
+    if (p->max_proposals > kAnnealMaxProposals)
+        return fail(BN_ERR_ARG, "anneal: max_proposals " + std::to_string(p->max_proposals) + " (at most 2^24 = " + std::to_string(kAnnealMaxProposals) + ")");
+    if (p->trace_chain < -1 || p->trace_chain >= chains) return fail(BN_ERR_ARG, "anneal: trace_chain out of range");
+    const bool tracing = p->trace_chain >= 0 && trace_out && p->trace_cap > 0;
+    const int32_t n = L->n, q = tt->q;
+    std::vector<uint64_t> pmask(size_t(n), 0);
+    std::vector<int64_t> rows(size_t(n), 1);
+    std::vector<uint16_t> edges;
+    for (int32_t v = 0; v < n; ++v) {
+        if (int32_t(L->parents[size_t(v)].size()) > q)
+            return fail(BN_ERR_ARG, "anneal: node " + std::to_string(v) + " starts with " + std::to_string(L->parents[size_t(v)].size()) +
+                                        " parents (the term table holds at most " + std::to_string(q) + ")");
+        for (int32_t u : L->parents[size_t(v)]) {
+            pmask[size_t(v)] |= uint64_t(1) << u;
+            edges.push_back(uint16_t(u | (v << 8)));
+        }
+        rows[size_t(v)] = L->rows_of(v);
+    }
+    const int32_t stride = std::max(n * q, 1);
+    bn_info_table* t = L->t;
+    ON_DEVICE(t);
+    hipStream_t s = t->stream;
+    DeviceBuf<uint64_t> d_pmask, d_masks;
+    DeviceBuf<int64_t> d_rows;
+    DeviceBuf<double> d_ll0, d_ll;
+    DeviceBuf<uint16_t> d_edges0, d_edges;
+    DeviceBuf<AnnealRecord> d_rec;
+    DeviceBuf<AnnealTrace> d_trace;
+    EventOwner ev0, ev1;
+    int r;
+    if ((r = upload(d_pmask, pmask, s)) || (r = upload(d_rows, rows, s)) || (r = upload(d_ll0, L->ll, s)) || (r = upload(d_edges0, edges, s)) ||
+        (r = dalloc(d_rec, size_t(chains))) || (r = dalloc(d_masks, size_t(chains) * size_t(n))) || (r = dalloc(d_ll, size_t(chains) * size_t(n))))
+        return r;
+    if (edges_out && (r = dalloc(d_edges, size_t(chains) * size_t(stride)))) return r;
+    if (tracing && (r = dalloc(d_trace, size_t(p->trace_cap)))) return r;
+    HIPCHK(hipEventCreate(ev0.put()));
+    HIPCHK(hipEventCreate(ev1.put()));
+    AnnealArgs a{};
+    a.terms = tt->d_terms;
+    a.tab = tt->d_tab;
+    a.T = tt->T;
+    a.k = tt->d_k;
+    a.pmask0 = d_pmask;
+    a.rows0 = d_rows;
+    a.ll0 = d_ll0;
+    a.edges0 = d_edges0;
+    a.n_edges0 = int32_t(edges.size());
+    a.n = n;
+    a.q = q;
+    a.max_parents = std::min(q, L->max_parents);
+    a.criterion = L->criterion;
+    a.rule = p->rule;
+    a.params0 = L->params;
+    a.penalty = L->penalty;
+    a.initial_temp = p->initial_temp;
+    a.final_temp = p->final_temp;
+    a.rate = p->decreasing_rate;
+    a.boltzmann = p->boltzmann;
+    a.same_state_max = p->same_state_max;
+    a.max_proposals = p->max_proposals == 0 ? (1u << 20) : p->max_proposals;
+    a.seed_lo = uint32_t(seed);
+    a.seed_hi = uint32_t(seed >> 32);
+    a.chains = chains;
+    a.trace_chain = tracing ? p->trace_chain : -1;
+    a.trace_cap = tracing ? p->trace_cap : 0;
+    a.rec = d_rec;
+    a.masks = d_masks;
+    a.ll = d_ll;
+    a.edges = edges_out ? d_edges.get() : nullptr;
+    a.edge_stride = stride;
+    a.trace = tracing ? d_trace.get() : nullptr;
+    HIPCHK(hipEventRecord(ev0, s));
+    if (int err = learn_launch_anneal(a, s)) return fail(BN_ERR_HIP, std::string("annealing kernel: ") + hipGetErrorString(hipError_t(err)));
+    HIPCHK(hipEventRecord(ev1, s));
+    std::vector<AnnealRecord> rec(static_cast<size_t>(chains));
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, size_t(chains) * sizeof(AnnealRecord), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int32_t winner = 0;
+    int64_t steps = 0;
+    for (int32_t j = 0; j < chains; ++j) {
+        if (rec[size_t(j)].eval < rec[size_t(winner)].eval) winner = j;   // strictly smaller: ties stay with the lowest index
+        steps += rec[size_t(j)].proposals;
+    }
+    std::vector<uint64_t> win_mask(static_cast<size_t>(n));
+    std::vector<double> win_ll(static_cast<size_t>(n));
+    HIPCHK(hipMemcpyAsync(win_mask.data(), d_masks.get() + size_t(winner) * size_t(n), size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(win_ll.data(), d_ll.get() + size_t(winner) * size_t(n), size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    if (masks_out) HIPCHK(hipMemcpyAsync(masks_out, d_masks, size_t(chains) * size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    if (edges_out) HIPCHK(hipMemcpyAsync(edges_out, d_edges, size_t(chains) * size_t(stride) * 2, hipMemcpyDeviceToHost, s));
+    if (tracing) {
+        const size_t len = std::min<size_t>(rec[size_t(p->trace_chain)].operated, p->trace_cap);
+        if (len > 0) HIPCHK(hipMemcpyAsync(trace_out, d_trace, len * sizeof(AnnealTrace), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    L->times.anneal_ns += double(ms) * 1e6;
+    L->times.anneal_chains += chains;
+    L->times.anneal_steps += steps;
+    for (int32_t j = 0; j < chains; ++j) {
+        const AnnealRecord& x = rec[size_t(j)];
+        if (eval_out) eval_out[j] = x.eval;
+        if (counts_out) {
+            counts_out[4 * j] = x.proposals;
+            counts_out[4 * j + 1] = x.operated;
+            counts_out[4 * j + 2] = x.accepted;
+            counts_out[4 * j + 3] = x.flags;
+        }
+        if (n_edges_out) n_edges_out[j] = int32_t(x.n_edges);
+    }
+    if (winner_out) *winner_out = winner;
+    // the winner's graph and terms become the learner's
+    for (int32_t v = 0; v < n; ++v) {
+        L->parents[size_t(v)].clear();
+        L->children[size_t(v)].clear();
+    }
+    L->params = 0;
+    for (int32_t v = 0; v < n; ++v) {
+        for (int32_t u = 0; u < n; ++u)
+            if ((win_mask[size_t(v)] >> u) & 1) {
+                L->parents[size_t(v)].push_back(u);
+                L->children[size_t(u)].push_back(v);
+            }
+        L->ll[size_t(v)] = win_ll[size_t(v)];
+        L->params += L->family_params(v, L->rows_of(v));
+    }
+    L->score = rec[size_t(winner)].eval;   // (= score_with(-1, 0.0, params): the kernel's evaluation is that function)
     return BN_OK;
 }

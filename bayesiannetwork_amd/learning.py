@@ -6,6 +6,9 @@ AIC and MDL are decomposable, so a candidate edge u -> c changes the family term
 terms and its score, and `Learner.try_parents` is the reference's inner loop for one child; `Greedy` and `K2` are the reference's
 functors on top of it.  `score_subsets` scores EVERY subset of a candidate parent set of one child from one pass over the table
 (the subset lattice); `Learner.best_parents`, `BruteForce` and `StepwiseStructure` are the exhaustive searches on top of that.
+`TermTable` holds the family term of every parent set of at most `max_parents` nodes per child on the device; `Learner.anneal` runs
+the reference's simulated annealing (simulated_annealing.hpp) as many independent device-resident chains over it, and
+`SimulatedAnnealing` is the reference's functor on top of that.
 The learner's score takes the DEVICE's fp64 logarithm (the header states the function); `AIC` / `MDL` of
 the learned model through evaluation.py agree with it to a few ulp per term, not bit for bit.
 
@@ -213,6 +216,41 @@ class Learner:
         _lib.check(_lib.lib().bn_learn_brute_force_hint(self._h, len(ps), _p(ps, ctypes.c_int32), len(cs), _p(cs, ctypes.c_int32)))
         return self.score()
 
+    def anneal(self, term_table: "TermTable", initial_temp: float, final_temp: float, decreasing_rate: float, boltzmann: float = 1.0,
+               same_state_max: int = 100, chains: int = 64, seed: int = 0, rule: str = "reference", max_proposals: int = 1 << 20,
+               trace_chain=None, trace_cap=None) -> dict:
+        """simulated_annealing::operator() as `chains` independent chains on the device, each from this learner's graph; the
+        chain with the strictly smallest final evaluation (the lowest index among equals) becomes this learner's graph.
+        rule: "reference" (accept uphill iff u < exp(-now / (boltzmann * T))) or "metropolis" (exp(-diff / ...)).  Returns the
+        per-chain records: eval [chains], proposals / operated / accepted / flags [chains] (END_* bits), masks [chains][n]
+        (bit u of masks[j][v]: u -> v), edges: per chain the ordered list of (from, to), winner, and with trace_chain the
+        structured array `trace` (TRACE_DTYPE) of that chain's operated proposals (the first trace_cap, default max_proposals)."""
+        if rule not in _RULES:
+            raise ValueError('rule: "reference" or "metropolis"')
+        chains = int(chains)
+        tracing = trace_chain is not None
+        cap = int(max_proposals if trace_cap is None else trace_cap) if tracing else 0
+        p = _lib.AnnealParams(float(initial_temp), float(final_temp), float(decreasing_rate), float(boltzmann), int(same_state_max),
+                              int(max_proposals), _RULES[rule], int(trace_chain) if tracing else -1, cap, 0)
+        c = max(chains, 1)
+        stride = max(self.n * term_table.max_parents, 1)
+        ev = np.zeros(c)
+        counts = np.zeros((c, 4), dtype=np.uint32)
+        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
+        n_edges = np.zeros(c, dtype=np.int32)
+        edges = np.zeros((c, stride), dtype=np.uint16)
+        trace = np.zeros(max(cap, 1), dtype=TRACE_DTYPE)
+        winner = ctypes.c_int32()
+        _lib.check(_lib.lib().bn_learn_anneal(self._h, term_table._h, ctypes.byref(p), chains, int(seed) & (2 ** 64 - 1), _p(ev, ctypes.c_double),
+                                              _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), _p(n_edges, ctypes.c_int32),
+                                              _p(edges, ctypes.c_uint16), trace.ctypes.data if tracing else None, ctypes.byref(winner)))
+        out = {"eval": ev, "proposals": counts[:, 0].copy(), "operated": counts[:, 1].copy(), "accepted": counts[:, 2].copy(),
+               "flags": counts[:, 3].copy(), "masks": masks[:, :self.n],
+               "edges": [[(int(e) & 255, int(e) >> 8) for e in edges[j, :n_edges[j]]] for j in range(chains)], "winner": winner.value}
+        if tracing:
+            out["trace"] = trace[:min(int(out["operated"][int(trace_chain)]), cap)].copy()
+        return out
+
     def score(self) -> float:
         out = ctypes.c_double()
         _lib.check(_lib.lib().bn_learn_score(self._h, ctypes.byref(out)))
@@ -233,6 +271,58 @@ class Learner:
     def parents(self):
         ptr, idx = self.structure()
         return [idx[ptr[v]:ptr[v + 1]].tolist() for v in range(self.n)]
+
+
+TRACE_DTYPE = np.dtype([("now_bits", np.uint64), ("method", np.uint8), ("from", np.uint8), ("to", np.uint8), ("accepted", np.uint8),
+                        ("pad", np.uint32)])
+END_TEMPERATURE, END_SAME_STATE, END_CAP = 1, 2, 4   # flags of a chain's record
+_RULES = {"reference": 0, "metropolis": 1}
+
+
+class TermTable:
+    """bn_term_table: ll(c, S) for every child c and every parent set S of at most `max_parents` nodes other than c, resident
+    on the device, each entry bit for bit what `score_groups` gives for that family (NaN: a family over 2^20 table entries, not
+    eligible).  At most 64 nodes and n * T(n, q) <= 2^22 entries.  `row(child)` fetches one child's T(n, q) entries, `rank(child,
+    parents)` is the index of a parent set in it.  Borrows `table`: close the term table first."""
+
+    def __init__(self, table: InfoTable, max_parents: int = 3):
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().bn_terms_create(table._h, int(max_parents), ctypes.byref(h)))
+        self._h = h
+        self.table, self.n, self.max_parents = table, table.n, int(max_parents)
+        self.row_entries = self.info("row_entries")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().bn_terms_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self, name: str) -> int:
+        out = ctypes.c_int64()
+        _lib.check(_lib.lib().bn_terms_get(self._h, name.encode(), ctypes.byref(out)))
+        return out.value
+
+    def row(self, child: int) -> np.ndarray:
+        out = np.zeros(self.row_entries)
+        _lib.check(_lib.lib().bn_terms_fetch(self._h, int(child), _p(out, ctypes.c_double)))
+        return out
+
+    def rank(self, child: int, parents) -> int:
+        """offset[j] + sum_i C(s'_i, i) over the parents relabelled s' = s - (s > child), in increasing order, i = 1 .. j."""
+        from math import comb
+        ps = sorted(int(u) for u in parents)
+        if len(ps) > self.max_parents or len(set(ps)) != len(ps) or any(u == child or not 0 <= u < self.n for u in ps):
+            raise ValueError("parents: distinct nodes other than the child, at most max_parents of them")
+        r = sum(comb(self.n - 1, t) for t in range(len(ps)))
+        return r + sum(comb(u - (u > child), i + 1) for i, u in enumerate(ps))
 
 
 def structure_model(k, in_ptr, in_idx, name: str = "") -> FlatModel:
@@ -435,3 +525,46 @@ class StepwiseStructure(_Search):
                 clusters.append(merged)
             self.last_plan = (done_clusters, done_pairs)
             return self._finish(model, L)
+
+
+class SimulatedAnnealing(_Search):
+    """bn::learning::simulated_annealing<Eval> (simulated_annealing.hpp).  `sa(model, initial_temp, final_temp, decreasing_rate,
+    boltzmann=1.0, same_state_max=100)`: `chains` independent chains from the model's graph, the best final graph returned as
+    (FlatModel with CPTs fitted to it, score).  max_parents (default 3) bounds the in-degree: the family terms of every parent
+    set up to it are computed once, into a TermTable kept for the object's lifetime, so a second call on the same samples pays
+    only for the chains.  rule: "reference" or "metropolis" (Learner.anneal).  Chain j of call number i uses the stream (seed +
+    i, j); without a seed one is drawn.  `last` also holds the anneal counters, the winning chain and the term table's."""
+
+    def __init__(self, criterion, sampling, max_parents: int = 3, chains: int = 64, rule: str = "reference", seed=None,
+                 max_proposals: int = 1 << 20, device: int = _lib.BN_DEVICE_CURRENT):
+        super().__init__(criterion, sampling, max_parents, seed, device)
+        self._chains, self._rule, self._max_proposals = int(chains), rule, int(max_proposals)
+        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
+        self._calls = 0
+        self._terms = None
+        self.records = None   # Learner.anneal's records of the last call
+
+    def close(self) -> None:
+        if getattr(self, "_terms", None) is not None:
+            self._terms.close()
+            self._terms = None
+
+    __del__ = close
+
+    def term_table(self, model) -> TermTable:
+        if self._terms is None:
+            self._terms = TermTable(self._ensure_table(model), self._max_parents)
+        return self._terms
+
+    def __call__(self, model, initial_temp: float, final_temp: float, decreasing_rate: float, boltzmann: float = 1.0,
+                 same_state_max: int = 100):
+        terms = self.term_table(model)
+        with self._learner(model) as L:
+            self.records = L.anneal(terms, initial_temp, final_temp, decreasing_rate, boltzmann, same_state_max, self._chains,
+                                    self._seed + self._calls, self._rule, self._max_proposals)
+            self._calls += 1
+            out = self._finish(model, L)
+            self.last.update({name: L.info(name) for name in ("anneal_ns", "anneal_chains", "anneal_steps")})
+            self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
+                              "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+            return out

@@ -117,6 +117,21 @@ public:
         return s;
     }
 
+    // simulated_annealing.hpp: the chains run on the learner over a term table of this session's table; the winner's graph
+    // REPLACES the edges of `graph` (annealing also erases and reverses edges).  Returns the winning chain.
+    std::int32_t anneal(graph_t& graph, std::int32_t max_parents, bn_anneal_params const& params, std::int32_t chains, std::uint64_t seed)
+    {
+        bn_term_table* terms = nullptr;
+        mi355x::engine_handle::check(bn_terms_create(table_.handle(), max_parents, &terms));
+        std::int32_t winner = 0;
+        int const rc = bn_learn_anneal(learner_, terms, &params, chains, seed, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &winner);
+        bn_terms_destroy(terms);
+        mi355x::engine_handle::check(rc);
+        graph.erase_all_edge();
+        apply_structure(graph);
+        return winner;
+    }
+
 private:
     std::vector<std::int32_t> indexes_of(std::vector<vertex_type> const& vs) const
     {

@@ -495,6 +495,72 @@ int bn_learn_terms(const bn_learner *L, double *ll_out, int64_t *params_out);
 int bn_learn_brute_force_hint(bn_learner *L, int32_t n_par, const int32_t *par, int32_t n_child, const int32_t *child);
 int bn_learn_brute_force(bn_learner *L, int32_t n_v, const int32_t *vertexes, double *eval_out);
 
+/* ---- simulated annealing as many device-resident chains over a table of family terms (reference
+ *      bayesian/learning/simulated_annealing.hpp:41-115). ----
+ *
+ *   bn_term_table holds, for every child c and every parent set S of at most q = max_parents nodes other than c, the family
+ *   term ll(c, S), resident on the device: bit for bit what bn_learn_score_groups gives for that family (it is built through it:
+ *   the groups (c, base B, candidates u > max(B)) for every B of fewer than q nodes, in one batch).  Index:
+ *     relabel the nodes other than c to 0 .. n - 2 by s' = s - (s > c);  for S = {s'_1 < ... < s'_j}
+ *     rank = offset[j] + sum over i = 1 .. j of C(s'_i, i),   offset[j] = sum over t < j of C(n - 1, t);
+ *     T(n, q) = offset[q + 1] entries per child, child c's row at c * T  (T(37, 3) = 7 807, T(64, 3) = 41 728).
+ *   A family over the per-family limit of 2^20 table entries holds a quiet NaN: "not eligible".  Limits (BN_ERR_ARG, the text names
+ *   the number): 1 <= max_parents <= 16; n <= 64 (the kernel gives a node a lane); n * T(n, q) <= 2^22 entries (32 MiB) -- a larger
+ *   table is refused, not trimmed.  bn_terms_fetch: ll_out [T], one child's row.  bn_terms_get names: "entries" (n * T), "row_entries"
+ *   (T), "nodes", "max_parents", "ineligible" (NaN entries), "families_scored", "passes", "build_ns" (device time of the counting and
+ *   scoring kernels).  The term table borrows the bn_info_table: destroy the term table first.
+ *
+ *   bn_learn_anneal runs `chains` independent chains (1 .. 2^16) from the learner's current graph, one wave per chain, lane v = node
+ *   v.  A chain's edge list starts child-major, parents increasing per child.  The loop, per iteration:
+ *     method = draw(3).  0: from = draw(n), to = draw(n); add_edge(from, to) is refused when from == to or `to` reaches `from`
+ *     (graph.hpp:270), when the edge exists (:284), and -- the library's limits, not the reference's -- when `to` has
+ *     min(q, the learner's max_parents) parents or the new family's term is NaN; otherwise the edge is appended to the list.
+ *     1, 2: with no edge the iteration ends here (`continue`: no draw, no cooling); else i = draw(edges) picks edge_list()[i],
+ *     which is erased in place; 2 then adds the opposite edge at the end of the list, and when that is refused adds the original
+ *     edge back AT THE END (graph.hpp:339-358): the list stays reordered and the proposal does not count as operated.
+ *     A proposal that was not operated neither cools nor counts towards same_state_max.  Otherwise now = the learner's score of
+ *     the proposed graph (the stated function above, node order, exact parameter count: the bits of bn_learn_score), diff = now -
+ *     current; accepted iff diff <= 0, else u = uniform() and accepted iff u < exp(-now / (boltzmann * T)) (rule 0, the
+ *     reference's :97: `now`, not `diff`, in the exponent) or u < exp(-diff / (boltzmann * T)) (rule 1, Metropolis); the multiply
+ *     and the divide are separate operations.  Rejected: the graph AND its edge list become those of the last accepted graph
+ *     (graph = best_graph, :109 -- this also undoes the reordering of refused reversals since then), same-state count + 1;
+ *     accepted: same-state count = 0.  T *= decreasing_rate.
+ *   The loop runs while T > final_temp && same-state count < same_state_max && iterations < max_proposals (0: 2^20; at most 2^24).
+ *   Random stream of chain j: xoshiro128++ seeded by Philox4x32-10(counter {j_lo, j_hi, 0, 0}, key {seed_lo, seed_hi}), an all-zero
+ *   block becoming {1, 0, 0, 0} (the sampler's stream_seed); one step per draw, 32-bit output r: draw(m) = (uint64(r) * m) >> 32,
+ *   uniform() = (r + 0.5) * 2^-32.  Draw order per iteration: method; from, to or the edge index; u only for an operated proposal
+ *   with diff > 0.  A chain depends on (seed, j) and the arguments only: not on `chains` or the launch shape.
+ *   Arguments (BN_ERR_ARG, nothing launched): temperatures finite and > 0, 0 < decreasing_rate < 1, boltzmann finite and > 0, rule
+ *   0 or 1, 1 <= chains <= 2^16, the term table built from the learner's table, no starting family over q parents.
+ *   Outputs (each may be NULL): eval_out [chains] final evaluations; counts_out [chains][4] iterations, operated, accepted, flags
+ *   (1: ended by temperature, 2: by same_state_max, 4: by max_proposals); masks_out [chains][n] final parent masks (bit u of word
+ *   v: u -> v); n_edges_out [chains] and edges_out [chains][n * q] the final ordered edge lists, from | to << 8; trace_out
+ *   [trace_cap] for chain trace_chain (-1: none), per operated proposal in order (the first trace_cap of them): the drawn edge
+ *   from -> to, the method, the bits of now, accepted; winner_out the winning chain: the STRICTLY smallest final evaluation, among
+ *   equal values the lowest index.  The learner's graph and terms are replaced by the winner's: bn_learn_score equals its
+ *   evaluation bit for bit, bn_learn_structure / bn_learn_terms work as usual.  Runs on the table's stream; no device-wide
+ *   synchronise.  bn_learn_get also names "anneal_ns" (device time of the kernel, summed), "anneal_chains", "anneal_steps"
+ *   (iterations of all chains). */
+typedef struct bn_term_table bn_term_table;
+typedef struct bn_anneal_params {
+    double initial_temp, final_temp, decreasing_rate, boltzmann;
+    uint32_t same_state_max, max_proposals;
+    int32_t rule, trace_chain;
+    uint32_t trace_cap, pad_;
+} bn_anneal_params;
+typedef struct bn_anneal_trace {
+    uint64_t now_bits;
+    uint8_t method, from, to, accepted;
+    uint32_t pad_;
+} bn_anneal_trace;
+int bn_terms_create(bn_info_table *table, int32_t max_parents, bn_term_table **out);
+int bn_terms_get(const bn_term_table *terms, const char *name, int64_t *out);
+int bn_terms_fetch(const bn_term_table *terms, int32_t child, double *ll_out);
+void bn_terms_destroy(bn_term_table *terms);
+int bn_learn_anneal(bn_learner *L, bn_term_table *terms, const bn_anneal_params *params, int32_t chains, uint64_t seed,
+                    double *eval_out, uint32_t *counts_out, uint64_t *masks_out, int32_t *n_edges_out, uint16_t *edges_out,
+                    bn_anneal_trace *trace_out, int32_t *winner_out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
