@@ -41,6 +41,11 @@ class AnnealParams(ctypes.Structure):
                 ("rule", ctypes.c_int32), ("trace_chain", ctypes.c_int32), ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
 
 
+class HcParams(ctypes.Structure):
+    _fields_ = [("alpha", ctypes.c_double), ("max_parents", ctypes.c_int32), ("trace_run", ctypes.c_int32),
+                ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
 class LayoutInfo(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_classes", ctypes.c_int32),
                 ("n_tiles", ctypes.c_int32), ("lanes_per_node_max", ctypes.c_int32),
@@ -146,6 +151,8 @@ SYMBOLS = [
     ("bn_learn_anneal", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(AnnealParams), ctypes.c_int32, ctypes.c_uint64, f64p,
                                        ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), i32p, ctypes.POINTER(ctypes.c_uint16),
                                        ctypes.c_void_p, i32p]),
+    ("bn_learn_hc", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HcParams), ctypes.c_int32, ctypes.c_uint64, f64p, f64p,
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p, i32p]),
 ]
 
 

@@ -134,8 +134,10 @@ namespace {
 
 // The all-pairs kernel over the columns `vars` of arity <= 32, the dense route for every pair with a wider
 // column.  hxy [m][m] and h [m] on the host; dump_off / dump: the pair blocks pair_counts asks for.
+// d_mi (device, may be null): [m][m] mi = h[x] + h[y] - hxy[x][y], made on the device from the kernel's own h and hxy; the rows and
+// columns of a wide column, whose entropies are finished on the host, are written from there.
 int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, double* hxy, const std::vector<int64_t>* dump_off,
-              unsigned long long* dump_host, size_t dump_len) {
+              unsigned long long* dump_host, size_t dump_len, double* d_mi = nullptr) {
     // slots: widths 32, 16, 8, 4, 2 in that order (stable in the caller's order), so each starts aligned
     std::vector<int32_t> order;
     std::vector<int32_t> wide;
@@ -189,6 +191,9 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
         if (int e = info_launch_pairs(a, flush, t->stream))
             return fail(BN_ERR_HIP, std::string("all-pairs kernel: ") + hipGetErrorString(hipError_t(e)));
         HIPCHK(hipEventRecord(ev1, t->stream));
+        if (d_mi)
+            if (int e = info_launch_mi(d_h, d_hxy, m, d_mi, t->stream))
+                return fail(BN_ERR_HIP, std::string("mutual-information kernel: ") + hipGetErrorString(hipError_t(e)));
         HIPCHK(hipMemcpyAsync(hxy, d_hxy, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
         std::vector<double> hs(static_cast<size_t>(m));
         HIPCHK(hipMemcpyAsync(hs.data(), d_h, size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
@@ -226,10 +231,35 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
                     if (o2 >= 0 && x != y) dump_host[o2 + j * kx + i] = v;
                 }
         }
+    if (d_mi && !wide.empty()) {
+        std::vector<double> rows(wide.size() * size_t(m));
+        for (size_t w = 0; w < wide.size(); ++w) {
+            const int32_t x = wide[w];
+            double* row = rows.data() + w * size_t(m);
+            for (int32_t y = 0; y < m; ++y) row[y] = h[x] + h[y] - hxy[size_t(x) * m + y];   // (= h[y] + h[x] - hxy[y][x]: the column too)
+            HIPCHK(hipMemcpyAsync(d_mi + size_t(x) * m, row, size_t(m) * 8, hipMemcpyHostToDevice, t->stream));
+            HIPCHK(hipMemcpy2DAsync(d_mi + x, size_t(m) * 8, row, 8, 8, size_t(m), hipMemcpyHostToDevice, t->stream));
+        }
+        HIPCHK(hipStreamSynchronize(t->stream));
+    }
     return BN_OK;
 }
 
 }  // namespace
+
+// every column's mutual information with every other, left on the device at d_mi [n][n]; mi_host: the same matrix from the
+// entropies the call brings to the host anyway (the same bits).  The caller has entered the table's device.
+int info_pair_mi_device(bn_info_table* t, double* d_mi, std::vector<double>& mi_host) {
+    const int32_t n = t->n;
+    std::vector<int32_t> all(static_cast<size_t>(n));
+    for (int32_t v = 0; v < n; ++v) all[size_t(v)] = v;
+    std::vector<double> h(static_cast<size_t>(n)), hxy(size_t(n) * size_t(n));
+    if (int r = all_pairs(t, n, all.data(), h.data(), hxy.data(), nullptr, nullptr, 0, d_mi)) return r;
+    mi_host.resize(hxy.size());
+    for (int32_t x = 0; x < n; ++x)
+        for (int32_t y = 0; y < n; ++y) mi_host[size_t(x) * n + y] = h[size_t(x)] + h[size_t(y)] - hxy[size_t(x) * n + y];
+    return BN_OK;
+}
 
 extern "C" int bn_info_pair_entropies(bn_info_table* t, int32_t m, const int32_t* vars, double* h_out, double* hxy_out, double* mi_out) {
     if (!t || !h_out || !hxy_out) return fail(BN_ERR_ARG, "null argument");

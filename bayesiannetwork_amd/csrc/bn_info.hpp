@@ -60,5 +60,8 @@ int info_launch_digits(const unsigned long long* w, int64_t P, int64_t Ppad, int
 int info_entropy_run(const InfoDev& t, const InfoSet& s, int route, uint64_t ncells, int key_bits, double Nd,
                      double* h_out, unsigned long long* cells_out, void* stream);
 int info_launch_pairs(const PairArgs& a, bool flush, void* stream);
+// mi[x][y] = h[x] + h[y] - hxy[x][y] over [m][m] on the device (transinformation.hpp:60): the arithmetic bn_info_pair_entropies
+// does on the host, so the same bits
+int info_launch_mi(const double* h, const double* hxy, int32_t m, double* mi, void* stream);
 
 }  // namespace bnmi

@@ -340,6 +340,19 @@ int info_entropy_run(const InfoDev& t, const InfoSet& s, int route, uint64_t nce
     return int(e);
 }
 
+__global__ void info_mi_kernel(const double* __restrict__ h, const double* __restrict__ hxy, int32_t m, double* __restrict__ mi) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= int64_t(m) * m) return;
+    const int32_t x = int32_t(i / m), y = int32_t(i % m);
+    mi[i] = h[x] + h[y] - hxy[i];
+}
+
+int info_launch_mi(const double* h, const double* hxy, int32_t m, double* mi, void* stream) {
+    const int64_t cells = int64_t(m) * m;
+    hipLaunchKernelGGL(info_mi_kernel, dim3(unsigned((cells + 255) / 256)), dim3(256), 0, hipStream_t(stream), h, hxy, m, mi);
+    return int(hipGetLastError());
+}
+
 int info_launch_pairs(const PairArgs& a, bool flush, void* stream) {
     const unsigned blocks = unsigned(int64_t(a.ntile) * (a.ntile + 1) / 2);
     if (flush)

@@ -28,3 +28,6 @@ struct bn_info_table {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// bn_info.cpp: the all-pairs mutual information of every column, left on the device (bn_learn_hc's similarity matrix)
+int info_pair_mi_device(bn_info_table* t, double* d_mi, std::vector<double>& mi_host);

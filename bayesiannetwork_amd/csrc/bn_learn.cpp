@@ -8,6 +8,7 @@
 // bn_term_table holds the family term of EVERY parent set of at most q nodes per child, made by one batch of run_groups;
 // bn_learn_anneal runs the reference's simulated_annealing.hpp as many device-resident chains over it (bn_learn_anneal.hip).
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <memory>
 
@@ -15,6 +16,7 @@
 #include "bn_info_table.hpp"
 #include "bn_learn.hpp"
 #include "bn_learn_anneal.hpp"
+#include "bn_learn_hc.hpp"
 #include "../../include/bn_mi355x.h"
 
 namespace {
@@ -35,6 +37,8 @@ struct LearnTimes {
     int64_t subsets = 0;       // families made by the lattice (the top family included)
     double anneal_ns = 0.0;    // the annealing kernel
     int64_t anneal_chains = 0, anneal_steps = 0;
+    double hc_ns = 0.0;        // the hierarchical-clustering kernel
+    int64_t hc_runs = 0, hc_merges = 0;
 };
 
 std::string gname(size_t g) { return "group " + std::to_string(g) + ": "; }
@@ -608,11 +612,14 @@ extern "C" int bn_learn_get(const bn_learner* L, const char* name, int64_t* out)
     else if (s == "anneal_ns") *out = int64_t(L->times.anneal_ns);
     else if (s == "anneal_chains") *out = L->times.anneal_chains;
     else if (s == "anneal_steps") *out = L->times.anneal_steps;
+    else if (s == "hc_ns") *out = int64_t(L->times.hc_ns);
+    else if (s == "hc_runs") *out = L->times.hc_runs;
+    else if (s == "hc_merges") *out = L->times.hc_merges;
     else if (s == "edges") {
         *out = 0;
         for (const auto& p : L->parents) *out += int64_t(p.size());
     } else if (s == "parameters") *out = L->params;
-    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, edges, parameters)");
+    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, hc_ns, hc_runs, hc_merges, edges, parameters)");
     return BN_OK;
 }
 
@@ -1139,6 +1146,26 @@ extern "C" int bn_terms_fetch(const bn_term_table* tt, int32_t child, double* ll
     return BN_OK;
 }
 
+// the winner's graph and terms become the learner's (score = score_with(-1, 0.0, params): the kernels' evaluation is that function)
+static void adopt_winner(bn_learner* L, const std::vector<uint64_t>& win_mask, const std::vector<double>& win_ll, double score) {
+    const int32_t n = L->n;
+    for (int32_t v = 0; v < n; ++v) {
+        L->parents[size_t(v)].clear();
+        L->children[size_t(v)].clear();
+    }
+    L->params = 0;
+    for (int32_t v = 0; v < n; ++v) {
+        for (int32_t u = 0; u < n; ++u)
+            if ((win_mask[size_t(v)] >> u) & 1) {
+                L->parents[size_t(v)].push_back(u);
+                L->children[size_t(u)].push_back(v);
+            }
+        L->ll[size_t(v)] = win_ll[size_t(v)];
+        L->params += L->family_params(v, L->rows_of(v));
+    }
+    L->score = score;
+}
+
 static_assert(sizeof(bn_anneal_trace) == sizeof(AnnealTrace) && sizeof(AnnealTrace) == 16, "the trace record is the ABI's");
 static_assert(sizeof(AnnealRecord) == 32, "one record per chain");
 
@@ -1264,21 +1291,126 @@ extern "C" int bn_learn_anneal(bn_learner* L, bn_term_table* tt, const bn_anneal
         if (n_edges_out) n_edges_out[j] = int32_t(x.n_edges);
     }
     if (winner_out) *winner_out = winner;
-    // the winner's graph and terms become the learner's
-    for (int32_t v = 0; v < n; ++v) {
-        L->parents[size_t(v)].clear();
-        L->children[size_t(v)].clear();
+    adopt_winner(L, win_mask, win_ll, rec[size_t(winner)].eval);
+    return BN_OK;
+}
+
+// ---- hierarchical clustering with stochastic pruning (reference bayesian/learning/stepwise_structure_hc.hpp) ------------------------
+
+static_assert(sizeof(bn_hc_trace) == sizeof(HcTrace) && sizeof(HcTrace) == 16, "the trace record is the ABI's");
+static_assert(sizeof(HcRecord) == 40, "one record per run");
+
+extern "C" int bn_learn_hc(bn_learner* L, bn_term_table* tt, const bn_hc_params* p, int32_t runs, uint64_t seed, const double* similarity,
+                           double* score_out, uint32_t* counts_out, uint64_t* masks_out, bn_hc_trace* trace_out, int32_t* n_trace_out,
+                           int32_t* winner_out) {
+    if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
+    if (tt->t != L->t) return fail(BN_ERR_ARG, "hc: the term table was built from another table than the learner's");
+    const int32_t n = L->n, q = tt->q;
+    if (n > kAnnealMaxNodes) return fail(BN_ERR_ARG, "hc: " + std::to_string(n) + " nodes (at most 64: a node has a lane)");
+    if (runs < 1 || runs > kHcMaxRuns) return fail(BN_ERR_ARG, "hc: " + std::to_string(runs) + " runs (1 .. 65536)");
+    if (!(std::isfinite(p->alpha) && p->alpha >= 0.0)) return fail(BN_ERR_ARG, "hc: alpha must be finite and >= 0");
+    if (p->max_parents < 1 || p->max_parents > q)
+        return fail(BN_ERR_ARG, "hc: max_parents " + std::to_string(p->max_parents) + " (1 .. " + std::to_string(q) + ", the term table's bound)");
+    if (p->trace_run < -1 || p->trace_run >= runs) return fail(BN_ERR_ARG, "hc: trace_run out of range");
+    const bool tracing = p->trace_run >= 0 && trace_out && p->trace_cap > 0;
+    bn_info_table* t = L->t;
+    std::vector<double> S(size_t(n) * size_t(n), 0.0);
+    if (similarity) {
+        for (int32_t x = 0; x < n; ++x)
+            for (int32_t y = x + 1; y < n; ++y)
+                if (std::memcmp(similarity + size_t(x) * n + y, similarity + size_t(y) * n + x, 8) != 0)
+                    return fail(BN_ERR_ARG, "hc: similarity[" + std::to_string(x) + "][" + std::to_string(y) + "] and [" + std::to_string(y) +
+                                                "][" + std::to_string(x) + "] differ in bits (the matrix must be symmetric)");
+        std::copy(similarity, similarity + S.size(), S.begin());
     }
-    L->params = 0;
-    for (int32_t v = 0; v < n; ++v) {
-        for (int32_t u = 0; u < n; ++u)
-            if ((win_mask[size_t(v)] >> u) & 1) {
-                L->parents[size_t(v)].push_back(u);
-                L->children[size_t(u)].push_back(v);
-            }
-        L->ll[size_t(v)] = win_ll[size_t(v)];
-        L->params += L->family_params(v, L->rows_of(v));
+    int64_t params0 = 0;
+    for (int32_t v = 0; v < n; ++v) params0 += L->family_params(v, 1);
+    ON_DEVICE(t);
+    hipStream_t s = t->stream;
+    DeviceBuf<double> d_S, d_ll;
+    DeviceBuf<uint64_t> d_masks;
+    DeviceBuf<HcRecord> d_rec;
+    DeviceBuf<HcTrace> d_trace;
+    EventOwner ev0, ev1;
+    int r;
+    if (similarity) {
+        if ((r = upload(d_S, S, s))) return r;
+    } else {
+        // the all-pairs mutual information stays where the kernel made it; the host sees it only for `average`
+        if ((r = dalloc(d_S, S.size())) || (r = info_pair_mi_device(t, d_S, S))) return r;
     }
-    L->score = rec[size_t(winner)].eval;   // (= score_with(-1, 0.0, params): the kernel's evaluation is that function)
+    // :171-186: the average of the initial similarities, one divide and one add per pair in row-major order
+    double average = 0.0;
+    const double pairs = double(int64_t(n) * (n - 1) / 2);
+    for (int32_t x = 0; x < n; ++x)
+        for (int32_t y = x + 1; y < n; ++y) average += (0.0 + S[size_t(x) * n + y] / 1.0) / pairs;
+    if ((r = dalloc(d_rec, size_t(runs))) || (r = dalloc(d_masks, size_t(runs) * size_t(n))) || (r = dalloc(d_ll, size_t(runs) * size_t(n))))
+        return r;
+    if (tracing && (r = dalloc(d_trace, size_t(p->trace_cap)))) return r;
+    HIPCHK(hipEventCreate(ev0.put()));
+    HIPCHK(hipEventCreate(ev1.put()));
+    HcArgs a{};
+    a.terms = tt->d_terms;
+    a.tab = tt->d_tab;
+    a.T = tt->T;
+    a.k = tt->d_k;
+    a.S = d_S;
+    a.n = n;
+    a.q = q;
+    a.max_parents = std::min(p->max_parents, L->max_parents);
+    a.criterion = L->criterion;
+    a.params0 = params0;
+    a.penalty = L->penalty;
+    a.alpha = p->alpha;
+    a.average = average;
+    a.seed_lo = uint32_t(seed);
+    a.seed_hi = uint32_t(seed >> 32);
+    a.runs = runs;
+    a.trace_run = tracing ? p->trace_run : -1;
+    a.trace_cap = tracing ? p->trace_cap : 0;
+    a.rec = d_rec;
+    a.masks = d_masks;
+    a.ll = d_ll;
+    a.trace = tracing ? d_trace.get() : nullptr;
+    HIPCHK(hipEventRecord(ev0, s));
+    if (int err = learn_launch_hc(a, s)) return fail(BN_ERR_HIP, std::string("hierarchical-clustering kernel: ") + hipGetErrorString(hipError_t(err)));
+    HIPCHK(hipEventRecord(ev1, s));
+    std::vector<HcRecord> rec(static_cast<size_t>(runs));
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, size_t(runs) * sizeof(HcRecord), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int32_t winner = 0;
+    int64_t merges = 0;
+    for (int32_t j = 0; j < runs; ++j) {
+        if (rec[size_t(j)].score < rec[size_t(winner)].score) winner = j;   // strictly smaller: ties stay with the lowest run
+        merges += rec[size_t(j)].merges;
+    }
+    std::vector<uint64_t> win_mask(static_cast<size_t>(n));
+    std::vector<double> win_ll(static_cast<size_t>(n));
+    HIPCHK(hipMemcpyAsync(win_mask.data(), d_masks.get() + size_t(winner) * size_t(n), size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(win_ll.data(), d_ll.get() + size_t(winner) * size_t(n), size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    if (masks_out) HIPCHK(hipMemcpyAsync(masks_out, d_masks, size_t(runs) * size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    size_t n_trace = 0;
+    if (tracing) {
+        const HcRecord& x = rec[size_t(p->trace_run)];
+        n_trace = std::min<size_t>(size_t(x.merges) + x.visits, p->trace_cap);
+        if (n_trace > 0) HIPCHK(hipMemcpyAsync(trace_out, d_trace, n_trace * sizeof(HcTrace), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    L->times.hc_ns += double(ms) * 1e6;
+    L->times.hc_runs += runs;
+    L->times.hc_merges += merges;
+    for (int32_t j = 0; j < runs; ++j) {
+        const HcRecord& x = rec[size_t(j)];
+        if (score_out) score_out[j] = x.score;
+        if (counts_out) {
+            uint32_t* c = counts_out + 6 * size_t(j);
+            c[0] = x.merges; c[1] = x.tried; c[2] = x.kept; c[3] = x.pruned; c[4] = x.pairs_kept; c[5] = x.flags;
+        }
+    }
+    if (n_trace_out) *n_trace_out = int32_t(n_trace);
+    if (winner_out) *winner_out = winner;
+    adopt_winner(L, win_mask, win_ll, rec[size_t(winner)].score);
     return BN_OK;
 }

@@ -8,7 +8,9 @@ functors on top of it.  `score_subsets` scores EVERY subset of a candidate paren
 (the subset lattice); `Learner.best_parents`, `BruteForce` and `StepwiseStructure` are the exhaustive searches on top of that.
 `TermTable` holds the family term of every parent set of at most `max_parents` nodes per child on the device; `Learner.anneal` runs
 the reference's simulated annealing (simulated_annealing.hpp) as many independent device-resident chains over it, and
-`SimulatedAnnealing` is the reference's functor on top of that.
+`SimulatedAnnealing` is the reference's functor on top of that.  `Learner.hc` runs the reference's hierarchical clustering with
+stochastic pruning (stepwise_structure_hc.hpp) as many device-resident runs over the same table and the all-pairs mutual
+information; `StepwiseStructureHC` is its functor.
 The learner's score takes the DEVICE's fp64 logarithm (the header states the function); `AIC` / `MDL` of
 the learned model through evaluation.py agree with it to a few ulp per term, not bit for bit.
 
@@ -251,6 +253,45 @@ class Learner:
             out["trace"] = trace[:min(int(out["operated"][int(trace_chain)]), cap)].copy()
         return out
 
+    def hc(self, term_table: "TermTable", alpha: float, runs: int = 64, seed: int = 0, max_parents=None, similarity=None,
+           trace_run=None, trace_cap: int = 2048) -> dict:
+        """stepwise_structure_hc::operator() as `runs` independent runs on the device, each from the empty graph (the algorithm
+        clears the edges); the run with the strictly smallest final score (the lowest among equals) becomes this learner's graph.
+        similarity: None (the table's all-pairs mutual information) or an [n][n] matrix, symmetric in bits.  max_parents: the
+        in-degree a run refuses at (default and at most the term table's).  Returns the per-run records: score [runs], merges /
+        tried / kept / pruned / pairs_kept / flags [runs] (HC_* bits), masks [runs][n] (bit u of masks[j][v]: u -> v), winner, and
+        with trace_run the structured arrays `merge_trace` (parent, child, value_bits, coin) and `prune_trace` (cluster,
+        connections, value_bits, pruned) of that run."""
+        runs = int(runs)
+        tracing = trace_run is not None
+        cap = int(trace_cap) if tracing else 0
+        p = _lib.HcParams(float(alpha), int(term_table.max_parents if max_parents is None else max_parents),
+                          int(trace_run) if tracing else -1, cap, 0)
+        c = max(runs, 1)
+        S = None
+        if similarity is not None:
+            S = np.ascontiguousarray(similarity, dtype=np.float64)
+            if S.shape != (self.n, self.n):
+                raise ValueError(f"similarity: an [{self.n}][{self.n}] matrix")
+        score = np.zeros(c)
+        counts = np.zeros((c, 6), dtype=np.uint32)
+        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
+        trace = np.zeros(max(cap, 1), dtype=HC_TRACE_DTYPE)
+        n_trace, winner = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.lib().bn_learn_hc(self._h, term_table._h, ctypes.byref(p), runs, int(seed) & (2 ** 64 - 1),
+                                          _p(S, ctypes.c_double) if S is not None else None, _p(score, ctypes.c_double),
+                                          _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), trace.ctypes.data if tracing else None,
+                                          ctypes.byref(n_trace), ctypes.byref(winner)))
+        out = {name: counts[:, i].copy() for i, name in enumerate(("merges", "tried", "kept", "pruned", "pairs_kept", "flags"))}
+        out.update({"score": score, "masks": masks[:, :self.n], "winner": winner.value})
+        if tracing:
+            tr = trace[:n_trace.value]
+            merge, visit = tr[tr["kind"] == 0], tr[tr["kind"] == 1]
+            out["merge_trace"] = np.rec.fromarrays([merge["a"], merge["b"], merge["value_bits"], merge["c"]], names="parent,child,value_bits,coin")
+            out["prune_trace"] = np.rec.fromarrays([visit["a"], visit["b"], visit["value_bits"], visit["c"]],
+                                                   names="cluster,connections,value_bits,pruned")
+        return out
+
     def score(self) -> float:
         out = ctypes.c_double()
         _lib.check(_lib.lib().bn_learn_score(self._h, ctypes.byref(out)))
@@ -277,6 +318,8 @@ TRACE_DTYPE = np.dtype([("now_bits", np.uint64), ("method", np.uint8), ("from", 
                         ("pad", np.uint32)])
 END_TEMPERATURE, END_SAME_STATE, END_CAP = 1, 2, 4   # flags of a chain's record
 _RULES = {"reference": 0, "metropolis": 1}
+HC_TRACE_DTYPE = np.dtype([("value_bits", np.uint64), ("kind", np.uint8), ("a", np.uint8), ("b", np.uint8), ("c", np.uint8), ("pad", np.uint32)])
+HC_ONE_CLUSTER, HC_NO_SIMILARITY = 1, 2   # flags of a run's record
 
 
 class TermTable:
@@ -568,3 +611,153 @@ class SimulatedAnnealing(_Search):
             self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
                               "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
             return out
+
+
+class _Stream:
+    """The library's stream (run j of a seed): xoshiro128++ seeded by Philox4x32-10({j_lo, j_hi, 0, 0}, {seed_lo, seed_hi})."""
+
+    def __init__(self, seed: int, j: int):
+        M = 0xFFFFFFFF
+        c = [j & M, (j >> 32) & M, 0, 0]
+        k0, k1 = seed & M, (seed >> 32) & M
+        for _ in range(10):
+            p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+            c = [(p1 >> 32) ^ c[1] ^ k0, p1 & M, (p0 >> 32) ^ c[3] ^ k1, p0 & M]
+            k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+        self.x = c if any(c) else [1, 0, 0, 0]
+
+    def next(self) -> int:
+        M = 0xFFFFFFFF
+        x = self.x
+        s = (x[0] + x[3]) & M
+        result = ((((s << 7) | (s >> 25)) & M) + x[0]) & M
+        t = (x[1] << 9) & M
+        x[2] ^= x[0]
+        x[3] ^= x[1]
+        x[1] ^= x[2]
+        x[0] ^= x[3]
+        x[2] ^= t
+        x[3] = ((x[3] << 11) | (x[3] >> 21)) & M
+        return result
+
+    def below(self, m: int) -> int:
+        return (self.next() * m) >> 32
+
+    def uniform(self) -> float:
+        return (self.next() + 0.5) * 2.0 ** -32
+
+
+class StepwiseStructureHC(_Search):
+    """bn::learning::stepwise_structure_hc<Eval, BetweenLearning> (stepwise_structure_hc.hpp): nodes are clustered by mutual
+    information; the two most similar clusters are merged, edges from the one to the other learned with `learn_with_hint`, and the
+    merged cluster's pairs with the others pruned at random (`alpha`: 0 prunes nothing, 1 everything).  `hc(model, alpha)` returns
+    (FlatModel with CPTs fitted to the final structure, score); the model's edges are not read (the algorithm clears them).
+    between unset or Greedy: `runs` independent runs resident on the device (Learner.hc), the best final graph returned; run j of
+    call number i uses the stream (seed + i, j).  The term table (max_parents, default 3) is kept for the object's lifetime.
+    Any other `between` (BruteForce, or anything with `hint_on`, class or instance): the same loop on the host as ONE run, coin
+    and pruning draws from run 0's stream, `between.hint_on(L, parent_nodes, child_nodes)` per merge.  Clusters are ordered by id
+    where the reference orders them by address: node i's cluster is i, merge s makes n + s.  With nothing to merge the score is
+    the empty graph's (the reference returns DBL_MAX).  `last` also holds the hc counters, the winner and the term table's."""
+
+    def __init__(self, criterion, sampling, between=None, max_parents: int = 3, runs: int = 64, seed=None,
+                 device: int = _lib.BN_DEVICE_CURRENT):
+        super().__init__(criterion, sampling, max_parents, seed, device)
+        self._between = Greedy if between is None else between
+        self._runs = int(runs)
+        self._seeded = seed is not None
+        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
+        self._calls = 0
+        self._terms = None
+        self.records = None   # Learner.hc's records of the last call (device path)
+
+    def close(self) -> None:
+        if getattr(self, "_terms", None) is not None:
+            self._terms.close()
+            self._terms = None
+
+    __del__ = close
+
+    def term_table(self, model) -> TermTable:
+        if self._terms is None:
+            self._terms = TermTable(self._ensure_table(model), self._max_parents)
+        return self._terms
+
+    def _resident(self) -> bool:
+        return self._between is Greedy or isinstance(self._between, Greedy)
+
+    def __call__(self, model, alpha: float):
+        table = self._ensure_table(model)
+        seed = self._seed + self._calls
+        self._calls += 1
+        criterion = "aic" if self._criterion == 0 else "mdl"
+        with Learner(table, None, criterion, self._max_parents) as L:   # (:134: erase_all_edge)
+            if self._resident():
+                terms = self.term_table(model)
+                self.records = L.hc(terms, alpha, self._runs, seed)
+                out = self._finish(model, L)
+                self.last.update({name: L.info(name) for name in ("hc_ns", "hc_runs", "hc_merges")})
+                self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
+                                  "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+                return out
+            merges = self._host_run(L, table, float(alpha), seed)
+            out = self._finish(model, L)
+            self.last.update({"hc_runs": 1, "hc_merges": merges, "winner": 0})
+            return out
+
+    def _host_run(self, L: Learner, table: InfoTable, alpha: float, seed: int) -> int:
+        between = self._between
+        if isinstance(between, type):
+            between = between("aic" if self._criterion == 0 else "mdl", table, max_parents=self._max_parents,
+                              seed=int(self._rng.integers(1 << 32)) if self._seeded else None, device=self._device)
+        n = L.n
+        S = table.pair_entropies()["mi"]
+        rng = _Stream(seed, 0)
+        f = np.float64
+
+        def make_similarity(X, Y):   # (:240-259)
+            count, value = f(len(X) * len(Y)), f(0.0)
+            for l in X:
+                for r in Y:
+                    value = value + S[l][r] / count
+            return value
+
+        with np.errstate(all="ignore"):
+            nodes = {i: [i] for i in range(n)}
+            clusters = list(range(n))
+            sims = []
+            average = f(0.0)
+            for i in range(n):
+                for j in range(i + 1, n):
+                    value = make_similarity([i], [j])
+                    average = average + value / f(n * (n - 1) // 2)
+                    sims.append((i, j, value))
+            merges = 0
+            while len(clusters) != 1 and sims:   # (:267)
+                best = 0
+                for i in range(1, len(sims)):
+                    if sims[best][2] < sims[i][2]:
+                        best = i
+                a, b, old_value = sims.pop(best)
+                parent, child = (b, a) if rng.below(2) else (a, b)
+                between.hint_on(L, list(nodes[parent]), list(nodes[child]))
+                new = n + merges
+                merges += 1
+                nodes[new] = nodes[parent] + nodes[child]
+                clusters.remove(parent)
+                clusters.remove(child)
+                clusters.append(new)
+                dead = (parent, child)
+                for c in clusters[:-1]:   # (:299-348)
+                    connection = [s for s in sims if (s[0] == c and s[1] in dead) or (s[1] == c and s[0] in dead)]
+                    sims = [s for s in sims if not ((s[0] == c and s[1] in dead) or (s[1] == c and s[0] in dead))]
+                    new_value = make_similarity(nodes[new], nodes[c])
+                    if len(connection) == 2:
+                        p = np.power(f(alpha), new_value / average)
+                    elif len(connection) == 1:
+                        p = np.power(f(alpha), old_value / connection[0][2])
+                    else:
+                        continue
+                    if rng.uniform() < p:
+                        continue
+                    sims.append((c, new, new_value))
+        return merges

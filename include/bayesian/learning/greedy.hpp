@@ -132,6 +132,22 @@ public:
         return winner;
     }
 
+    // stepwise_structure_hc.hpp: the runs start from the empty graph over a term table of this session's table and the table's
+    // all-pairs mutual information; the winner's graph REPLACES the edges of `graph`.  Returns the winning run.
+    std::int32_t hc(graph_t& graph, std::int32_t max_parents, double alpha, std::int32_t runs, std::uint64_t seed)
+    {
+        bn_term_table* terms = nullptr;
+        mi355x::engine_handle::check(bn_terms_create(table_.handle(), max_parents, &terms));
+        bn_hc_params const params{alpha, max_parents, -1, 0, 0};
+        std::int32_t winner = 0;
+        int const rc = bn_learn_hc(learner_, terms, &params, runs, seed, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &winner);
+        bn_terms_destroy(terms);
+        mi355x::engine_handle::check(rc);
+        graph.erase_all_edge();
+        apply_structure(graph);
+        return winner;
+    }
+
 private:
     std::vector<std::int32_t> indexes_of(std::vector<vertex_type> const& vs) const
     {

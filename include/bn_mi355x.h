@@ -561,6 +561,71 @@ int bn_learn_anneal(bn_learner *L, bn_term_table *terms, const bn_anneal_params 
                     double *eval_out, uint32_t *counts_out, uint64_t *masks_out, int32_t *n_edges_out, uint16_t *edges_out,
                     bn_anneal_trace *trace_out, int32_t *winner_out);
 
+/* ---- hierarchical clustering with stochastic pruning as many device-resident runs (reference
+ *      bayesian/learning/stepwise_structure_hc.hpp:131-360 over greedy.hpp:67-101). ----
+ *
+ *   bn_learn_hc runs `runs` independent searches (1 .. 2^16), one wave per run, lane v = node v (n <= 64), over a bn_term_table
+ *   built on the learner's table and a similarity matrix S [n][n], and makes the best final graph the learner's.  The learner's
+ *   starting edges are ignored: the algorithm clears them (:134).
+ *   Difference from the reference: it orders clusters, and the two halves of a similarity, by shared_ptr address (:199, :257),
+ *   which depends on the allocator.  Here a cluster has an id: node i's initial cluster is i, the cluster made by merge number s
+ *   (from 0) is n + s (at most 2n - 2), and "smaller address" reads "smaller id".
+ *   State of a run: the graph; `clusters`, the ordered list of live ids, initially 0 .. n-1; per cluster its ordered node list (a
+ *   merged cluster holds the parent cluster's nodes, then the child cluster's, in their stored order); `sims`, the ordered list of
+ *   (a, b, value), a < b, initially every i < j in row-major order with value = make_similarity(i, j); average = 0.0, then +=
+ *   value / double(n (n - 1) / 2) in that order (:171-186).
+ *   make_similarity(X, Y) (:240-259): value = 0.0; for l in nodes(X) (outer), r in nodes(Y) (inner): value += S[l][r] /
+ *   double(|X| |Y|): one divide and one add per pair, no tree.
+ *   The loop, while more than one cluster is live and sims is not empty (:267):
+ *     pick: best = 0; for i >= 1: if value[best] < value[i]: best = i -- the FIRST maximum (:220-237); that entry (a, b, old_value)
+ *     leaves the list; coin = draw(2): (parent, child) = (b, a) when set, else (a, b).
+ *     learn_with_hint(nodes(parent), nodes(child)) (greedy.hpp:67-101): the copy of the child nodes is shuffled (for i = len-1 ..
+ *     1: j = draw(i + 1); swap(x[i], x[j])); eval_now = the learner's score; per child the copy of the parent nodes is shuffled
+ *     again (the shuffles accumulate within the call) and each parent visited in order: the edge parent -> child is refused when
+ *     the child has max_parents parents or the new family's term is NaN (the library's limits; the reference's own refusals, a
+ *     cycle or an existing edge, cannot occur: two clusters meet once and their edges run one way between disjoint node sets);
+ *     otherwise eval_next = the learner's score with the edge (the stated function, node order, exact parameter count: the bits
+ *     of bn_learn_score), and the edge is kept iff eval_next < eval_now.
+ *     merge (:204-217): parent and child leave `clusters` (ordered erase), the new id is appended.
+ *     prune (:299-360): for each c in `clusters` order, c != new: its connections, the entries of sims that join c with parent or
+ *     with child, leave the list (ordered erase); new_value = make_similarity(new, c); two connections: p = pow(alpha, new_value /
+ *     average); one: p = pow(alpha, old_value / that connection's value); none: next cluster, no draw.  u = uniform(); u < p: the
+ *     pair is pruned; otherwise (c, new, new_value) is appended to sims.  IEEE arithmetic as it falls: a zero average or
+ *     connection gives inf or NaN, and u < NaN keeps the pair.  (The reference's closing sweep, :351-359, never finds anything.)
+ *   A run's result is the learner's score of its final graph; with no merge (n == 1) that of the empty graph, where the
+ *   reference returns DBL_MAX.
+ *   Random stream of run j: as chain j of bn_learn_anneal.  Draw order per merge: the coin, the child shuffle, per child its parent
+ *   shuffle, then one uniform per surviving cluster that has a connection, in `clusters` order.  A run depends on (seed, j) and
+ *   the arguments only: not on `runs` or the launch shape.
+ *   similarity NULL: S is the `mi` matrix bn_info_pair_entropies gives for every column of the learner's table, bit for bit,
+ *   read as S[l][r]: made on the device from the all-pairs kernel's own entropies, on the table's stream, and left there (no
+ *   host round trip; only the pairs of a column of arity > 32, which that call finishes on the host, are written from it).  Non-NULL: the caller's [n][n] matrix; one whose [x][y]
+ *   and [y][x] differ in bits is refused; the diagonal is not read.
+ *   Arguments (BN_ERR_ARG, the text names the limit, nothing launched): n <= 64; 1 <= runs <= 2^16; alpha finite and >= 0; 1 <=
+ *   max_parents <= the term table's (a run refuses at min(max_parents, the learner's)); the term table built on the learner's
+ *   table; -1 <= trace_run < runs.
+ *   Outputs (each may be NULL): score_out [runs]; counts_out [runs][6]: merges, candidates that reached an evaluation, edges kept,
+ *   pairs pruned, pairs kept, flags (1: one cluster left, 2: sims empty; both may be set); masks_out [runs][n] final parent masks
+ *   (bit u of word v: u -> v); trace_out [trace_cap] for run trace_run, in the order things happen (the first trace_cap records;
+ *   a run makes at most 2 016), n_trace_out their number: kind 0, a merge: a = parent id, b = child id, c = coin, value_bits = the
+ *   bits of old_value; kind 1, a pruning visit: a = cluster id, b = connections, c = pruned, value_bits = the bits of new_value.
+ *   winner_out: the run with the STRICTLY smallest score, among equals the lowest.  The learner's graph and terms become the
+ *   winner's: bn_learn_score equals its score bit for bit, bn_learn_structure / bn_learn_terms work as after bn_learn_anneal.
+ *   bn_learn_get also names "hc_ns" (device time of the kernel, summed), "hc_runs", "hc_merges". */
+typedef struct bn_hc_params {
+    double alpha;
+    int32_t max_parents, trace_run;
+    uint32_t trace_cap, pad_;
+} bn_hc_params;
+typedef struct bn_hc_trace {
+    uint64_t value_bits;
+    uint8_t kind, a, b, c;
+    uint32_t pad_;
+} bn_hc_trace;
+int bn_learn_hc(bn_learner *L, bn_term_table *terms, const bn_hc_params *params, int32_t runs, uint64_t seed,
+                const double *similarity, double *score_out, uint32_t *counts_out, uint64_t *masks_out, bn_hc_trace *trace_out,
+                int32_t *n_trace_out, int32_t *winner_out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
