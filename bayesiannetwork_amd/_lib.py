@@ -46,6 +46,10 @@ class HcParams(ctypes.Structure):
                 ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
 
 
+class ScoreSpec(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("ess", ctypes.c_double)]
+
+
 class LayoutInfo(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_classes", ctypes.c_int32),
                 ("n_tiles", ctypes.c_int32), ("lanes_per_node_max", ctypes.c_int32),
@@ -153,6 +157,13 @@ SYMBOLS = [
                                        ctypes.c_void_p, i32p]),
     ("bn_learn_hc", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HcParams), ctypes.c_int32, ctypes.c_uint64, f64p, f64p,
                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p, i32p]),
+    ("bn_learn_score_groups_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, i32p, i32p, i32p, i32p, i32p,
+                                                  f64p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_learn_score_subsets_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, ctypes.c_int32, i32p,
+                                                   ctypes.c_int32, i32p, f64p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_learn_create_spec", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, ctypes.c_int32, ctypes.POINTER(ScoreSpec), ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    ("bn_terms_create_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
 ]
 
 

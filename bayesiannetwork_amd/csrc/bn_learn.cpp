@@ -43,6 +43,32 @@ struct LearnTimes {
 
 std::string gname(size_t g) { return "group " + std::to_string(g) + ": "; }
 
+// The family term: kind 0 the log-likelihood term (AIC / MDL), 2 BDeu, 3 K2.  Held normalised (ess 0.0 where the kind does not
+// read it), so two specs are the same function iff kind and the bits of ess agree.
+const bn_score_spec kLogLikSpec{0, 0, 0.0};
+
+int check_spec(const bn_score_spec* in, bn_score_spec& out) {
+    out = kLogLikSpec;
+    if (!in) return BN_OK;
+    if (in->kind != 0 && in->kind != 2 && in->kind != 3)
+        return fail(BN_ERR_ARG, "score spec: unknown kind " + std::to_string(in->kind) + " (0 log-likelihood term, 2 BDeu, 3 K2)");
+    out.kind = in->kind;
+    if (in->kind == 2) {
+        if (!(std::isfinite(in->ess) && in->ess >= 0x1p-20 && in->ess <= 0x1p20))
+            return fail(BN_ERR_ARG, "score spec: BDeu's ess must be finite and within [2^-20, 2^20]");
+        out.ess = in->ess;
+    }
+    return BN_OK;
+}
+
+bool same_spec(const bn_score_spec& x, const bn_score_spec& y) { return x.kind == y.kind && std::memcmp(&x.ess, &y.ess, 8) == 0; }
+
+const char* spec_name(const bn_score_spec& x) { return x.kind == 0 ? "the log-likelihood term (AIC / MDL)" : x.kind == 2 ? "BDeu" : "K2"; }
+
+int launch_score(const bn_score_spec& spec, const LearnArgs& a, int32_t fam0, int32_t n_fams, void* stream) {
+    return spec.kind == 0 ? learn_launch_score(a, fam0, n_fams, stream) : learn_launch_score_bd(a, fam0, n_fams, spec.kind, spec.ess, stream);
+}
+
 // the limits of one family: rows = product of the parents' arities
 int check_family(const bn_info_table* t, size_t g, int32_t child, int64_t rows, int32_t n_parents) {
     if (n_parents > kLearnMaxParents)
@@ -83,7 +109,8 @@ int check_group(const bn_info_table* t, size_t g, const GroupIn& in, int64_t& ba
 }
 
 // ll_out [families], group-major, base first; counts_out: null, or every family's counts back to back in the fitted layout
-int run_groups(bn_info_table* t, const std::vector<GroupIn>& groups, double* ll_out, uint64_t* counts_out, LearnTimes* times) {
+int run_groups(bn_info_table* t, const bn_score_spec& spec, const std::vector<GroupIn>& groups, double* ll_out, uint64_t* counts_out,
+               LearnTimes* times) {
     std::vector<LearnChunk> chunks;
     std::vector<LearnFamily> fams;
     std::vector<int32_t> par_id, par_k, cand_id, cand_k, cand_cell;
@@ -225,7 +252,7 @@ int run_groups(bn_info_table* t, const std::vector<GroupIn>& groups, double* ll_
         if (int err = learn_launch_count(a, p.chunk0, n_chunks, splits, s))
             return fail(BN_ERR_HIP, std::string("family-group count kernel: ") + hipGetErrorString(hipError_t(err)));
         HIPCHK(hipEventRecord(ev1, s));
-        if (int err = learn_launch_score(a, int32_t(fam_at), int32_t(fam_end - fam_at), s))
+        if (int err = launch_score(spec, a, int32_t(fam_at), int32_t(fam_end - fam_at), s))
             return fail(BN_ERR_HIP, std::string("family score kernel: ") + hipGetErrorString(hipError_t(err)));
         HIPCHK(hipEventRecord(ev2, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -302,8 +329,8 @@ int check_subsets(const bn_info_table* t, int32_t child, int32_t n_base, const i
 }
 
 // ll_out [2^m] in mask order (bit j: cand[j] is a parent); counts_out: null, or every family's counts in the fitted layout, mask order
-int run_subsets(bn_info_table* t, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand, double* ll_out,
-                uint64_t* counts_out, LearnTimes* times) {
+int run_subsets(bn_info_table* t, const bn_score_spec& spec, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand,
+                double* ll_out, uint64_t* counts_out, LearnTimes* times) {
     SubsetShape sh;
     if (int r = check_subsets(t, child, n_base, base, m, cand, sh)) return r;
     const int32_t nv = n_base + m, n_fams = int32_t(1) << m, full = n_fams - 1;
@@ -394,7 +421,7 @@ int run_subsets(bn_info_table* t, int32_t child, int32_t n_base, const int32_t* 
                 return fail(BN_ERR_HIP, std::string("subset lattice level kernel: ") + hipGetErrorString(hipError_t(err)));
     }
     HIPCHK(hipEventRecord(ev2, s));
-    if (int err = learn_launch_score(a, 0, n_fams, s))
+    if (int err = launch_score(spec, a, 0, n_fams, s))
         return fail(BN_ERR_HIP, std::string("family score kernel: ") + hipGetErrorString(hipError_t(err)));
     HIPCHK(hipEventRecord(ev3, s));
     HIPCHK(hipMemcpyAsync(ll_out, d_ll, size_t(n_fams) * 8, hipMemcpyDeviceToHost, s));
@@ -427,8 +454,9 @@ struct bn_learner {
     std::vector<std::vector<int32_t>> parents, children;   // parents increasing per node
     std::vector<double> ll;                                // family term of every node
     int64_t params = 0;
-    double penalty = 1.0;    // per parameter: 1 (AIC), log2(total) / 2 (MDL)
+    double penalty = 1.0;    // per parameter: 1 (AIC), log2(total) / 2 (MDL); criteria 2 (BDeu) and 3 (K2) have none
     double score = 0.0;
+    bn_score_spec spec = kLogLikSpec;   // the family term: kind 0 under AIC / MDL, else the criterion
     LearnTimes times;
 
     int64_t family_params(int32_t v, int64_t rows) const { return int64_t(t->k[size_t(v)] - 1) * rows; }
@@ -441,14 +469,17 @@ struct bn_learner {
     double score_with(int32_t c, double ll_c, int64_t params_now) const {
         double likelihood = 0.0;
         for (int32_t v = 0; v < n; ++v) likelihood -= v == c ? ll_c : ll[size_t(v)];
+        if (criterion >= 2) return likelihood;
         return criterion == 0 ? likelihood + double(params_now) : likelihood + double(params_now) * penalty;
     }
 };
 
-extern "C" int bn_learn_score_groups(bn_info_table* t, int32_t n_groups, const int32_t* child, const int32_t* base_ptr,
-                                     const int32_t* base_idx, const int32_t* cand_ptr, const int32_t* cand_idx, double* ll_out,
-                                     uint64_t* counts_out) {
+extern "C" int bn_learn_score_groups_spec(bn_info_table* t, const bn_score_spec* spec_in, int32_t n_groups, const int32_t* child,
+                                          const int32_t* base_ptr, const int32_t* base_idx, const int32_t* cand_ptr, const int32_t* cand_idx,
+                                          double* ll_out, uint64_t* counts_out) {
     if (!t || !ll_out) return fail(BN_ERR_ARG, "null argument");
+    bn_score_spec spec;
+    if (int r = check_spec(spec_in, spec)) return r;
     if (n_groups < 0) return fail(BN_ERR_ARG, "n_groups < 0");
     if (n_groups > 0 && (!child || !base_ptr || !cand_ptr)) return fail(BN_ERR_ARG, "null argument");
     std::vector<GroupIn> groups(static_cast<size_t>(n_groups));
@@ -458,8 +489,17 @@ extern "C" int bn_learn_score_groups(bn_info_table* t, int32_t n_groups, const i
             return fail(BN_ERR_ARG, gname(size_t(g)) + "bad parent or candidate list");
         groups[size_t(g)] = GroupIn{child[g], base_idx ? base_idx + b0 : nullptr, b1 - b0, cand_idx ? cand_idx + c0 : nullptr, c1 - c0};
     }
-    return run_groups(t, groups, ll_out, counts_out, nullptr);
+    return run_groups(t, spec, groups, ll_out, counts_out, nullptr);
 }
+
+extern "C" int bn_learn_score_groups(bn_info_table* t, int32_t n_groups, const int32_t* child, const int32_t* base_ptr,
+                                     const int32_t* base_idx, const int32_t* cand_ptr, const int32_t* cand_idx, double* ll_out,
+                                     uint64_t* counts_out) {
+    return bn_learn_score_groups_spec(t, nullptr, n_groups, child, base_ptr, base_idx, cand_ptr, cand_idx, ll_out, counts_out);
+}
+
+static int learn_create(bn_info_table* t, const int32_t* in_ptr, const int32_t* in_idx, int32_t criterion, const bn_score_spec& spec,
+                        int32_t max_parents, bn_learner** out);
 
 extern "C" int bn_learn_create(bn_info_table* t, const int32_t* in_ptr, const int32_t* in_idx, int32_t criterion, int32_t max_parents,
                                bn_learner** out) {
@@ -467,6 +507,25 @@ extern "C" int bn_learn_create(bn_info_table* t, const int32_t* in_ptr, const in
     *out = nullptr;
     if (!t || !in_ptr) return fail(BN_ERR_ARG, "null argument");
     if (criterion != 0 && criterion != 1) return fail(BN_ERR_ARG, "criterion: 0 AIC, 1 MDL");
+    return learn_create(t, in_ptr, in_idx, criterion, kLogLikSpec, max_parents, out);
+}
+
+extern "C" int bn_learn_create_spec(bn_info_table* t, const int32_t* in_ptr, const int32_t* in_idx, int32_t criterion, const bn_score_spec* spec_in,
+                                    int32_t max_parents, bn_learner** out) {
+    if (!out) return fail(BN_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (criterion < 0 || criterion > 3) return fail(BN_ERR_ARG, "criterion: 0 AIC, 1 MDL, 2 BDeu, 3 K2");
+    bn_score_spec spec;
+    if (int r = check_spec(spec_in, spec)) return r;
+    if (spec.kind != (criterion >= 2 ? criterion : 0))
+        return fail(BN_ERR_ARG, "criterion " + std::to_string(criterion) + " takes a score spec of kind " + std::to_string(criterion >= 2 ? criterion : 0) +
+                                    ", not " + std::to_string(spec.kind) + (criterion >= 2 && !spec_in ? " (no spec given)" : ""));
+    return learn_create(t, in_ptr, in_idx, criterion, spec, max_parents, out);
+}
+
+static int learn_create(bn_info_table* t, const int32_t* in_ptr, const int32_t* in_idx, int32_t criterion, const bn_score_spec& spec,
+                        int32_t max_parents, bn_learner** out) {
+    if (!t || !in_ptr) return fail(BN_ERR_ARG, "null argument");
     if (max_parents < 0 || max_parents > kLearnMaxParents) return fail(BN_ERR_ARG, "max_parents must be in 0..16");
     const int32_t n = t->n;
     if (in_ptr[0] != 0) return fail(BN_ERR_ARG, "in_ptr must start at 0");
@@ -478,8 +537,9 @@ extern "C" int bn_learn_create(bn_info_table* t, const int32_t* in_ptr, const in
     L->t = t;
     L->n = n;
     L->criterion = criterion;
+    L->spec = spec;
     L->max_parents = max_parents;
-    L->penalty = criterion == 0 ? 1.0 : std::log2(t->Nd) / 2;
+    L->penalty = criterion == 1 ? std::log2(t->Nd) / 2 : 1.0;
     L->parents.resize(size_t(n));
     L->children.resize(size_t(n));
     for (int32_t v = 0; v < n; ++v) {
@@ -503,7 +563,7 @@ extern "C" int bn_learn_create(bn_info_table* t, const int32_t* in_ptr, const in
     std::vector<GroupIn> groups(static_cast<size_t>(n));
     for (int32_t v = 0; v < n; ++v) groups[size_t(v)] = GroupIn{v, L->parents[size_t(v)].data(), int32_t(L->parents[size_t(v)].size()), nullptr, 0};
     L->ll.assign(size_t(n), 0.0);
-    if (int r = run_groups(t, groups, L->ll.data(), nullptr, &L->times)) return r;   // (names the node as "group v" when over a limit)
+    if (int r = run_groups(t, spec, groups, L->ll.data(), nullptr, &L->times)) return r;   // (names the node as "group v" when over a limit)
     for (int32_t v = 0; v < n; ++v) L->params += L->family_params(v, L->rows_of(v));
     L->score = L->score_with(-1, 0.0, L->params);
     *out = L.release();
@@ -553,7 +613,7 @@ extern "C" int bn_learn_try_parents(bn_learner* L, int32_t child, int32_t n_cand
         if (uniq.empty()) break;
         const std::vector<GroupIn> group{GroupIn{child, par.data(), int32_t(par.size()), uniq.data(), int32_t(uniq.size())}};
         ll.assign(uniq.size() + 1, 0.0);
-        if (int r = run_groups(L->t, group, ll.data(), nullptr, &L->times)) return r;
+        if (int r = run_groups(L->t, L->spec, group, ll.data(), nullptr, &L->times)) return r;
         for (size_t j = 0; j < uniq.size(); ++j) fam_of[size_t(uniq[j])] = int32_t(j) + 1;
         int32_t taken = -1;
         for (int32_t i = pos; i < n_cand && taken < 0; ++i) {
@@ -619,16 +679,24 @@ extern "C" int bn_learn_get(const bn_learner* L, const char* name, int64_t* out)
         *out = 0;
         for (const auto& p : L->parents) *out += int64_t(p.size());
     } else if (s == "parameters") *out = L->params;
-    else return fail(BN_ERR_ARG, "unknown name (families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, hc_ns, hc_runs, hc_merges, edges, parameters)");
+    else if (s == "criterion") *out = L->criterion;
+    else return fail(BN_ERR_ARG, "unknown name (criterion, families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, hc_ns, hc_runs, hc_merges, edges, parameters)");
     return BN_OK;
 }
 
 // ---- exhaustive search: the subset lattice per child (reference bayesian/learning/brute_force.hpp) ----------------------------------
 
+extern "C" int bn_learn_score_subsets_spec(bn_info_table* t, const bn_score_spec* spec_in, int32_t child, int32_t n_base, const int32_t* base,
+                                           int32_t m, const int32_t* cand, double* ll_out, uint64_t* counts_out) {
+    if (!t || !ll_out) return fail(BN_ERR_ARG, "null argument");
+    bn_score_spec spec;
+    if (int r = check_spec(spec_in, spec)) return r;
+    return run_subsets(t, spec, child, n_base, base, m, cand, ll_out, counts_out, nullptr);
+}
+
 extern "C" int bn_learn_score_subsets(bn_info_table* t, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand,
                                       double* ll_out, uint64_t* counts_out) {
-    if (!t || !ll_out) return fail(BN_ERR_ARG, "null argument");
-    return run_subsets(t, child, n_base, base, m, cand, ll_out, counts_out, nullptr);
+    return bn_learn_score_subsets_spec(t, nullptr, child, n_base, base, m, cand, ll_out, counts_out);
 }
 
 namespace {
@@ -701,7 +769,8 @@ struct Walk {
             return fail(BN_ERR_ARG, "node " + std::to_string(node) + ": " + std::to_string(sl.cand.size()) + " candidate parents (at most " +
                                         std::to_string(kLearnMaxParents) + " minus its parents)");
         sl.ll.assign(size_t(1) << sl.cand.size(), 0.0);
-        if (int r = run_subsets(L->t, node, int32_t(par.size()), par.data(), int32_t(sl.cand.size()), sl.cand.data(), sl.ll.data(), nullptr, &L->times))
+        if (int r = run_subsets(L->t, L->spec, node, int32_t(par.size()), par.data(), int32_t(sl.cand.size()), sl.cand.data(), sl.ll.data(), nullptr,
+                                 &L->times))
             return r;
         slot_of[size_t(node)] = int32_t(slots.size());
         slots.push_back(std::move(sl));
@@ -758,6 +827,7 @@ struct Walk {
         ll[size_t(c)] = sl.ll[size_t(sl.mask)];
     }
     double penalised(double likelihood) const {
+        if (L->criterion >= 2) return likelihood;
         return L->criterion == 0 ? likelihood + double(params) : likelihood + double(params) * L->penalty;
     }
     void keep() {
@@ -809,7 +879,7 @@ extern "C" int bn_learn_best_parents(bn_learner* L, int32_t child, int32_t n_can
     if (m > kLearnMaxParents)
         return fail(BN_ERR_ARG, std::to_string(m) + " candidates may be added (at most " + std::to_string(kLearnMaxParents) + " minus the parents)");
     std::vector<double> ll(size_t(1) << m);
-    if (int r = run_subsets(L->t, child, int32_t(par.size()), par.data(), m, surv.data(), ll.data(), nullptr, &L->times)) return r;
+    if (int r = run_subsets(L->t, L->spec, child, int32_t(par.size()), par.data(), m, surv.data(), ll.data(), nullptr, &L->times)) return r;
     // the reference's visiting order (brute_force.hpp:104-111): "not added" before "added", cand[0] outermost
     int32_t best_mask = 0;
     int64_t best_params = L->params;
@@ -981,6 +1051,7 @@ struct bn_term_table {
     DeviceBuf<uint32_t> d_tab;
     DeviceBuf<int32_t> d_k;
     int64_t ineligible = 0;
+    bn_score_spec spec = kLogLikSpec;    // the family term the entries hold
     LearnTimes times;
 
     // sorted parents, none of them c
@@ -997,9 +1068,15 @@ struct bn_term_table {
 };
 
 extern "C" int bn_terms_create(bn_info_table* t, int32_t max_parents, bn_term_table** out) {
+    return bn_terms_create_spec(t, nullptr, max_parents, out);
+}
+
+extern "C" int bn_terms_create_spec(bn_info_table* t, const bn_score_spec* spec_in, int32_t max_parents, bn_term_table** out) {
     if (!out) return fail(BN_ERR_ARG, "null argument");
     *out = nullptr;
     if (!t) return fail(BN_ERR_ARG, "null argument");
+    bn_score_spec spec;
+    if (int r = check_spec(spec_in, spec)) return r;
     if (max_parents < 1 || max_parents > kLearnMaxParents) return fail(BN_ERR_ARG, "term table: max_parents must be in 1..16");
     const int32_t n = t->n, q = max_parents;
     if (n > kAnnealMaxNodes)
@@ -1028,6 +1105,7 @@ extern "C" int bn_terms_create(bn_info_table* t, int32_t max_parents, bn_term_ta
     tt->device = t->device;
     tt->n = n;
     tt->q = q;
+    tt->spec = spec;
     tt->T = offset[size_t(q) + 1];
     tt->tab.assign(size_t(kAnnealTabWords), 0u);
     for (int32_t j = 0; j <= q; ++j) tt->tab[size_t(j)] = uint32_t(offset[size_t(j)]);
@@ -1093,7 +1171,7 @@ extern "C" int bn_terms_create(bn_info_table* t, int32_t max_parents, bn_term_ta
         n_fams += size_t(1 + g_ncand[g]);
     }
     std::vector<double> ll(std::max<size_t>(n_fams, 1), 0.0);
-    if (int r = run_groups(t, groups, ll.data(), nullptr, &tt->times)) return r;
+    if (int r = run_groups(t, spec, groups, ll.data(), nullptr, &tt->times)) return r;
     std::vector<double> terms(size_t(tt->T) * size_t(n), std::numeric_limits<double>::quiet_NaN());
     {
         size_t at = 0;
@@ -1133,7 +1211,9 @@ extern "C" int bn_terms_get(const bn_term_table* tt, const char* name, int64_t* 
     else if (s == "families_scored") *out = tt->times.families;
     else if (s == "passes") *out = tt->times.passes;
     else if (s == "build_ns") *out = int64_t(tt->times.count_ns + tt->times.score_ns);
-    else return fail(BN_ERR_ARG, "unknown name (entries, row_entries, nodes, max_parents, ineligible, families_scored, passes, build_ns)");
+    else if (s == "score_kind") *out = tt->spec.kind;
+    else if (s == "ess_bits") std::memcpy(out, &tt->spec.ess, 8);
+    else return fail(BN_ERR_ARG, "unknown name (score_kind, ess_bits, entries, row_entries, nodes, max_parents, ineligible, families_scored, passes, build_ns)");
     return BN_OK;
 }
 
@@ -1147,6 +1227,14 @@ extern "C" int bn_terms_fetch(const bn_term_table* tt, int32_t child, double* ll
 }
 
 // the winner's graph and terms become the learner's (score = score_with(-1, 0.0, params): the kernels' evaluation is that function)
+// a search over a term table reads the table's terms as the learner's: they must be the same function
+static int check_table_spec(const char* who, const bn_learner* L, const bn_term_table* tt) {
+    if (same_spec(L->spec, tt->spec)) return BN_OK;
+    std::string what = std::string(who) + ": the term table holds " + spec_name(tt->spec) + " terms, the learner scores by " + spec_name(L->spec);
+    if (L->spec.kind == 2 && tt->spec.kind == 2) what += " with another ess (" + std::to_string(tt->spec.ess) + " against " + std::to_string(L->spec.ess) + ")";
+    return fail(BN_ERR_ARG, what);
+}
+
 static void adopt_winner(bn_learner* L, const std::vector<uint64_t>& win_mask, const std::vector<double>& win_ll, double score) {
     const int32_t n = L->n;
     for (int32_t v = 0; v < n; ++v) {
@@ -1174,6 +1262,7 @@ extern "C" int bn_learn_anneal(bn_learner* L, bn_term_table* tt, const bn_anneal
                                bn_anneal_trace* trace_out, int32_t* winner_out) {
     if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
     if (tt->t != L->t) return fail(BN_ERR_ARG, "anneal: the term table was built from another table than the learner's");
+    if (int r = check_table_spec("anneal", L, tt)) return r;
     auto positive = [](double x) { return std::isfinite(x) && x > 0.0; };
     if (!positive(p->initial_temp) || !positive(p->final_temp)) return fail(BN_ERR_ARG, "anneal: the temperatures must be finite and positive");
     if (!(p->decreasing_rate > 0.0 && p->decreasing_rate < 1.0)) return fail(BN_ERR_ARG, "anneal: decreasing_rate must be in (0, 1)");
@@ -1305,6 +1394,7 @@ extern "C" int bn_learn_hc(bn_learner* L, bn_term_table* tt, const bn_hc_params*
                            int32_t* winner_out) {
     if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
     if (tt->t != L->t) return fail(BN_ERR_ARG, "hc: the term table was built from another table than the learner's");
+    if (int r = check_table_spec("hc", L, tt)) return r;
     const int32_t n = L->n, q = tt->q;
     if (n > kAnnealMaxNodes) return fail(BN_ERR_ARG, "hc: " + std::to_string(n) + " nodes (at most 64: a node has a lane)");
     if (runs < 1 || runs > kHcMaxRuns) return fail(BN_ERR_ARG, "hc: " + std::to_string(runs) + " runs (1 .. 65536)");

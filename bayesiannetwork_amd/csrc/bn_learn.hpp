@@ -62,6 +62,8 @@ struct LearnArgs {
 // each returns a hipError_t value (0: success).  chunk0 / fam0: first chunk / family of the pass; N is the pass's own scratch.
 int learn_launch_count(const LearnArgs& a, int32_t chunk0, int32_t n_chunks, int splits, void* stream);
 int learn_launch_score(const LearnArgs& a, int32_t fam0, int32_t n_fams, void* stream);
+// the Bayesian-Dirichlet form (bn_learn_bd.hip): kind 2 BDeu with equivalent sample size ess, kind 3 K2 (ess not read)
+int learn_launch_score_bd(const LearnArgs& a, int32_t fam0, int32_t n_fams, int32_t kind, double ess, void* stream);
 
 // ---- the subset lattice (bn_learn_lattice.hip): the counts of base + every subset of the candidates, from the counts of the TOP
 // family base + all candidates.  The top family's variables are held in increasing id (position 0 most significant); family `mask`

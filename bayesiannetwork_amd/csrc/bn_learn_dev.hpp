@@ -42,11 +42,40 @@ __device__ __forceinline__ double term_of(const double* __restrict__ terms, int6
 }
 
 // the learner's score of the graph whose family terms the lanes hold in x: likelihood -= ll[v] in node order through lane reads (no
-// tree), then the AIC / MDL penalty from the exact parameter count -- the bits of bn_learn_score
+// tree), then the AIC / MDL penalty from the exact parameter count -- the bits of bn_learn_score.  Criteria 2 and 3 (BDeu, K2) have
+// no penalty: the likelihood alone.
 __device__ __forceinline__ double evaluate_terms(double x, int64_t params, int n, int criterion, double penalty) {
     double likelihood = 0.0;
     for (int v = 0; v < n; ++v) likelihood -= lane_f64(x, v);
+    if (criterion >= 2) return likelihood;
     return criterion == 0 ? likelihood + double(params) : likelihood + double(params) * penalty;
+}
+
+// log Gamma(x) for finite x > 0 as a stated function (include/bn_mi355x.h, "Bayesian-Dirichlet scores"): the argument is shifted
+// to x >= 16 by the recurrence, then Stirling's series with six terms; every operation is a plain fp64 one (no contraction) and the
+// only library call is the device's log.
+constexpr double kLgC0 = 1.0 / 12.0, kLgC1 = -1.0 / 360.0, kLgC2 = 1.0 / 1260.0, kLgC3 = -1.0 / 1680.0, kLgC4 = 1.0 / 1188.0,
+                 kLgC5 = -691.0 / 360360.0;
+constexpr uint64_t kHalfLog2PiBits = 0x3FED67F1C864BEB4ull;   // 0.9189385332046727
+
+__device__ inline double lgamma_pos(double x) {
+    double p = 1.0;
+    bool shifted = false;
+    while (x < 16.0) {   // at most 16 steps
+        p = p * x;
+        x = x + 1.0;
+        shifted = true;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    double s = kLgC5;
+    s = s * r2 + kLgC4;
+    s = s * r2 + kLgC3;
+    s = s * r2 + kLgC2;
+    s = s * r2 + kLgC1;
+    s = s * r2 + kLgC0;
+    s = s * r;
+    const double v = (((x - 0.5) * log(x)) - x) + __longlong_as_double((long long)kHalfLog2PiBits) + s;
+    return shifted ? v - log(p) : v;
 }
 
 }  // namespace

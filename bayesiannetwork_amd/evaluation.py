@@ -11,7 +11,10 @@ reference's value.  Not in the reference: InfoTable itself and mutual_informatio
 Also the mirror of bn::evaluation::aic / mdl (reference bayesian/evaluation/aic.hpp, mdl.hpp over
 basic_info_criteria.hpp:44-117): `AIC(sampling)` / `MDL(sampling)` score a network against a table through
 bn_score_nodes.  Not in the reference: `log_likelihood_rows` (per distinct pattern), `log_likelihood_nodes`
-(per node, optionally with the family counts), `log_cpt` and `parameters` as functions of their own."""
+(per node, optionally with the family counts), `log_cpt` and `parameters` as functions of their own.
+
+`BDeu(ess)` and `K2Score()` are the Bayesian-Dirichlet scores (not in the reference): called on a model and a table they give minus
+the log marginal likelihood of the table under the model's structure, the function learning.py's searches minimise under them."""
 from __future__ import annotations
 
 import ctypes
@@ -275,3 +278,45 @@ class MDL(_InfoCriterion):
             raise RuntimeError("Sampling is not finished yet.")
         likelihood, params = self._terms(engine_or_model, nodes)
         return likelihood + params * (math.log2(float(self.sampling_size())) / 2)
+
+
+# ---- Bayesian-Dirichlet scores (bn_score_spec of include/bn_mi355x.h) -------------------------------
+
+class _BDScore:
+    """score(model, sampling): minus the log marginal likelihood of `sampling` (an InfoTable over every node in node order, or an
+    engine.Sampler) under the structure of `model` (a FlatModel, or per-node parent lists with an InfoTable); the CPTs are not
+    read.  Smaller is better.  Computed by the library's learner (bn_learn_create_spec): the bits of `Learner.score()`."""
+
+    kind, ess = 0, 0.0
+
+    def __call__(self, model, sampling) -> float:
+        from .learning import Learner
+        if isinstance(sampling, InfoTable):
+            with Learner(sampling, model, self) as L:
+                return L.score()
+        with table_from_sampler(sampling, range(model.n), model.k) as t, Learner(t, model, self) as L:
+            return L.score()
+
+
+class BDeu(_BDScore):
+    """BDeu with the equivalent sample size `ess` (finite, within [2^-20, 2^20])."""
+
+    kind = 2
+
+    def __init__(self, ess: float = 1.0):
+        ess = float(ess)
+        if not (math.isfinite(ess) and 2.0 ** -20 <= ess <= 2.0 ** 20):
+            raise ValueError(f"BDeu: ess must be finite and within [2^-20, 2^20], not {ess!r}")
+        self.ess = ess
+
+    def __repr__(self):
+        return f"BDeu(ess={self.ess!r})"
+
+
+class K2Score(_BDScore):
+    """The K2 (Cooper-Herskovits) score: a uniform Dirichlet prior, every hyperparameter 1."""
+
+    kind = 3
+
+    def __repr__(self):
+        return "K2Score()"

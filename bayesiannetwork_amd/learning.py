@@ -1,5 +1,7 @@
 """Mirror of bn::learning (reference bayesian/learning/greedy.hpp, k2_algorithm.hpp, brute_force.hpp, stepwise_structure.hpp):
-structure search under AIC / MDL on the GPU (bn_learn_* of include/bn_mi355x.h).
+structure search under AIC / MDL, BDeu or the K2 score on the GPU (bn_learn_* of include/bn_mi355x.h).  Every class and function
+here takes `criterion`: "aic", "mdl", "bdeu", "k2score", or the AIC / MDL / BDeu / K2Score classes or instances (`BDeu(10)` for
+another equivalent sample size).  Under BDeu and K2 the score is minus the log marginal likelihood, no penalty: smaller is better.
 
 AIC and MDL are decomposable, so a candidate edge u -> c changes the family term of c and the parameter count and nothing else.
 `score_groups` scores many candidate families of a child in one pass over an `InfoTable`; `Learner` holds a graph, its family
@@ -25,7 +27,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .evaluation import AIC, MDL, InfoTable, table_from_sampler
+from .evaluation import AIC, MDL, BDeu, InfoTable, K2Score, table_from_sampler
 from .flat import FlatModel
 
 MAX_PARENTS = 16
@@ -35,14 +37,37 @@ def _p(a, t):
     return a.ctypes.data_as(ctypes.POINTER(t))
 
 
-def _criterion(c) -> int:
+def _canon(c):
+    """A criterion in the form the classes here pass on: "aic", "mdl", a BDeu instance or a K2Score instance."""
     if isinstance(c, str) and c.lower() in ("aic", "mdl"):
-        return 0 if c.lower() == "aic" else 1
+        return c.lower()
     if c is AIC or isinstance(c, AIC):
-        return 0
+        return "aic"
     if c is MDL or isinstance(c, MDL):
-        return 1
-    raise ValueError('criterion: "aic", "mdl", or the AIC / MDL classes')
+        return "mdl"
+    if isinstance(c, (BDeu, K2Score)):
+        return c
+    if c is BDeu or (isinstance(c, str) and c.lower() == "bdeu"):
+        return BDeu()
+    if c is K2Score or (isinstance(c, str) and c.lower() == "k2score"):
+        return K2Score()
+    raise ValueError('criterion: "aic", "mdl", "bdeu", "k2score", or the AIC / MDL / BDeu / K2Score classes or instances')
+
+
+def _criterion(c) -> int:
+    """0 AIC, 1 MDL, 2 BDeu, 3 K2."""
+    c = _canon(c)
+    return {"aic": 0, "mdl": 1}[c] if isinstance(c, str) else c.kind
+
+
+def _spec(c) -> _lib.ScoreSpec:
+    """The family term of a criterion: kind 0 under AIC / MDL."""
+    c = _canon(c)
+    return _lib.ScoreSpec(0, 0, 0.0) if isinstance(c, str) else _lib.ScoreSpec(c.kind, 0, float(c.ess))
+
+
+def _spec_text(kind: int, ess: float) -> str:
+    return {0: "the log-likelihood term (AIC / MDL)", 2: f"BDeu(ess={ess!r})", 3: "K2"}[kind]
 
 
 def _csr(lists):
@@ -53,10 +78,12 @@ def _csr(lists):
     return ptr, idx
 
 
-def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0):
+def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0, criterion=None):
     """groups: [(child, base parents (strictly increasing), candidates), ...].  Returns per group the list of family terms
     [ll(base), ll(base + u_0), ...]; counts=True: (that, per group the list of uint64 count arrays in the fitted layout).
-    splits > 0 fixes the number of workgroups the patterns are split over (no result depends on it)."""
+    splits > 0 fixes the number of workgroups the patterns are split over (no result depends on it).  criterion: None, "aic" or
+    "mdl" give the log-likelihood term; BDeu / K2Score the Bayesian-Dirichlet term (bn_learn_score_groups_spec)."""
+    spec = None if criterion is None else _spec(criterion)
     groups = [(int(c), [int(x) for x in b], [int(x) for x in u]) for c, b, u in groups]
     child = np.array([g[0] for g in groups], dtype=np.int32)
     bptr, bidx = _csr([g[1] for g in groups])
@@ -82,9 +109,12 @@ def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0
     if splits > 0:
         os.environ["BN_LEARN_SPLITS"] = str(int(splits))
     try:
-        _lib.check(_lib.lib().bn_learn_score_groups(table._h, len(groups), _p(child, ctypes.c_int32), _p(bptr, ctypes.c_int32),
-                                                    _p(bidx, ctypes.c_int32), _p(cptr, ctypes.c_int32), _p(cidx, ctypes.c_int32),
-                                                    _p(ll, ctypes.c_double), _p(N, ctypes.c_uint64) if counts else None))
+        args = (len(groups), _p(child, ctypes.c_int32), _p(bptr, ctypes.c_int32), _p(bidx, ctypes.c_int32), _p(cptr, ctypes.c_int32),
+                _p(cidx, ctypes.c_int32), _p(ll, ctypes.c_double), _p(N, ctypes.c_uint64) if counts else None)
+        if spec is None:
+            _lib.check(_lib.lib().bn_learn_score_groups(table._h, *args))
+        else:
+            _lib.check(_lib.lib().bn_learn_score_groups_spec(table._h, ctypes.byref(spec), *args))
     finally:
         if splits > 0:
             if old is None:
@@ -107,10 +137,12 @@ def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0
     return out, blocks
 
 
-def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False, splits: int = 0):
+def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False, splits: int = 0, criterion=None):
     """The family terms of `child` with the parents base + S for every subset S of `cand`: a list of 2^m values, entry `mask`
     standing for S = {cand[j] : bit j of mask}.  counts=True: (that, the list of the 2^m uint64 count arrays in the fitted
-    layout).  One count of the top family base + cand; every other family is summed out of it on the device."""
+    layout).  One count of the top family base + cand; every other family is summed out of it on the device.  criterion: as
+    score_groups'."""
+    spec = None if criterion is None else _spec(criterion)
     base = np.ascontiguousarray([int(x) for x in base], dtype=np.int32)
     cand = np.ascontiguousarray([int(x) for x in cand], dtype=np.int32)
     m = len(cand)
@@ -131,8 +163,12 @@ def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False
     if splits > 0:
         os.environ["BN_LEARN_SPLITS"] = str(int(splits))
     try:
-        _lib.check(_lib.lib().bn_learn_score_subsets(table._h, int(child), len(base), _p(base, ctypes.c_int32), m, _p(cand, ctypes.c_int32),
-                                                     _p(ll, ctypes.c_double), _p(N, ctypes.c_uint64) if counts else None))
+        args = (int(child), len(base), _p(base, ctypes.c_int32), m, _p(cand, ctypes.c_int32), _p(ll, ctypes.c_double),
+                _p(N, ctypes.c_uint64) if counts else None)
+        if spec is None:
+            _lib.check(_lib.lib().bn_learn_score_subsets(table._h, *args))
+        else:
+            _lib.check(_lib.lib().bn_learn_score_subsets_spec(table._h, ctypes.byref(spec), *args))
     finally:
         if splits > 0:
             if old is None:
@@ -150,7 +186,7 @@ def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False
 
 class Learner:
     """bn_learner: a graph over the columns of `table`, its family terms and its score.  `structure`: None (no edges), a
-    FlatModel, or per-node parent lists."""
+    FlatModel, or per-node parent lists.  `criterion`: see the module's text; `info("criterion")` gives 0 AIC, 1 MDL, 2 BDeu, 3 K2."""
 
     def __init__(self, table: InfoTable, structure=None, criterion="aic", max_parents: int = MAX_PARENTS):
         if structure is None:
@@ -163,10 +199,21 @@ class Learner:
             raise ValueError(f"the structure has {len(parents)} nodes, the table {table.n} columns")
         ptr, idx = _csr(parents)
         self.table, self.n = table, table.n
+        self.criterion = _canon(criterion)
+        spec = _spec(self.criterion)
+        self.spec = (spec.kind, spec.ess)   # the family term: what a term table must hold for anneal / hc
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().bn_learn_create(table._h, _p(ptr, ctypes.c_int32), _p(idx, ctypes.c_int32), _criterion(criterion),
-                                              int(max_parents), ctypes.byref(h)))
+        if spec.kind == 0:
+            _lib.check(_lib.lib().bn_learn_create(table._h, _p(ptr, ctypes.c_int32), _p(idx, ctypes.c_int32), _criterion(self.criterion),
+                                                  int(max_parents), ctypes.byref(h)))
+        else:
+            _lib.check(_lib.lib().bn_learn_create_spec(table._h, _p(ptr, ctypes.c_int32), _p(idx, ctypes.c_int32), spec.kind,
+                                                       ctypes.byref(spec), int(max_parents), ctypes.byref(h)))
         self._h = h
+
+    def _check_terms(self, term_table: "TermTable") -> None:
+        if term_table.spec != self.spec:
+            raise ValueError(f"the term table holds {_spec_text(*term_table.spec)} terms, the learner scores by {_spec_text(*self.spec)}")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -229,6 +276,7 @@ class Learner:
         structured array `trace` (TRACE_DTYPE) of that chain's operated proposals (the first trace_cap, default max_proposals)."""
         if rule not in _RULES:
             raise ValueError('rule: "reference" or "metropolis"')
+        self._check_terms(term_table)
         chains = int(chains)
         tracing = trace_chain is not None
         cap = int(max_proposals if trace_cap is None else trace_cap) if tracing else 0
@@ -263,6 +311,7 @@ class Learner:
         with trace_run the structured arrays `merge_trace` (parent, child, value_bits, coin) and `prune_trace` (cluster,
         connections, value_bits, pruned) of that run."""
         runs = int(runs)
+        self._check_terms(term_table)
         tracing = trace_run is not None
         cap = int(trace_cap) if tracing else 0
         p = _lib.HcParams(float(alpha), int(term_table.max_parents if max_parents is None else max_parents),
@@ -328,10 +377,15 @@ class TermTable:
     eligible).  At most 64 nodes and n * T(n, q) <= 2^22 entries.  `row(child)` fetches one child's T(n, q) entries, `rank(child,
     parents)` is the index of a parent set in it.  Borrows `table`: close the term table first."""
 
-    def __init__(self, table: InfoTable, max_parents: int = 3):
+    def __init__(self, table: InfoTable, max_parents: int = 3, criterion=None):
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().bn_terms_create(table._h, int(max_parents), ctypes.byref(h)))
+        spec = _lib.ScoreSpec(0, 0, 0.0) if criterion is None else _spec(criterion)
+        if criterion is None:
+            _lib.check(_lib.lib().bn_terms_create(table._h, int(max_parents), ctypes.byref(h)))
+        else:
+            _lib.check(_lib.lib().bn_terms_create_spec(table._h, ctypes.byref(spec), int(max_parents), ctypes.byref(h)))
         self._h = h
+        self.spec = (spec.kind, spec.ess)
         self.table, self.n, self.max_parents = table, table.n, int(max_parents)
         self.row_entries = self.info("row_entries")
 
@@ -383,6 +437,7 @@ def structure_model(k, in_ptr, in_idx, name: str = "") -> FlatModel:
 class _Search:
     def __init__(self, criterion, sampling, max_parents: int = MAX_PARENTS, seed=None, device: int = _lib.BN_DEVICE_CURRENT):
         self._criterion, self._sampling, self._max_parents, self._device = _criterion(criterion), sampling, int(max_parents), device
+        self._name = _canon(criterion)   # what is passed on to Learner, TermTable and the inner searches
         self._rng = np.random.default_rng(seed)
         self._table = sampling if isinstance(sampling, InfoTable) else None
         self.last = {}   # counters of the last search: families_scored, passes, count_ns, score_ns, lattice_ns, subsets_scored
@@ -393,7 +448,7 @@ class _Search:
         return self._table
 
     def _learner(self, model) -> Learner:
-        return Learner(self._ensure_table(model), model, "aic" if self._criterion == 0 else "mdl", self._max_parents)
+        return Learner(self._ensure_table(model), model, self._name, self._max_parents)
 
     def _finish(self, model, L: Learner):
         from .engine import fit_cpt
@@ -523,7 +578,7 @@ class StepwiseStructure(_Search):
         if not isinstance(kind, type):
             return kind
         seed = int(self._rng.integers(1 << 32)) if self._seeded else None
-        return kind("aic" if self._criterion == 0 else "mdl", self._table, max_parents=self._max_parents, seed=seed, device=self._device)
+        return kind(self._name, self._table, max_parents=self._max_parents, seed=seed, device=self._device)
 
     def __call__(self, model, initial_cluster_size: int, plan=None):
         size = int(initial_cluster_size)
@@ -531,7 +586,7 @@ class StepwiseStructure(_Search):
             raise ValueError("initial_cluster_size must be positive")
         table = self._ensure_table(model)
         inner, between = self._make(self._inner), self._make(self._between)
-        with Learner(table, None, "aic" if self._criterion == 0 else "mdl", self._max_parents) as L:   # (:26: erase_all_edge)
+        with Learner(table, None, self._name, self._max_parents) as L:   # (:26: erase_all_edge)
             n = L.n
             if plan is not None:
                 clusters = [[int(v) for v in c] for c in plan[0]]
@@ -596,7 +651,7 @@ class SimulatedAnnealing(_Search):
 
     def term_table(self, model) -> TermTable:
         if self._terms is None:
-            self._terms = TermTable(self._ensure_table(model), self._max_parents)
+            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
         return self._terms
 
     def __call__(self, model, initial_temp: float, final_temp: float, decreasing_rate: float, boltzmann: float = 1.0,
@@ -679,7 +734,7 @@ class StepwiseStructureHC(_Search):
 
     def term_table(self, model) -> TermTable:
         if self._terms is None:
-            self._terms = TermTable(self._ensure_table(model), self._max_parents)
+            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
         return self._terms
 
     def _resident(self) -> bool:
@@ -689,8 +744,7 @@ class StepwiseStructureHC(_Search):
         table = self._ensure_table(model)
         seed = self._seed + self._calls
         self._calls += 1
-        criterion = "aic" if self._criterion == 0 else "mdl"
-        with Learner(table, None, criterion, self._max_parents) as L:   # (:134: erase_all_edge)
+        with Learner(table, None, self._name, self._max_parents) as L:   # (:134: erase_all_edge)
             if self._resident():
                 terms = self.term_table(model)
                 self.records = L.hc(terms, alpha, self._runs, seed)
@@ -707,7 +761,7 @@ class StepwiseStructureHC(_Search):
     def _host_run(self, L: Learner, table: InfoTable, alpha: float, seed: int) -> int:
         between = self._between
         if isinstance(between, type):
-            between = between("aic" if self._criterion == 0 else "mdl", table, max_parents=self._max_parents,
+            between = between(self._name, table, max_parents=self._max_parents,
                               seed=int(self._rng.integers(1 << 32)) if self._seeded else None, device=self._device)
         n = L.n
         S = table.pair_entropies()["mi"]

@@ -56,7 +56,7 @@ public:
     {
         if(on_device())
         {
-            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
             double const best = session.brute_force(graph, vertexes);
             sampling_.make_cpt(graph);
             return best;
@@ -74,7 +74,7 @@ public:
     {
         if(on_device())
         {
-            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
             double const best = session.brute_force_hint(graph, parent_nodes, child_nodes);
             sampling_.make_cpt(graph);
             return best;

@@ -1,5 +1,6 @@
 // bayesian/learning/greedy.hpp -- drop-in for the reference's bn::learning::greedy<Eval> (bayesian/learning/greedy.hpp), the
-// search running on the MI355X through bn_learn_* (include/bn_mi355x.h) when Eval is bn::evaluation::aic or mdl.  C++14, no Boost.
+// search running on the MI355X through bn_learn_* (include/bn_mi355x.h) when Eval is bn::evaluation::aic, mdl, basic_bdeu<> or k2_score
+// (evaluation/bdeu.hpp; under the last two the score is the likelihood alone and eval_(graph) has its bits).  C++14, no Boost.
 //
 // Same class, same members: greedy(sampler const&), operator()(graph), operator()(graph, vertexes),
 // learn_with_hint(graph, parent_nodes, child_nodes); the shuffles are the reference's (std::shuffle with a std::mt19937).
@@ -32,6 +33,7 @@
 #include <bayesian/graph.hpp>
 #include <bayesian/sampler.hpp>
 #include <bayesian/evaluation/aic.hpp>
+#include <bayesian/evaluation/bdeu.hpp>
 #include <bayesian/evaluation/mdl.hpp>
 #include <bayesian/evaluation/transinformation.hpp>
 
@@ -46,10 +48,19 @@ struct visit_t {
 
 namespace detail {
 
-// 0 AIC, 1 MDL, -1: any other evaluation (the literal loop)
-template<class Eval> struct criterion_of : std::integral_constant<int, -1> {};
-template<> struct criterion_of<evaluation::aic> : std::integral_constant<int, 0> {};
-template<> struct criterion_of<evaluation::mdl> : std::integral_constant<int, 1> {};
+// 0 AIC, 1 MDL, 2 BDeu, 3 K2, -1: any other evaluation (the literal loop); spec(): the family term bn_learn_create_spec takes
+struct loglik_spec {
+    static bn_score_spec spec() { return bn_score_spec{0, 0, 0.0}; }
+};
+template<class Eval> struct criterion_of : std::integral_constant<int, -1>, loglik_spec {};
+template<> struct criterion_of<evaluation::aic> : std::integral_constant<int, 0>, loglik_spec {};
+template<> struct criterion_of<evaluation::mdl> : std::integral_constant<int, 1>, loglik_spec {};
+template<class Ess> struct criterion_of<evaluation::basic_bdeu<Ess>> : std::integral_constant<int, 2> {
+    static bn_score_spec spec() { return bn_score_spec{2, 0, evaluation::basic_bdeu<Ess>::ess()}; }
+};
+template<> struct criterion_of<evaluation::k2_score> : std::integral_constant<int, 3> {
+    static bn_score_spec spec() { return bn_score_spec{3, 0, 0.0}; }
+};
 
 // (reference bayesian/utility.hpp: make_engine)
 inline std::mt19937 make_engine()
@@ -61,8 +72,9 @@ inline std::mt19937 make_engine()
 // a bn_learner over the graph's vertex_list(), starting from the graph's edges
 class learner_session {
 public:
-    learner_session(sampler const& sampling, graph_t const& graph, int criterion, int max_parents = 16)
-        : nodes_(graph.vertex_list()), table_(sampling, nodes_)
+    learner_session(sampler const& sampling, graph_t const& graph, int criterion, bn_score_spec const& spec = bn_score_spec{0, 0, 0.0},
+                    int max_parents = 16)
+        : nodes_(graph.vertex_list()), table_(sampling, nodes_), spec_(spec)
     {
         std::vector<std::int32_t> in_ptr(1, 0), in_idx;
         for(auto const& node : nodes_)
@@ -70,7 +82,7 @@ public:
             for(auto const& parent : graph.in_vertexes(node)) in_idx.push_back(index_of(parent));
             in_ptr.push_back(static_cast<std::int32_t>(in_idx.size()));
         }
-        mi355x::engine_handle::check(bn_learn_create(table_.handle(), in_ptr.data(), in_idx.data(), criterion, max_parents, &learner_));
+        mi355x::engine_handle::check(bn_learn_create_spec(table_.handle(), in_ptr.data(), in_idx.data(), criterion, &spec_, max_parents, &learner_));
     }
     ~learner_session() { bn_learn_destroy(learner_); }
     learner_session(learner_session const&) = delete;
@@ -122,7 +134,7 @@ public:
     std::int32_t anneal(graph_t& graph, std::int32_t max_parents, bn_anneal_params const& params, std::int32_t chains, std::uint64_t seed)
     {
         bn_term_table* terms = nullptr;
-        mi355x::engine_handle::check(bn_terms_create(table_.handle(), max_parents, &terms));
+        mi355x::engine_handle::check(bn_terms_create_spec(table_.handle(), &spec_, max_parents, &terms));
         std::int32_t winner = 0;
         int const rc = bn_learn_anneal(learner_, terms, &params, chains, seed, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &winner);
         bn_terms_destroy(terms);
@@ -137,7 +149,7 @@ public:
     std::int32_t hc(graph_t& graph, std::int32_t max_parents, double alpha, std::int32_t runs, std::uint64_t seed)
     {
         bn_term_table* terms = nullptr;
-        mi355x::engine_handle::check(bn_terms_create(table_.handle(), max_parents, &terms));
+        mi355x::engine_handle::check(bn_terms_create_spec(table_.handle(), &spec_, max_parents, &terms));
         bn_hc_params const params{alpha, max_parents, -1, 0, 0};
         std::int32_t winner = 0;
         int const rc = bn_learn_hc(learner_, terms, &params, runs, seed, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &winner);
@@ -186,6 +198,7 @@ private:
 
     std::vector<vertex_type> nodes_;
     evaluation::information_table table_;
+    bn_score_spec spec_;
     bn_learner* learner_ = nullptr;
 };
 
@@ -272,7 +285,7 @@ private:
     {
         if(detail::criterion_of<Eval>::value >= 0 && sampling_.sampling_size() != 0)
         {
-            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
             for(auto const& visit : visits_) session.try_parents(graph, visit.child, visit.candidates);
             sampling_.make_cpt(graph);
             return session.score();

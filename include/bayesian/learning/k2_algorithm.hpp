@@ -45,7 +45,7 @@ public:
         bool const on_device = detail::criterion_of<Eval>::value >= 0 && sampling_.sampling_size() != 0;
         std::unique_ptr<detail::learner_session> session;
         double eval_best = 0.0;
-        if(on_device) session.reset(new detail::learner_session(sampling_, graph, detail::criterion_of<Eval>::value));
+        if(on_device) session.reset(new detail::learner_session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec()));
         else
         {
             sampling_.make_cpt(graph);

@@ -125,7 +125,7 @@ public:
         if(rule_ != 0 && rule_ != 1) throw std::invalid_argument("simulated_annealing: rule 0 or 1");
         if(detail::criterion_of<Eval>::value >= 0 && sampling_.sampling_size() != 0)
         {
-            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
             bn_anneal_params params{initial_temp, final_temp, decreasing_rate, boltzmann, same_state_max, max_proposals_, rule_, -1, 0, 0};
             last_winner_ = session.anneal(graph, max_parents_, params, chains_, seed_);
             sampling_.make_cpt(graph);

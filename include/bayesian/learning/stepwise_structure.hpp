@@ -149,7 +149,7 @@ private:
     template<class Inner, class Between>
     double on_session(graph_t& graph, std::vector<cluster_type>& clusters, Inner& inner, Between& between, std::true_type)
     {
-        detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+        detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
         for(auto const& cluster : clusters) inner.learn_on(session, graph, cluster);
         double score = std::numeric_limits<double>::max();
         while(clusters.size() != 1)

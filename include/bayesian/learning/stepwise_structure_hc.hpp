@@ -146,7 +146,7 @@ public:
         graph.erase_all_edge();
         if(resident && sampling_.sampling_size() != 0)
         {
-            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value);
+            detail::learner_session session(sampling_, graph, detail::criterion_of<Eval>::value, detail::criterion_of<Eval>::spec());
             last_winner_ = session.hc(graph, max_parents_, alpha, runs_, seed_);
             sampling_.make_cpt(graph);
             return session.score();

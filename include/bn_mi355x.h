@@ -626,6 +626,55 @@ int bn_learn_hc(bn_learner *L, bn_term_table *terms, const bn_hc_params *params,
                 const double *similarity, double *score_out, uint32_t *counts_out, uint64_t *masks_out, bn_hc_trace *trace_out,
                 int32_t *n_trace_out, int32_t *winner_out);
 
+/* ---- Bayesian-Dirichlet scores: BDeu and K2 (Cooper-Herskovits) as family terms of every search above ----
+ *
+ *   A bn_score_spec names the family term: kind 0 the log-likelihood term ll above (used with AIC / MDL), kind 2 BDeu with the
+ *   equivalent sample size ess, kind 3 K2 (ess not read).  Every *_spec entry point is the entry point of the same name with the
+ *   term chosen by the spec; a NULL spec or kind 0 gives the bits of the entry point without _spec.  Another kind, or a BDeu ess
+ *   that is not finite and within [2^-20, 2^20], is BN_ERR_ARG and nothing is launched.
+ *
+ *   lgamma_pos(x), finite x > 0, every operation a plain fp64 one (no fused multiply-add), log the DEVICE's fp64 log:
+ *     p = 1.0;  while (x < 16.0) { p = p * x;  x = x + 1.0; }                      (at most 16 steps)
+ *     r = 1.0 / x;  r2 = r * r;
+ *     s = c5; s = s * r2 + c4; s = s * r2 + c3; s = s * r2 + c2; s = s * r2 + c1; s = s * r2 + c0;  s = s * r;
+ *         c0 .. c5 = the doubles nearest 1/12, -1/360, 1/1260, -1/1680, 1/1188, -691/360360
+ *     v = (((x - 0.5) * log(x)) - x) + HALF_LOG_2PI + s;                          HALF_LOG_2PI = 0x3FED67F1C864BEB4 (0.9189385332046727)
+ *     return (the loop ran at least once) ? v - log(p) : v;
+ *
+ *   The term of a family with child arity kc, R parent configurations (all of them, observed or not) and E = R * kc entries in the
+ *   fitted layout:
+ *     BDeu: a_r = ess / double(R), a_c = ess / double(E);    K2: a_c = 1.0, a_r = double(kc);
+ *     G_r = lgamma_pos(a_r), G_c = lgamma_pos(a_c);
+ *     entry r (row j, state s) with count N and row total tot:  t_r = 0.0;
+ *       if N != 0:               t_r = lgamma_pos(a_c + double(N)) - G_c;
+ *       if s == 0 and tot != 0:  t_r = t_r + (G_r - lgamma_pos(a_r + double(tot)));
+ *     bd = the sum of the t_r in ll's order: 256 partial sums (partial t takes r = t, t + 256, ... from +0.0), folded by halves.
+ *   bd is the log marginal likelihood of the family's counts; like ll it is a function of the counts and the spec alone (same bits
+ *   alone, as a base, as a candidate, out of the subset lattice, in any batch, at any split).  The counts are the same exact N.
+ *
+ *   bn_learn_create_spec: criteria 0 and 1 take a NULL or kind-0 spec; criterion 2 (BDeu) a kind-2 spec, criterion 3 (K2) a kind-3
+ *   spec.  Under criteria 2 and 3 the score is the likelihood alone, no penalty:
+ *     likelihood = 0.0; for v = 0 .. n - 1: likelihood -= bd[v];  score = likelihood
+ *   that is MINUS the log marginal likelihood: smaller is better, and every "accept iff strictly smaller" rule above holds as it
+ *   stands (try_parents, best_parents, the brute-force searches, the chains' and runs' evaluation).  The parameter count is kept and
+ *   reported as before.  bn_learn_get also names "criterion".
+ *   bn_terms_create_spec: a term table of that term; bn_terms_get also names "score_kind" and "ess_bits" (the bits of ess; 0 for
+ *   kinds 0 and 3).  bn_learn_anneal and bn_learn_hc refuse (BN_ERR_ARG, before any launch) a table whose spec is not the
+ *   learner's: kinds equal and ess equal in bits; an AIC / MDL learner needs a kind-0 table. */
+typedef struct bn_score_spec {
+    int32_t kind;   /* 0 log-likelihood term, 2 BDeu, 3 K2 */
+    int32_t pad;
+    double ess;     /* BDeu's equivalent sample size */
+} bn_score_spec;
+int bn_learn_score_groups_spec(bn_info_table *table, const bn_score_spec *spec, int32_t n_groups, const int32_t *child,
+                               const int32_t *base_ptr, const int32_t *base_idx, const int32_t *cand_ptr, const int32_t *cand_idx,
+                               double *ll_out, uint64_t *counts_out);
+int bn_learn_score_subsets_spec(bn_info_table *table, const bn_score_spec *spec, int32_t child, int32_t n_base, const int32_t *base,
+                                int32_t m, const int32_t *cand, double *ll_out, uint64_t *counts_out);
+int bn_learn_create_spec(bn_info_table *table, const int32_t *in_ptr, const int32_t *in_idx, int32_t criterion,
+                         const bn_score_spec *spec, int32_t max_parents, bn_learner **out);
+int bn_terms_create_spec(bn_info_table *table, const bn_score_spec *spec, int32_t max_parents, bn_term_table **out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;

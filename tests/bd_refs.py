@@ -1,0 +1,351 @@
+"""Plain Python / libm restatement of the Bayesian-Dirichlet family terms of include/bn_mi355x.h (bn_score_spec: BDeu, K2), the
+bound B_bd between the device's term and this restatement, and the host loops the GPU tests compare the searches with.
+
+`lgamma_pos` is the header's function operation by operation; with math.log it differs from the device's only through the
+logarithm (device within 2 ulp, libm within 1).  DESIGN 4.15 derives, per lgamma_pos call at the shifted argument x',
+|device - restatement| <= 22u * M(x'), M(x') = |(x' - 1/2) * log x'| + x', and per family
+    B_bd = (K * u + gamma_{m+1}) * sum M,  K = 26,
+the sum taken over the lgamma_pos calls behind the family's non-zero terms (G_r and G_c once per term that uses them), m the
+number of non-zero terms.  K comes from that derivation, not from any GPU output.
+
+Under BDeu and K2 the learner's score is the likelihood alone.  learning_refs.score_arith has no such criterion, but "mdl" over a
+table of total 1 is exactly that: float(params) * (log2(1.0) / 2) = +0.0 and likelihood + 0.0 has the bits of likelihood.  `BDSearch`
+uses that, so the loops are learning_refs' and subset_refs' own, unchanged."""
+import math
+
+import numpy as np
+
+import anneal_refs as AR
+import learning_refs as LR
+import subset_refs as SS
+from loglik_refs import gamma
+
+U = 2.0 ** -53
+C = (1.0 / 12.0, -1.0 / 360.0, 1.0 / 1260.0, -1.0 / 1680.0, 1.0 / 1188.0, -691.0 / 360360.0)
+HALF_LOG_2PI = 0.9189385332046727
+K_CALL, K_BD = 22, 26
+ESS_MIN, ESS_MAX = 2.0 ** -20, 2.0 ** 20
+
+
+# ---- the function ------------------------------------------------------------------------------------
+
+def lgamma_pos(x, log=math.log):
+    """(value, M): the header's lgamma_pos and M(x') at the shifted argument."""
+    p, shifted = 1.0, False
+    while x < 16.0:
+        p = p * x
+        x = x + 1.0
+        shifted = True
+    r = 1.0 / x
+    r2 = r * r
+    s = C[5]
+    s = s * r2 + C[4]
+    s = s * r2 + C[3]
+    s = s * r2 + C[2]
+    s = s * r2 + C[1]
+    s = s * r2 + C[0]
+    s = s * r
+    lx = log(x)
+    v = (((x - 0.5) * lx) - x) + HALF_LOG_2PI + s
+    M = abs((x - 0.5) * math.log(x)) + x
+    return (v - log(p) if shifted else v), M
+
+
+class PerturbedLog:
+    """math.log moved by a random 0 .. +-3 ulp (fixed seed): what "device within 2 ulp, libm within 1" allows between the two."""
+
+    def __init__(self, seed):
+        self.rng = np.random.default_rng(seed)
+
+    def __call__(self, x):
+        y = math.log(x)
+        steps = int(self.rng.integers(-3, 4))
+        for _ in range(abs(steps)):
+            y = math.nextafter(y, math.inf if steps > 0 else -math.inf)
+        return y
+
+
+class Spec:
+    """kind 2: BDeu(ess); kind 3: K2."""
+
+    def __init__(self, kind, ess=0.0):
+        self.kind, self.ess = int(kind), float(ess) if kind == 2 else 0.0
+
+    def criterion(self):
+        from bayesiannetwork_amd.evaluation import BDeu, K2Score
+        return BDeu(self.ess) if self.kind == 2 else K2Score()
+
+    def alphas(self, kc, R):
+        """(a_r, a_c)."""
+        if self.kind == 2:
+            return self.ess / float(R), self.ess / float(R * kc)
+        return float(kc), 1.0
+
+    def __repr__(self):
+        return f"bdeu({self.ess!r})" if self.kind == 2 else "k2"
+
+
+BDEU1, BDEU10, BDEU_HALF, K2S = Spec(2, 1.0), Spec(2, 10.0), Spec(2, 0.5), Spec(3)
+SPECS = (BDEU1, BDEU10, BDEU_HALF, K2S)
+
+
+def bd_terms(N, kc, spec, log=math.log, memo=None):
+    """(t [E] in the fitted layout, sum of M over the calls behind the non-zero terms, number of non-zero terms)."""
+    N = np.asarray(N, dtype=np.uint64).reshape(-1, int(kc))
+    R = N.shape[0]
+    a_r, a_c = spec.alphas(int(kc), R)
+
+    def lg(x):
+        if memo is None:
+            return lgamma_pos(x, log)
+        if x not in memo:
+            memo[x] = lgamma_pos(x, log)
+        return memo[x]
+
+    (G_r, M_r), (G_c, M_c) = lg(a_r), lg(a_c)
+    tot = N.sum(axis=1, dtype=np.uint64)
+    t = np.zeros(N.shape)
+    mags = []
+    for j in np.nonzero(tot)[0]:
+        for s in np.nonzero(N[j])[0]:
+            v, M = lg(a_c + float(N[j, s]))
+            t[j, s] = v - G_c
+            mags += [M, M_c]
+        v, M = lg(a_r + float(tot[j]))
+        t[j, 0] = t[j, 0] + (G_r - v)
+        mags += [M, M_r]
+    return t.reshape(-1), math.fsum(mags), int(np.count_nonzero(t))
+
+
+def bd_bound(sum_M, m):
+    return (K_BD * U + gamma(m + 1)) * sum_M
+
+
+def bd_family(N, kc, spec, log=math.log, memo=None):
+    """(bd in the stated order, math.fsum of the terms, B_bd)."""
+    t, sum_M, m = bd_terms(N, kc, spec, log, memo)
+    return LR.sum256(t), math.fsum(t.tolist()), bd_bound(sum_M, m)
+
+
+class BDTable:
+    """A learning_refs.Table with a cache of restated Bayesian-Dirichlet family terms under one spec."""
+
+    def __init__(self, table, spec):
+        self.table, self.spec, self.k, self.n = table, spec, table.k, table.n
+        self._cache, self._memo = {}, {}
+
+    def family(self, child, parents):
+        key = (int(child), tuple(sorted(int(u) for u in parents)))
+        if key not in self._cache:
+            N = LR.family_counts(self.table.pats, self.table.counts, self.k, key[0], key[1])
+            self._cache[key] = bd_family(N, self.k[key[0]], self.spec, memo=self._memo)
+        return self._cache[key]
+
+    def term(self, child, parents):
+        return self.family(child, parents)[0]
+
+    def graph_bound(self, parents):
+        """Bounds |learner score - restated score| of a graph: the families' bounds, and the n subtractions on either side."""
+        b = math.fsum(self.family(v, ps)[2] for v, ps in enumerate(parents))
+        mag = math.fsum(abs(self.family(v, ps)[0]) for v, ps in enumerate(parents))
+        return b + 2 * gamma(self.n + 1) * mag
+
+
+# ---- the host loops -----------------------------------------------------------------------------------
+
+class BDSearch(SS.RefSearch):
+    """learning_refs.RefLearner / subset_refs.RefSearch with the likelihood alone as the score ("mdl" over a total of 1: the
+    penalty is +0.0).  record=True keeps try_parents' `decisions` as RefLearner does."""
+
+    def __init__(self, k, parents, term, max_parents=LR.MAX_PARENTS, record=False):
+        super().__init__(k, parents, "mdl", 1, term, max_parents, record)
+
+
+def likelihood_alone(ll):
+    likelihood = 0.0
+    for x in ll:
+        likelihood -= float(x)
+    return likelihood
+
+
+class BDProblem(AR.Problem):
+    """anneal_refs.Problem whose score is the likelihood alone (criteria 2 and 3)."""
+
+    def __init__(self, k, q, term, start=None):
+        super().__init__(k, q, "bd", 1, term, start)
+
+    def score(self, ll, params):
+        return likelihood_alone(ll)
+
+
+def bd_term_fn(bdt):
+    """term(child, parents) over a BDTable; NaN for a family over 2^20 entries."""
+    def term(child, parents):
+        if int(bdt.k[child]) * math.prod(int(bdt.k[u]) for u in parents) > AR.MAX_ENTRIES:
+            return math.nan
+        return bdt.term(child, parents)
+    return term
+
+
+# ---- margins -------------------------------------------------------------------------------------------
+
+def try_margins(bdt, L):
+    """Per recorded try_parents decision: (|score_next - score_now|, B(next) + B(now))."""
+    out = []
+    for child, u, now, nxt, _, parents in L.decisions:
+        after = [list(p) for p in parents]
+        after[child] = sorted(after[child] + [u])
+        out.append((abs(nxt - now), bdt.graph_bound(after) + bdt.graph_bound(parents)))
+    return out
+
+
+def best_parents_margins(bdt, L, child, cand):
+    """The comparisons bn_learn_best_parents makes for (child, cand) on L's current graph, BEFORE the call: every subset in
+    visiting order against the best so far.  (margin, bound) per comparison."""
+    surv, _ = L.survivors(child, cand)
+    out, best, best_S = [], None, None
+    for mask, score in L.subset_scores(child, surv).items():
+        S = [surv[j] for j in range(len(surv)) if (mask >> j) & 1]
+        if best is not None:
+            g_now, g_best = [list(p) for p in L.parents], [list(p) for p in L.parents]
+            g_now[child], g_best[child] = sorted(L.parents[child] + S), sorted(L.parents[child] + best_S)
+            out.append((abs(score - best), bdt.graph_bound(g_now) + bdt.graph_bound(g_best)))
+        if best is None or score < best:
+            best, best_S = score, S
+    return out
+
+
+def leaf_margins(bdt, start_parents, start_score, leaves):
+    """The comparisons of a literal enumeration (subset_refs.literal_hint / literal_brute_force): every leaf against the best so
+    far.  A leaf that IS the best graph so far has the best's bits on either side and is not a decision."""
+    out, best, best_g = [], start_score, [sorted(p) for p in start_parents]
+    for g, now in leaves:
+        if g != best_g:
+            out.append((abs(now - best), bdt.graph_bound(g) + bdt.graph_bound(best_g)))
+        if now < best:
+            best, best_g = now, g
+    return out
+
+
+def margins_ok(margins, factor=1000.0):
+    return all(m > factor * b for m, b in margins)
+
+
+# ---- the fixed inputs of the CPU and the GPU tests ------------------------------------------------------
+
+_INPUTS = {}
+
+
+def learner_input():
+    """(model, learning_refs.Table) for greedy, greedy with hint, K2 and best_parents: 12 nodes of arities 2, 3, 2, ... from
+    learning_refs' generators (synth.random_dag, sample_table)."""
+    if "learner" not in _INPUTS:
+        from bayesiannetwork_amd import synth
+        model = synth.random_dag(12, 3, 8, [2, 3, 2], seed=8)
+        _INPUTS["learner"] = (model, LR.sample_table(model, 3000, 23))
+    return _INPUTS["learner"]
+
+
+LEARNER_SPECS = (BDEU1, K2S)
+MAX_PARENTS = 4
+GREEDY_SEED, HINT_SEED, K2_SEED = 3, 31, 41
+K2_PRECONDITION = {3: [0, 1, 2], 10: [4]}
+HINT_PARENTS, HINT_CHILDREN = list(range(5)), list(range(5, 12))
+BEST_CALLS = [(11, [0, 3, 5, 7, 9]), (6, [1, 2, 4, 11, 10]), (2, [0, 1, 3])]   # on one learner, one after another
+
+
+def hint_orders(seed):
+    children = [HINT_CHILDREN[i] for i in np.random.default_rng(seed).permutation(len(HINT_CHILDREN))]
+    return children, [[HINT_PARENTS[j] for j in np.random.default_rng(seed + 1 + i).permutation(len(HINT_PARENTS))]
+                      for i in range(len(children))]
+
+
+def run_searches(make, bdt=None):
+    """Every learner search of the tests on learners from make(start parents): {name: (flags or result, parents, score)}.  With
+    `bdt` (host learners that record), also the margins of every decision under "margins"."""
+    model, _ = learner_input()
+    n = model.n
+    out, margins = {}, []
+    L = make(LR.empty_graph(n))
+    flags = LR.run_greedy(L, LR.greedy_orders(range(n), GREEDY_SEED))
+    out["greedy"] = ([[bool(x) for x in f] for f in flags], L.parents() if callable(L.parents) else L.parents, L)
+    L = make(LR.empty_graph(n))
+    flags = LR.run_hint(L, hint_orders(HINT_SEED))
+    out["hint"] = ([[bool(x) for x in f] for f in flags], L.parents() if callable(L.parents) else L.parents, L)
+    L = make(LR.empty_graph(n))
+    flags = LR.run_k2(L, LR.k2_children(n, K2_SEED), K2_PRECONDITION)
+    out["k2"] = ([(c, [bool(x) for x in f]) for c, f in flags], L.parents() if callable(L.parents) else L.parents, L)
+    L = make(LR.empty_graph(n))
+    taken = []
+    for child, cand in BEST_CALLS:
+        if bdt is not None:
+            margins += best_parents_margins(bdt, L, child, cand)
+        taken.append([bool(x) for x in L.best_parents(child, cand)])
+    out["best"] = (taken, L.parents() if callable(L.parents) else L.parents, L)
+    if bdt is not None:
+        for name in ("greedy", "hint", "k2"):
+            margins += try_margins(bdt, out[name][2])
+        out["margins"] = margins
+    return out
+
+
+def brute_input():
+    """(model, Table) for the brute-force searches: anneal_refs' n5 (arities 2, 3, 2, 4, 2)."""
+    return AR.anneal_input("n5")
+
+
+BRUTE_VERTEXES = [3, 0, 4, 1, 2]
+BRUTE_HINT_START = [[], [], [1], [], []]           # 1 -> 2: child 1 reaches parent node 2, so the hint search enumerates literally
+BRUTE_HINT = ([2, 0, 4], [1, 3])                   # parent nodes, child nodes
+
+
+# ---- the families of the term tests (CPU: the bound under a perturbed logarithm; GPU: the device against the restatement) ----
+
+# columns 0-16 binary; 17: k 3; 18: k 1; 19, 20: k 255; 21: k 17; 22: k 241; 23-27: k 16; 28: k 4; 29: k 5; 30: k 129
+KS = [2] * 17 + [3, 1, 255, 255, 17, 241] + [16] * 5 + [4, 5, 129]
+# 257 is prime and an arity is at most 255, so no family has 257 entries: the first size past 256 is 258 = 129 * 2.
+GROUPS = [
+    (17, [], []), (18, [], [17, 0]), (19, [], [0]),                # no parent: kc 3, 1, 255 (E = 255); kc 255 with rows that straddle a 256-entry step
+    (0, [], [1, 30]), (23, [24], []),                              # kc 2; E = 258 (129 * 2); E = 256 (16 * 16)
+    (17, [0], [18, 28]), (19, [18], [17]), (18, [17], [19]),       # one parent; a parent of arity 1; a child of arity 1; 3 rows of 255
+    (17, [0, 28], [1]),                                            # two parents
+    (16, list(range(16)), []),                                     # sixteen binary parents: 2^17 entries
+    (25, [23, 24], [0]),                                           # 4 096 entries; candidate: 8 192
+    (21, [22], []),                                                # 4 097
+    (27, [23, 24, 25, 26], []),                                    # 2^20: the cap
+    (17, [3, 9, 28], [0, 5, 16, 29]),                              # candidates below, between and above the base ids
+]
+TERM_CASES = [(1, SPECS), (2049, SPECS), (4097, (BDEU1, K2S))]      # (patterns, specs)
+SMALL_K = [4, 2]                                                    # counts 0, 1, 15, 16, 17 and an all-zero row (parent state 3)
+SMALL_PATS = np.array([[0, 1], [1, 0], [1, 1], [2, 0]], np.uint8)
+SMALL_COUNTS = np.array([1, 15, 16, 17], np.uint64)
+
+
+def term_weights(P, seed):
+    r = np.random.default_rng(seed)
+    return r.choice(np.array([1, 15, 16, 17, 127, (1 << 31) - 1, 1 << 31, 1 << 40], np.uint64), P)
+
+
+def term_table(P):
+    from pattern_refs import random_patterns
+    return random_patterns(KS, P, seed=P), term_weights(P, P + 1)
+
+
+def families_of(groups):
+    for c, b, us in groups:
+        yield c, list(b)
+        for u in us:
+            yield c, sorted(b + [u])
+
+
+# ---- chains and runs -------------------------------------------------------------------------------------
+
+ANNEAL = {   # name: (input, q, rule, t0, t1, rate, boltzmann, same_state_max, max_proposals, chains, seed)
+    "n5_met": ("n5", 2, "metropolis", 50.0, 0.5, 0.9, 1.0, 100, 1 << 20, 5, 5),
+    "n5_ref": ("n5", 2, "reference", 1e5, 1e3, 0.9, 1.0, 100, 1 << 20, 5, 3),
+    "n33_met": ("n33", 3, "metropolis", 20.0, 0.2, 0.8, 1.0, 100, 1 << 20, 257, 9),
+}
+HC = {       # name: (input, q, alpha, runs, seed)
+    "n5": ("n5", 2, 0.5, 257, 6),
+    "n33": ("n33", 3, 0.4, 5, 12),      # (the replay of a run of 33 nodes takes the host 70 ms: the 257 runs are n5's)
+}
