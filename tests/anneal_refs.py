@@ -154,10 +154,18 @@ class RefGraph:
     def in_vertexes(self, v):
         return [i for i in range(self.n) if self.adj[i][v] is not None]
 
-    def is_able_trace(self, a, b):   # graph.hpp:437
+    def is_able_trace(self, a, b, dead=None):   # graph.hpp:437
+        """The reference's depth-first walk.  It visits a node once per PATH that leads to it, which on the dense starting graphs
+        is more than 2^40 visits; `dead` holds the nodes a walk has already left without finding b.  The graph does not change
+        during a walk, so a second visit would fail as the first did: the same answer, in the same order, without the repeats."""
         if a == b:
             return True
-        return any(self.is_able_trace(c, b) for c in self.out_vertexes(a))
+        dead = set() if dead is None else dead
+        for c in self.out_vertexes(a):
+            if c not in dead and self.is_able_trace(c, b, dead):
+                return True
+        dead.add(a)
+        return False
 
     def edge_search(self, e):
         for i in range(self.n):
@@ -291,6 +299,7 @@ def restated_chain(pb, sched, seed, j, events=None):
     current, temperature = pb.score(ll, params), sched.t0
     no_changed = proposals = operated = accepted = 0
     trace, uphill = [], []
+    longest = len(lst)
 
     def reaches(masks, a, b):
         if a == b:
@@ -337,6 +346,11 @@ def restated_chain(pb, sched, seed, j, events=None):
                 note("no_edges")
                 continue
             at = rng.below(len(lst))
+            tail = len(lst) - 1 - at   # the entries the ordered erase moves down: the kernel moves 64 of them per round
+            if tail > 64:
+                note("erase_tail_gt64")
+            if tail > 128:
+                note("erase_tail_gt128")
             frm, to = lst.pop(at)
             without = list(pm)
             without[to] &= ~(1 << frm)
@@ -354,10 +368,13 @@ def restated_chain(pb, sched, seed, j, events=None):
                     note("reverse_refused")
                     if at != len(lst) - 1:
                         note("reverse_refused_moved")
+                        if len(lst) > 64:
+                            note("reverse_refused_moved_gt64")
                     continue
                 lst.append((to, frm))
             new[to] = (without[to], rows[to] // k[frm], pb.term(to, _parents_of(without[to])))
         operated += 1
+        longest = max(longest, len(lst))
         ll_new = [new[v][2] if v in new else ll[v] for v in range(n)]
         params_new = params + sum((k[v] - 1) * (new[v][1] - rows[v]) for v in new)
         now = pb.score(ll_new, params_new)
@@ -374,8 +391,12 @@ def restated_chain(pb, sched, seed, j, events=None):
                 pm[v], rows[v], ll[v] = mask, r, x
             params, current, no_changed = params_new, now, 0
             accepted += 1
+            if len(lst) > 64:      # the copies go 64 entries per trip
+                note("copy_gt64_accept")
             kept = list(lst)
         else:
+            if len(kept) > 64:
+                note("copy_gt64_reject")
             lst = list(kept)
             no_changed += 1
         note(("add_operated", "delete_operated", "reverse_operated")[method])
@@ -385,7 +406,7 @@ def restated_chain(pb, sched, seed, j, events=None):
         if flags & bit:
             note(name)
     return {"eval": current, "proposals": proposals, "operated": operated, "accepted": accepted, "flags": flags, "masks": pm,
-            "edges": lst, "trace": trace, "uphill": uphill, "ll": ll, "params": params}
+            "edges": lst, "trace": trace, "uphill": uphill, "ll": ll, "params": params, "longest_list": longest}
 
 
 def exp_margin_ok(uphill):
@@ -429,6 +450,15 @@ def libm_term(table):
 
 PATH64 = [[]] + [[v - 1] for v in range(1, 64)]   # 0 -> 1 -> ... -> 63
 
+
+def dense_start(n, degree):
+    """Node v has the up to `degree` nodes before it as parents: 186 edges at n = 64, 93 at n = 33 (degree 3)."""
+    return [list(range(max(0, v - degree), v)) for v in range(n)]
+
+
+DENSE64, DENSE33, DENSE33_2 = dense_start(64, 3), dense_start(33, 3), dense_start(33, 2)
+NEVER = 1 << 30   # a same_state_max no chain reaches
+
 # name: (input, q, criterion, rule, initial_temp, final_temp, rate, boltzmann, same_state_max, max_proposals, chains, seed, start)
 # The reference rule compares u with exp(-now / T): an uphill move needs a temperature of the order of the score, hence 1e4 .. 1e6.
 RUNS = {
@@ -446,12 +476,26 @@ RUNS = {
     "n64_path_met": ("n64", 2, "aic", "metropolis", 20.0, 0.2, 0.9, 1.0, 100, 1 << 20, 4, 11, PATH64),
     "n64_path_ref": ("n64", 2, "mdl", "reference", 1e6, 1e4, 0.9, 1.0, 100, 1 << 20, 5, 12, PATH64),
     "bigk_met": ("bigk", 3, "aic", "metropolis", 1e7, 1e5, 0.9, 1.0, 100, 1 << 20, 4, 13, None),
+    # Long lists: the ordered erase moves 64 entries per round and the accept / reject copies go 64 per trip, so a dense start
+    # (93 and 186 edges) puts tails of more than 64 and of more than 128 entries behind an erased edge.
+    "n64_dense_met": ("n64", 3, "aic", "metropolis", 20.0, 0.2, 0.999, 1.0, NEVER, 250, 4, 31, DENSE64),
+    "n64_dense_ref": ("n64", 3, "mdl", "reference", 1e6, 1e4, 0.98, 1.0, NEVER, 1 << 20, 4, 32, DENSE64),
+    "n33_dense_ref": ("n33", 3, "aic", "reference", 1e6, 1e4, 0.98, 1.0, NEVER, 1 << 20, 4, 33, DENSE33),
+    # the learner's bound (2) below the table's q (3): the refusal at in-degree 2 over rank tables sized for 3
+    "n33_bound2_over_q3": ("n33", 3, "mdl", "metropolis", 20.0, 0.2, 0.98, 1.0, NEVER, 1 << 20, 4, 34, DENSE33_2),
+    # Long chains: rate 0.9995, thousands of uphill decisions per chain.  (Every seed below passes exp_margin_ok on the CPU replay
+    # over libm's terms; the GPU test asserts it again over the device's.)
+    "n5_long_met": ("n5", 2, "aic", "metropolis", 50.0, 0.5, 0.9995, 1.0, NEVER, 1 << 20, 2, 35, None),
+    "n6_long_ref": ("n6", 3, "mdl", "reference", 1e5, 1e3, 0.9995, 1.0, NEVER, 1 << 20, 2, 36, None),
 }
+
+# the learner's in-degree bound of a run where it is below the table's q: the Problem's q is the bound
+MAX_PARENTS = {"n33_bound2_over_q3": 2}
 
 
 def run_setup(name, term=None):
     """(Problem, Schedule, chains, seed) of one row of RUNS; `term`: the family terms (default: libm over the input's table)."""
     inp, q, criterion, rule, t0, t1, rate, boltz, same, cap, chains, seed, start = RUNS[name]
     model, table = anneal_input(inp)
-    pb = Problem(table.k, q, criterion, table.total, term or libm_term(table), start)
+    pb = Problem(table.k, MAX_PARENTS.get(name, q), criterion, table.total, term or libm_term(table), start)
     return pb, Schedule(t0, t1, rate, boltz, same, rule, cap), chains, seed

@@ -344,8 +344,13 @@ ANNEAL = {   # name: (input, q, rule, t0, t1, rate, boltzmann, same_state_max, m
     "n5_met": ("n5", 2, "metropolis", 50.0, 0.5, 0.9, 1.0, 100, 1 << 20, 5, 5),
     "n5_ref": ("n5", 2, "reference", 1e5, 1e3, 0.9, 1.0, 100, 1 << 20, 5, 3),
     "n33_met": ("n33", 3, "metropolis", 20.0, 0.2, 0.8, 1.0, 100, 1 << 20, 257, 9),
+    "n33_dense_met": ("n33", 3, "metropolis", 20.0, 0.2, 0.98, 1.0, AR.NEVER, 1 << 20, 4, 61),   # from ANNEAL_START: a list of 93 edges
 }
+ANNEAL_START = {"n33_dense_met": AR.DENSE33}   # the starting graph of a row that has one (anneal_refs.dense_start)
 HC = {       # name: (input, q, alpha, runs, seed)
     "n5": ("n5", 2, 0.5, 257, 6),
     "n33": ("n33", 3, 0.4, 5, 12),      # (the replay of a run of 33 nodes takes the host 70 ms: the 257 runs are n5's)
+    "n33_nan_first": ("n33", 3, 0.5, 2, 62),    # a caller's matrix (HC_SIMILARITY): a NaN wins the first pick, every pair is kept
+    "n33_inf_sparse": ("n33", 3, 0.5, 3, 63),   # +inf among finite entries: p NaN, >= 1 and exactly 0; pairs cut and kept
 }
+HC_SIMILARITY = {"n33_nan_first": "nan_first", "n33_inf_sparse": "inf_sparse"}   # hc_refs.similarity_matrix kinds; else the mutual information

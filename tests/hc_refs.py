@@ -21,6 +21,15 @@ ONE_CLUSTER, NO_SIMILARITY = 1, 2
 bits = AR.bits
 
 
+def canonical_bits(b):
+    """The bits of a double as two machines can be asked to agree on them: every NaN reads as the one quiet NaN.  IEEE 754 leaves a
+    NaN's sign and payload to the implementation -- inf - inf is 0xFFF8... on x86 and 0x7FF8... on the GPU, and which of two NaN
+    operands an add hands on differs too -- and no step of the search can tell one NaN from another (every compare is false, every
+    sum is NaN).  Any other value keeps its bits, the sign of a zero included."""
+    b = int(b)
+    return 0x7FF8000000000000 if (b & 0x7FFFFFFFFFFFFFFF) > 0x7FF0000000000000 else b
+
+
 def _f(x):
     return np.float64(x)
 
@@ -258,9 +267,22 @@ def restated_run(pb, S, alpha, seed, j, events=None):
             sa.append(i), sb.append(r), sv.append(value)
     current = pb.score(ll, params)
     merges = tried = kept = pruned = pairs_kept = 0
-    merge_trace, prune_trace, decisions = [], [], []
+    merge_trace, prune_trace, decisions, exponents = [], [], [], []
     while len(clusters) != 1 and sa:
         best = first_maximum_keyed(sv)
+        if events is not None:   # what the pick had to decide: lane i % 64 scans the entries i, i + 64, ..., then the lanes are reduced
+            keys = [(math.inf if i == 0 else -math.inf) if v != v else v for i, v in enumerate(sv)]
+            again = [i for i in range(best + 1, len(sv)) if keys[i] == keys[best]]
+            if again and len(sv) > 64:
+                note("pick_tie_gt64")
+            if again and again[0] % 64 != best % 64:
+                note("pick_tie_other_lane")
+            if again and len(sv) > 64 and any(i % 64 == best % 64 for i in again):
+                note("pick_tie_same_lane")
+            if sv[0] != sv[0]:
+                note("pick_nan_index0")
+            if any(v != v for v in sv[1:]):
+                note("pick_nan_elsewhere")
         a, b, old_value = sa[best], sb[best], sv[best]
         coin = rng.below(2)
         parent, child = (b, a) if coin else (a, b)
@@ -312,26 +334,37 @@ def restated_run(pb, S, alpha, seed, j, events=None):
                 prune_trace.append((c, 0, bits(new_value), 0))
                 continue
             note("visit_%d" % len(conn))
-            p = _pow(alpha, _div(new_value, average) if len(conn) == 2 else _div(old_value, conn[0][1]))
+            exponent = _div(new_value, average) if len(conn) == 2 else _div(old_value, conn[0][1])
+            p = _pow(alpha, exponent)
             u = rng.uniform()
             decisions.append((u, p))
+            exponents.append(exponent)
+            if p != p:
+                note("p_nan")
+            elif p >= 1.0:
+                note("p_ge1")
+            elif p == 0.0:
+                note("p_zero")
             if u < p:
                 pruned += 1
+                note("pruned")
                 prune_trace.append((c, len(conn), bits(new_value), 1))
                 continue
             pairs_kept += 1
+            note("kept_pair")
             prune_trace.append((c, len(conn), bits(new_value), 0))
             sa.append(c), sb.append(new), sv.append(new_value)
     return {"score": current, "merges": merges, "tried": tried, "kept": kept, "pruned": pruned, "pairs_kept": pairs_kept,
             "flags": _flags(clusters, sa), "masks": pm, "merge_trace": merge_trace, "prune_trace": prune_trace,
-            "decisions": decisions, "ll": ll, "params": params,
+            "decisions": decisions, "exponents": exponents, "ll": ll, "params": params,
             "sims": [(x, y, bits(v)) for x, y, v in zip(sa, sb, sv)], "clusters": clusters}
 
 
-def cluster_plan(S, n, alpha, seed, j):
+def cluster_plan(S, n, alpha, seed, j, exponents=None):
     """The clustering alone, as the reference's loop does it when BetweenLearning draws from an engine of its own: the stream gives
     the coin and the pruning uniforms only, and no pick, merge or pruning depends on the edges learned.  Returns (the (parent
-    nodes, child nodes) of every learn_with_hint call in order, the (u, p) of every pruning decision)."""
+    nodes, child nodes) of every learn_with_hint call in order, the (u, p) of every pruning decision); `exponents`: a list that
+    takes every decision's exponent (what pow_margin_ok asks for)."""
     rng = AR.Stream(seed, j)
     nodes = {i: [i] for i in range(n)}
     clusters = list(range(n))
@@ -357,18 +390,41 @@ def cluster_plan(S, n, alpha, seed, j):
             new_value = make_similarity(S, nodes[new], nodes[c])
             if not joins:
                 continue
-            p = _pow(alpha, _div(new_value, average) if len(joins) == 2 else _div(old_value, joins[0][2]))
+            exponent = _div(new_value, average) if len(joins) == 2 else _div(old_value, joins[0][2])
+            p = _pow(alpha, exponent)
             u = rng.uniform()
             decisions.append((u, p))
+            if exponents is not None:
+                exponents.append(exponent)
             if not u < p:
                 sims.append((c, new, new_value))
     return calls, decisions
 
 
-def pow_margin_ok(decisions):
-    """The only arithmetic that may differ between the host and the device is pow: no pruning decision may have
-    |u - p| <= 2^-40 * max(u, p).  A NaN p keeps the pair on both sides (u < NaN is false)."""
-    return all(p != p or not abs(u - p) <= 2.0 ** -40 * max(u, p) for u, p in decisions)
+def pow_decision_clear(u, p, alpha, exponent):
+    """One pruning decision u < p with p = pow(alpha, exponent): can the device's pow decide it otherwise?
+      p is NaN        clear: u < NaN is false on both sides, the pair is kept
+      p >= 1          clear: the largest u is 1 - 2^-33, both sides prune (+inf included)
+      p == 0 exactly  clear BY EXACTNESS where 0 is one of pow's special cases: alpha = 0 with a positive exponent, or an infinite
+                      exponent -- both sides return the same 0
+      otherwise       |u - p| > 2^-40 * max(u, p).  A 0 from underflow is judged here and not above: the device may return a
+                      subnormal in its place, and the rule holds for either because the smallest u is 2^-33 (what was clear
+                      under this rule before the cases above were named stays clear)."""
+    if p != p or p >= 1.0:
+        return True
+    if p == 0.0 and ((alpha == 0.0 and exponent > 0.0) or math.isinf(exponent)):
+        return True
+    return not abs(u - p) <= 2.0 ** -40 * max(u, p)
+
+
+def pow_margin_ok(decisions, alpha=None, exponents=None):
+    """The only arithmetic that may differ between the host and the device is pow: EVERY pruning decision of a run (its (u, p)
+    and the exponent p came from) must be clear in the sense of pow_decision_clear.  Without the exponents only the NaN case and
+    the margin can be judged (an infinite p then reads as unclear)."""
+    if exponents is None:
+        return all(p != p or not abs(u - p) <= 2.0 ** -40 * max(u, p) for u, p in decisions)
+    assert len(decisions) == len(exponents)
+    return all(pow_decision_clear(u, p, alpha, x) for (u, p), x in zip(decisions, exponents))
 
 
 # ---- the fixed inputs of the CPU and the GPU tests --------------------------------------------------
@@ -417,10 +473,64 @@ def host_mi(table):
     return mi
 
 
+INF_TIES_PAIRS = ((1, 3), (4, 9), (8, 20), (15, 17), (20, 31))   # the +inf entries of "inf_ties" (n >= 32)
+INF_TIES_NAN = (0, 2)                                             # its NaN: index 1 of the initial list
+_KIND_IDS = {"sparse_nonfinite": 1, "nan_first": 1, "inf_ties": 2, "inf_sparse": 3}
+
+
+def list_index(n, x, y):
+    """Where the pair x < y sits in the initial list (row-major over the upper triangle)."""
+    return x * (2 * n - x - 1) // 2 + y - x - 1
+
+
+def _finite_entry(h):
+    """A dyadic value in (0, 1) from a hash word, negative one time in eight: exact in every divide by a power of two."""
+    v = (1 + (h >> 8) % 4093) / 4096.0
+    return -v if (h >> 24) % 8 == 0 else v
+
+
+def _nonfinite_matrix(kind, n):
+    """A pure function of (kind, n): Philox4x32-10 on (x, y, kind id, 0) under the key (n, 0) decides every pair x < y.
+      sparse_nonfinite  5 % NaN, 5 % +inf, 5 % -inf, else finite; S[0][1] finite
+      nan_first         the same matrix with S[0][1] = NaN: the NaN at index 0 of the initial list wins the first pick
+      inf_ties          finite but for +inf at INF_TIES_PAIRS (list indices in different lanes, more than 64 apart) and one NaN at
+                        index 1: the first +inf wins the first pick, its merge of 1 and 3 takes (0, 1) out of the list, and
+                        the NaN, now at index 0, wins the second
+      inf_sparse        5 % +inf, else finite; no NaN and no -inf, so the initial average is +inf and not NaN
+    Any NaN among the initial similarities (or +inf next to -inf) makes their average NaN, and then a visit with two connections
+    has p = pow(alpha, x / NaN) = NaN and keeps its pair -- unless alpha = 1, where pow gives 1 and every visit prunes.  Starting
+    from the complete list every visit has two connections until something is pruned, so under the first three kinds a run
+    keeps every pair (alpha != 1) or cuts every pair (alpha = 1).  inf_sparse is the matrix with non-finite entries whose runs
+    do both: finite / +inf = 0 gives p = 1 (prune), +inf / +inf = NaN keeps, and the visits with one connection that follow see
+    +inf / finite = +-inf: pow's exact 0 and +inf."""
+    S = np.zeros((n, n))
+    for x in range(n):
+        for y in range(x + 1, n):
+            h = AR.philox4x32_10((x, y, _KIND_IDS[kind], 0), (n, 0))
+            v = _finite_entry(h[1])
+            if kind in ("sparse_nonfinite", "nan_first"):
+                r = h[0] % 100
+                v = math.nan if r < 5 else math.inf if r < 10 else -math.inf if r < 15 else v
+            elif kind == "inf_sparse" and h[0] % 100 < 5:
+                v = math.inf
+            S[x][y] = S[y][x] = v
+    if kind == "sparse_nonfinite" and not math.isfinite(S[0][1]):
+        S[0][1] = S[1][0] = 0.5
+    elif kind == "nan_first":
+        S[0][1] = S[1][0] = math.nan
+    elif kind == "inf_ties":
+        for x, y in INF_TIES_PAIRS:
+            S[x][y] = S[y][x] = math.inf
+        S[INF_TIES_NAN[0]][INF_TIES_NAN[1]] = S[INF_TIES_NAN[1]][INF_TIES_NAN[0]] = math.nan
+    return S
+
+
 def similarity_matrix(kind, n, mi=None):
     """"mi": the mutual information; the others are a caller's matrix (symmetric in bits)."""
     if kind == "mi":
         return mi
+    if kind in _KIND_IDS:
+        return _nonfinite_matrix(kind, n)
     S = np.zeros((n, n))
     if kind == "zero":
         return S
@@ -458,13 +568,32 @@ RUNS = {
     "n5_ties": ("n5", 2, "aic", 0.5, 4, 14, "ties"),
     "n5_zero": ("n5", 2, "aic", 0.5, 4, 15, "zero"),
     "n5_negative": ("n5", 2, "mdl", 0.5, 8, 16, "negative"),
+    # Lists of more than 64 entries (528 at n = 33, 2 016 at n = 64), where a lane scans several strided entries and equal maxima
+    # sit in different lanes and in different slots of one lane; and a caller's non-finite matrices (_nonfinite_matrix), which
+    # put NaN, +-inf and 0 exponents through pow at alpha 0, 0.5, 1 and 2
+    "n33_ties": ("n33", 3, "aic", 0.5, 3, 40, "ties"),
+    "n64_ties": ("n64", 2, "mdl", 0.5, 2, 41, "ties"),
+    "n33_ties_alpha0": ("n33", 3, "mdl", 0.0, 2, 42, "ties"),
+    "n33_ties_bound2": ("n33", 3, "aic", 0.5, 2, 43, "ties"),
+    "n33_sparse": ("n33", 3, "aic", 0.5, 2, 44, "sparse_nonfinite"),
+    "n33_nan_first": ("n33", 3, "mdl", 0.5, 2, 45, "nan_first"),
+    "n33_inf_ties": ("n33", 3, "aic", 0.5, 2, 46, "inf_ties"),
+    "n33_sparse_alpha0": ("n33", 3, "mdl", 0.0, 2, 47, "sparse_nonfinite"),
+    "n33_sparse_alpha1": ("n33", 3, "aic", 1.0, 2, 48, "sparse_nonfinite"),
+    "n33_sparse_alpha2": ("n33", 3, "mdl", 2.0, 2, 49, "sparse_nonfinite"),
+    "n64_inf_ties": ("n64", 2, "aic", 0.5, 2, 50, "inf_ties"),
+    "n33_inf_sparse": ("n33", 3, "aic", 0.5, 3, 51, "inf_sparse"),
+    "n33_inf_sparse_alpha0": ("n33", 3, "mdl", 0.0, 2, 52, "inf_sparse"),
+    "n33_inf_sparse_alpha2": ("n33", 3, "aic", 2.0, 2, 53, "inf_sparse"),
 }
+NEW_ROWS = tuple(list(RUNS)[list(RUNS).index("n33_ties"):])   # the rows of the long lists and the non-finite matrices
 
 
 # the in-degree bound of a run where it is below the table's q.  On n6's samples no node ever earns a second parent (the largest
 # mutual information but one is 0.026 bits), so a refusal AT in-degree 2 cannot be shown there: the q = 2 run bounds the in-degree
 # at 1 over the q = 2 table, which is the kernel's other path -- the bound and the rank tables differ.
-MAX_PARENTS = {"n6_q2": 1}
+# n33 does earn second and third parents (the n33 row refuses at in-degree 3): its bounded row refuses at in-degree 2.
+MAX_PARENTS = {"n6_q2": 1, "n33_ties_bound2": 2}
 
 
 def run_setup(name, term=None, mi=None):

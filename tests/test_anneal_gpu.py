@@ -64,7 +64,7 @@ def test_term_table_n6_every_subset_mixed_arities(bnlib):
         check_entries(t, table, tt, q, families)
 
 
-@pytest.mark.parametrize("name,q", [("n33", 3), ("n64", 2)])
+@pytest.mark.parametrize("name,q", [("n33", 3), ("n64", 2), ("n64", 3)])
 def test_term_table_sampled_entries(bnlib, name, q):
     from bayesiannetwork_amd.learning import TermTable
     _, table = AR.anneal_input(name)
@@ -140,16 +140,17 @@ def run_on_device(name, chains=None, trace_chain=None):
     _, table = AR.anneal_input(inp)
     with info_table(table) as t, TermTable(t, q) as tt:
         rows = [tt.row(c) for c in range(table.n)]
-        with Learner(t, start, criterion) as L:
+        bound = {"max_parents": AR.MAX_PARENTS[name]} if name in AR.MAX_PARENTS else {}   # (below the table's q)
+        with Learner(t, start, criterion, **bound) as L:
             rec = L.anneal(tt, t0, t1, rate, boltz, same, chains, seed, rule, cap, trace_chain=trace_chain)
             after = (L.score(), L.terms(), L.parents(), L.info("anneal_chains"), L.info("anneal_steps"), L.info("anneal_ns"))
     pb, sched, _, _ = AR.run_setup(name, device_term(rows, table.n))
     return rec, pb, sched, chains, seed, after
 
 
-def replay(pb, sched, chains, seed):
+def replay(pb, sched, chains, seed, events=None):
     """The restated chains over the device's terms; the exp margin is checked on EVERY uphill decision before anything is compared."""
-    out = [AR.restated_chain(pb, sched, seed, j) for j in range(chains)]
+    out = [AR.restated_chain(pb, sched, seed, j, events) for j in range(chains)]
     for j, r in enumerate(out):
         assert AR.exp_margin_ok(r["uphill"]), f"chain {j}: an uphill decision within 2^-40 of its threshold: change the seed"
     return out
@@ -172,8 +173,20 @@ def compare(rec, want, trace_chain=None):
 def test_chains_equal_the_restated_chain_bit_for_bit(bnlib, name):
     trace_chain = AR.RUNS[name][10] - 1 if AR.RUNS[name][10] < 100 else 129
     rec, pb, sched, chains, seed, after = run_on_device(name, trace_chain=trace_chain)
-    want = replay(pb, sched, chains, seed)
+    events = {}
+    want = replay(pb, sched, chains, seed, events)
     compare(rec, want, trace_chain)
+    if name in ("n64_dense_met", "n64_dense_ref"):
+        # over the DEVICE's terms the chains still hold the long list and erase, accept and reject in it 64 entries at a time
+        assert all(events.get(key, 0) > 0 for key in ("erase_tail_gt64", "erase_tail_gt128", "copy_gt64_accept", "copy_gt64_reject",
+                                                      "reverse_refused_moved_gt64")), events
+        assert max(w["longest_list"] for w in want) >= 180
+    elif name == "n33_dense_ref":
+        assert all(events.get(key, 0) > 0 for key in ("erase_tail_gt64", "copy_gt64_accept", "copy_gt64_reject")), events
+    elif name == "n33_bound2_over_q3":
+        assert events.get("refused_q", 0) > 0 and all(bin(m).count("1") <= 2 for w in want for m in w["masks"])
+    elif name in ("n5_long_met", "n6_long_ref"):
+        assert all(w["flags"] == AR.END_TEMPERATURE and w["proposals"] > 10000 for w in want)
     # the winner: the strictly smallest evaluation, the lowest index among equals; the learner holds its graph and terms
     evals = [w["eval"] for w in want]
     winner = evals.index(min(evals))

@@ -263,10 +263,10 @@ def anneal_on_device(name, spec, chains=None, trace_chain=None):
     _, table = AR.anneal_input(inp)
     with info_table(table.pats, table.counts, table.k) as t, TermTable(t, q, crit) as tt:
         rows = [tt.row(c) for c in range(table.n)]
-        with Learner(t, None, crit) as L:
+        with Learner(t, BD.ANNEAL_START.get(name), crit) as L:
             rec = L.anneal(tt, t0, t1, rate, boltz, same, chains, seed, rule, cap, trace_chain=trace_chain)
             after = (L.score(), L.terms(), L.parents())
-    pb = BD.BDProblem(table.k, q, table_term(rows, table.n))
+    pb = BD.BDProblem(table.k, q, table_term(rows, table.n), BD.ANNEAL_START.get(name))
     return rec, pb, AR.Schedule(t0, t1, rate, boltz, same, rule, cap), chains, seed, after
 
 
@@ -275,7 +275,10 @@ def anneal_on_device(name, spec, chains=None, trace_chain=None):
 def test_chains_equal_the_restated_chain_bit_for_bit(bnlib, name, spec):
     trace_chain = 3 if BD.ANNEAL[name][9] < 100 else 129
     rec, pb, sched, chains, seed, after = anneal_on_device(name, spec, trace_chain=trace_chain)
-    want = [AR.restated_chain(pb, sched, seed, j) for j in range(chains)]
+    events = {}
+    want = [AR.restated_chain(pb, sched, seed, j, events) for j in range(chains)]
+    if name in BD.ANNEAL_START:   # the dense start: erases with a second round of 64, copies with a second trip
+        assert all(events.get(key, 0) > 0 for key in ("erase_tail_gt64", "copy_gt64_accept", "copy_gt64_reject")), events
     for j, w in enumerate(want):
         assert AR.exp_margin_ok(w["uphill"]), f"chain {j}: an uphill decision within 2^-40 of its threshold: change the seed"
     for j, w in enumerate(want):
@@ -320,23 +323,32 @@ def test_hc_runs_equal_the_restated_run_bit_for_bit(bnlib, name, spec):
     trace_run = min(runs - 1, 129)
     with info_table(table.pats, table.counts, table.k) as t, TermTable(t, q, crit) as tt:
         rows = [tt.row(c) for c in range(table.n)]
-        mi = t.pair_entropies()["mi"]
+        kind = BD.HC_SIMILARITY.get(name)
+        mi = HR.similarity_matrix(kind, table.n) if kind else t.pair_entropies()["mi"]
+        given = {"similarity": mi} if kind else {}
         with Learner(t, None, crit) as L:
-            rec = L.hc(tt, alpha, runs, seed, trace_run=trace_run)
+            rec = L.hc(tt, alpha, runs, seed, trace_run=trace_run, **given)
             score, (ll, _), parents = L.score(), L.terms(), L.parents()
-            fewer = [(n_runs, L.hc(tt, alpha, n_runs, seed)) for n_runs in (1, 5) if n_runs < runs]
+            fewer = [(n_runs, L.hc(tt, alpha, n_runs, seed, **given)) for n_runs in (1, 5) if n_runs < runs]
     pb = BD.BDProblem(table.k, q, table_term(rows, table.n))
-    want = [HR.restated_run(pb, mi, alpha, seed, j) for j in range(runs)]
+    events = {}
+    want = [HR.restated_run(pb, mi, alpha, seed, j, events) for j in range(runs)]
+    if kind == "nan_first":
+        assert events.get("pick_nan_index0", 0) > 0 and events["p_nan"] == events["kept_pair"] > 0 and events.get("pick_tie_other_lane", 0) > 0
+    elif kind == "inf_sparse":
+        assert all(events.get(key, 0) > 0 for key in ("pick_tie_other_lane", "p_nan", "p_ge1", "p_zero", "pruned", "kept_pair")), events
     for j, w in enumerate(want):
-        assert HR.pow_margin_ok(w["decisions"]), f"run {j}: a pruning decision within 2^-40 of its threshold: change the seed"
+        assert HR.pow_margin_ok(w["decisions"], alpha, w["exponents"]), f"run {j}: a pruning decision within 2^-40 of its threshold: change the seed"
     for j, w in enumerate(want):
         assert bits([rec["score"][j]])[0] == HR.bits(w["score"]), j
         got = tuple(int(rec[key][j]) for key in ("merges", "tried", "kept", "pruned", "pairs_kept", "flags"))
         assert got == (w["merges"], w["tried"], w["kept"], w["pruned"], w["pairs_kept"], w["flags"]), j
         assert [int(x) for x in rec["masks"][j]] == w["masks"], j
-    w = want[trace_run]
-    assert [(int(x.parent), int(x.child), int(x.value_bits), int(x.coin)) for x in rec["merge_trace"]] == w["merge_trace"]
-    assert [(int(x.cluster), int(x.connections), int(x.value_bits), int(x.pruned)) for x in rec["prune_trace"]] == w["prune_trace"]
+    w, cb = want[trace_run], HR.canonical_bits   # (a NaN's sign and payload are the machine's: hc_refs.canonical_bits)
+    assert [(int(x.parent), int(x.child), cb(x.value_bits), int(x.coin)) for x in rec["merge_trace"]] == \
+        [(p, c, cb(v), coin) for p, c, v, coin in w["merge_trace"]]
+    assert [(int(x.cluster), int(x.connections), cb(x.value_bits), int(x.pruned)) for x in rec["prune_trace"]] == \
+        [(c, k, cb(v), cut) for c, k, v, cut in w["prune_trace"]]
     scores = [w["score"] for w in want]
     winner = scores.index(min(scores))
     assert rec["winner"] == winner and bits([score])[0] == HR.bits(want[winner]["score"]) and score == BD.likelihood_alone(ll)

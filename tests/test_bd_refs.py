@@ -137,10 +137,10 @@ def test_brute_force_margins_and_the_one_class_that_cannot_have_them(spec):
 
 @pytest.mark.parametrize("spec", BD.LEARNER_SPECS, ids=repr)
 def test_the_literal_and_the_restated_chain_agree_under_the_likelihood_alone(spec):
-    for name in ("n5_met", "n5_ref"):
+    for name in ("n5_met", "n5_ref", "n33_dense_met"):
         inp, q, rule, t0, t1, rate, boltz, same, cap, chains, seed = BD.ANNEAL[name]
         _, table = AR.anneal_input(inp)
-        pb = BD.BDProblem(table.k, q, BD.bd_term_fn(BD.BDTable(table, spec)))
+        pb = BD.BDProblem(table.k, q, BD.bd_term_fn(BD.BDTable(table, spec)), BD.ANNEAL_START.get(name))
         sched = AR.Schedule(t0, t1, rate, boltz, same, rule, cap)
         operated = 0
         for j in range(chains):
@@ -155,12 +155,14 @@ def test_the_literal_and_the_restated_chain_agree_under_the_likelihood_alone(spe
 
 @pytest.mark.parametrize("spec", BD.LEARNER_SPECS, ids=repr)
 def test_the_literal_and_the_restated_hc_run_agree_under_the_likelihood_alone(spec):
-    inp, q, alpha, runs, seed = BD.HC["n5"]
-    _, table = AR.anneal_input(inp)
-    pb = BD.BDProblem(table.k, q, BD.bd_term_fn(BD.BDTable(table, spec)))
-    S = HR.host_mi(table)
-    for j in range(min(runs, 8)):
-        lit, res = HR.literal_run(pb, S, alpha, seed, j), HR.restated_run(pb, S, alpha, seed, j)
-        for key in ("score", "merges", "masks", "flags"):
-            assert lit[key] == res[key], (j, key)
-        assert HR.pow_margin_ok(res["decisions"]), j
+    for name in ("n5", "n33_nan_first", "n33_inf_sparse"):
+        inp, q, alpha, runs, seed = BD.HC[name]
+        _, table = AR.anneal_input(inp)
+        pb = BD.BDProblem(table.k, q, BD.bd_term_fn(BD.BDTable(table, spec)))
+        S = HR.similarity_matrix(BD.HC_SIMILARITY[name], table.n) if name in BD.HC_SIMILARITY else HR.host_mi(table)
+        for j in range(min(runs, 8)):
+            lit, res = HR.literal_run(pb, S, alpha, seed, j), HR.restated_run(pb, S, alpha, seed, j)
+            for key in ("score", "merges", "masks", "flags"):
+                a, b = lit[key], res[key]
+                assert (HR.bits(a) == HR.bits(b) if key == "score" else a == b), (name, j, key)
+            assert HR.pow_margin_ok(res["decisions"], alpha, res["exponents"]), (name, j)

@@ -70,8 +70,9 @@ def test_cpp_hc_both_paths_and_the_python_learner(bnlib, tmp_path):
         assert sorted((u, v) for v, ps in enumerate(L.parents()) for u in ps) == sorted(map(tuple, d["device"]["edges"]))
         assert L.score() == d["device"]["score"] and rec["winner"] == d["winner"]                     # bit for bit
         # the host path: the calls are the plan, and every edge runs from a call's parent list to its child list
-        calls, decisions = HR.cluster_plan(t.pair_entropies()["mi"], model.n, ALPHA, SEED, 0)
-        assert HR.pow_margin_ok(decisions), "a pruning decision within 2^-40 of its threshold: change SEED"
+        exponents = []
+        calls, decisions = HR.cluster_plan(t.pair_entropies()["mi"], model.n, ALPHA, SEED, 0, exponents)
+        assert HR.pow_margin_ok(decisions, ALPHA, exponents), "a pruning decision within 2^-40 of its threshold: change SEED"
         assert [(list(p), list(c)) for p, c in d["hint_calls"]] == calls and len(calls) > 1
         assert any(len(p) > 1 for p, _ in calls) and any(len(c) > 1 for _, c in calls)
         for u, v in d["host"]["edges"]:

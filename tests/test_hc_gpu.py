@@ -10,7 +10,11 @@ Two of the cases differ from their one-line statement, for reasons tests/hc_refs
 only where three nodes are all there is (t3_alpha1; on n5 the untouched clusters go on merging: n // 2 merges), and bigk's own 500
 samples never keep an edge between 255-state nodes, so the NaN refusal is shown on bigk_counts (the same arities, weighted
 patterns) while bigk itself is still compared bit for bit; n6 with q = 2 refuses at in-degree 1 over the q = 2 table (no node of
-n6 earns a second parent) and n33 shows the refusal at in-degree 3."""
+n6 earns a second parent) and n33 shows the refusal at in-degree 3.
+
+The rows of hc_refs.NEW_ROWS put lists of 528 and 2 016 entries with equal maxima through the pick (several strided entries per
+lane, ties across lanes) and a caller's NaN, +inf and -inf through the keys, the compaction and pow; for each the replay over the
+device's terms must still reach the forms the row exists for."""
 import math
 
 import numpy as np
@@ -58,7 +62,7 @@ def run_on_device(name, runs=None, trace_run=None):
 def replay(pb, S, alpha, runs, seed, events=None):
     out = [HR.restated_run(pb, S, alpha, seed, j, events) for j in range(runs)]
     for j, r in enumerate(out):
-        assert HR.pow_margin_ok(r["decisions"]), f"run {j}: a pruning decision within 2^-40 of its threshold: change the seed"
+        assert HR.pow_margin_ok(r["decisions"], alpha, r["exponents"]), f"run {j}: a pruning decision within 2^-40 of its threshold: change the seed"
     return out
 
 
@@ -69,9 +73,11 @@ def compare(rec, want, trace_run=None):
         assert got == (w["merges"], w["tried"], w["kept"], w["pruned"], w["pairs_kept"], w["flags"]), j
         assert [int(x) for x in rec["masks"][j]] == w["masks"], j
     if trace_run is not None:
-        w = want[trace_run]
-        assert [(int(x.parent), int(x.child), int(x.value_bits), int(x.coin)) for x in rec["merge_trace"]] == w["merge_trace"]
-        assert [(int(x.cluster), int(x.connections), int(x.value_bits), int(x.pruned)) for x in rec["prune_trace"]] == w["prune_trace"]
+        w, cb = want[trace_run], HR.canonical_bits   # (a NaN's sign and payload are the machine's: hc_refs.canonical_bits)
+        assert [(int(x.parent), int(x.child), cb(x.value_bits), int(x.coin)) for x in rec["merge_trace"]] == \
+            [(p, c, cb(v), coin) for p, c, v, coin in w["merge_trace"]]
+        assert [(int(x.cluster), int(x.connections), cb(x.value_bits), int(x.pruned)) for x in rec["prune_trace"]] == \
+            [(c, k, cb(v), cut) for c, k, v, cut in w["prune_trace"]]
 
 
 @pytest.mark.parametrize("name", list(HR.RUNS))
@@ -132,6 +138,35 @@ def test_runs_equal_the_restated_run_bit_for_bit(bnlib, name):
         assert {int(first.parent), int(first.child)} == {0, 2} and int(first.value_bits) == HR.bits(0.5)
     elif name == "n5_negative":
         assert S[0][n - 1] == -0.375 and all(w["merges"] >= 1 for w in want)
+    elif name in HR.NEW_ROWS:
+        # the replay over the DEVICE's terms still reaches what the row exists for (tests/test_hc_refs.py shows it over libm's)
+        kind = HR.RUNS[name][6]
+        assert events.get("pick_tie_gt64", 0) > 0 and events.get("pick_tie_other_lane", 0) > 0, events
+        if kind == "ties":
+            assert events.get("pick_tie_same_lane", 0) > 0
+            if alpha > 0:
+                assert all(events.get(key, 0) > 0 for key in ("pruned", "kept_pair", "visit_0", "visit_1", "visit_2")), events
+            else:
+                assert events["p_zero"] == events["kept_pair"] > 0 and all(int(x) == 0 for x in rec["pruned"])
+        if name in HR.MAX_PARENTS:
+            assert events.get("refused_q", 0) > 0 and all(bin(m).count("1") <= HR.MAX_PARENTS[name] for w in want for m in w["masks"])
+        if kind in ("sparse_nonfinite", "nan_first", "inf_ties"):
+            assert events.get("pick_nan_index0", 0) > 0 or alpha == 1.0
+            assert events.get("pick_nan_elsewhere", 0) > 0
+            if alpha == 1.0:   # pow(1, NaN) = 1: every visit prunes
+                assert events["p_ge1"] == events["pruned"] > 0 and all(int(x) == 0 for x in rec["pairs_kept"])
+            else:              # a NaN average: every visit keeps
+                assert events["p_nan"] == events["kept_pair"] > 0 and all(int(x) == 0 for x in rec["pruned"])
+                assert all(int(rec["merges"][j]) == n - 1 and int(rec["flags"][j]) == HR.ONE_CLUSTER | HR.NO_SIMILARITY for j in range(runs))
+        if kind == "nan_first":
+            first = rec["merge_trace"][0]
+            assert {int(first.parent), int(first.child)} == {0, 1} and HR.canonical_bits(first.value_bits) == HR.bits(math.nan)
+        if kind == "inf_ties":
+            first, second = rec["merge_trace"][0], rec["merge_trace"][1]
+            assert {int(first.parent), int(first.child)} == set(HR.INF_TIES_PAIRS[0]) and int(first.value_bits) == HR.bits(math.inf)
+            assert {int(second.parent), int(second.child)} == set(HR.INF_TIES_NAN) and HR.canonical_bits(second.value_bits) == HR.bits(math.nan)
+        if kind == "inf_sparse":
+            assert all(events.get(key, 0) > 0 for key in ("p_nan", "p_ge1", "p_zero", "pruned", "kept_pair", "visit_0", "visit_1", "visit_2")), events
     # the winner: the strictly smallest score, the lowest run among equals; the learner holds its graph and terms
     scores = [w["score"] for w in want]
     winner = scores.index(min(scores))

@@ -44,7 +44,8 @@ def test_literal_equals_restated_on_the_fixed_runs(name):
 def test_every_fixed_seed_keeps_its_pruning_decisions_off_the_threshold(name):
     pb, S, alpha, runs, seed = HR.run_setup(name)
     for j in range(runs):
-        assert HR.pow_margin_ok(HR.restated_run(pb, S, alpha, seed, j)["decisions"]), (name, j)
+        res = HR.restated_run(pb, S, alpha, seed, j)
+        assert HR.pow_margin_ok(res["decisions"], alpha, res["exponents"]), (name, j)
 
 
 def random_case(rng):
@@ -129,6 +130,31 @@ def test_the_draw_order_of_a_merge():
             assert g.uniform() == lit["decisions"][-1][0]
 
 
+def lane_strided_pick(values):
+    """The pick as 64 lanes make it: per lane the first largest key of its strided entries, then a butterfly over the lanes in
+    which the larger key wins and, among equal keys, the lower index."""
+    lanes = []
+    for lane in range(64):
+        best, best_key = None, 0.0
+        for i in range(lane, len(values), 64):
+            v = values[i]
+            key = (math.inf if i == 0 else -math.inf) if v != v else v
+            if best is None or key > best_key:
+                best, best_key = i, key
+        lanes.append((best, best_key))
+    off = 32
+    while off >= 1:
+        merged = []
+        for lane in range(64):
+            (best, best_key), (other, other_key) = lanes[lane], lanes[lane ^ off]
+            if other is not None and (best is None or other_key > best_key or (other_key == best_key and other < best)):
+                best, best_key = other, other_key
+            merged.append((best, best_key))
+        lanes, off = merged, off >> 1
+    assert len({b for b, _ in lanes}) == 1
+    return lanes[0][0]
+
+
 def test_first_maximum_takes_the_first_of_equal_maxima_and_treats_nan_as_the_loop_does():
     assert HR.first_maximum([1.0, 3.0, 3.0, 2.0]) == 1 == HR.first_maximum_keyed([1.0, 3.0, 3.0, 2.0])
     assert HR.first_maximum([0.5, 0.5, 0.5]) == 0 == HR.first_maximum_keyed([0.5, 0.5, 0.5])
@@ -139,6 +165,21 @@ def test_first_maximum_takes_the_first_of_equal_maxima_and_treats_nan_as_the_loo
     for _ in range(2000):
         values = [float(x) for x in rng.choice([nan, inf, -inf, 0.0, 0.25, 0.5, 1.0], int(rng.integers(1, 12)))]
         assert HR.first_maximum(values) == HR.first_maximum_keyed(values), values
+    # the kernel's form of the pick on lists of more than 64 entries: lane l takes the first maximum of the entries l, l + 64, ...
+    # (a later one replaces it only when strictly larger), then the lanes are merged pairwise, the lower index winning among equal
+    # keys.  With repeated maxima and +-inf it must give the index of std::max_element.
+    for _ in range(1500):
+        m = int(rng.integers(65, 301))
+        pool = [[inf, -inf, 0.25, 0.5], [inf, nan, 0.5], [-inf, nan], [0.5], [0.25, 0.5, 1.0, -0.375, 0.0, -0.0]][int(rng.integers(5))]
+        values = [float(x) for x in rng.choice(pool, m)]
+        top = float(rng.choice([inf, 1.0, 2.0]))
+        for i in rng.choice(m, int(rng.integers(2, 6)), replace=False):   # repeated maxima (or, under +inf in the pool, more of them)
+            values[int(i)] = top
+        want = HR.first_maximum(values)
+        assert HR.first_maximum_keyed(values) == want, values
+        assert lane_strided_pick(values) == want, values
+        keys = [(inf if i == 0 else -inf) if v != v else v for i, v in enumerate(values)]
+        assert keys.count(keys[want]) >= 2 or values[0] != values[0]
     # in a run: a caller's matrix of two values, the first pair in row-major order that holds the larger is merged first
     pb, S, alpha, runs, seed = HR.run_setup("n5_ties")
     res = HR.restated_run(pb, S, alpha, seed, 0)
@@ -217,3 +258,75 @@ def test_the_package_stream_is_the_library_stream():
         a, b = _Stream(seed, j), AR.Stream(seed, j)
         assert [a.next() for _ in range(8)] == [b.next() for _ in range(8)]
         assert [a.below(m) for m in (2, 3, 64)] == [b.below(m) for m in (2, 3, 64)] and a.uniform() == b.uniform()
+
+
+def _new_row_events():
+    out = {}
+    for name in HR.NEW_ROWS:
+        pb, S, alpha, runs, seed = HR.run_setup(name)
+        out[name] = ({}, [])
+        for j in range(runs):
+            out[name][1].append(HR.restated_run(pb, S, alpha, seed, j, out[name][0]))
+    return out
+
+
+def test_the_new_matrices_are_what_they_say():
+    nan_count = inf_count = 0
+    for kind in ("sparse_nonfinite", "nan_first", "inf_ties", "inf_sparse"):
+        for n in (33, 64):
+            S = HR.similarity_matrix(kind, n)
+            again = HR.similarity_matrix(kind, n)
+            assert np.array_equal(S.view(np.uint64), S.T.copy().view(np.uint64)) and np.array_equal(S.view(np.uint64), again.view(np.uint64))
+            upper = S[np.triu_indices(n, 1)]
+            share = [np.isnan(upper).mean(), np.isposinf(upper).mean(), np.isneginf(upper).mean()]
+            if kind in ("sparse_nonfinite", "nan_first"):
+                assert all(0.025 < x < 0.085 for x in share), (kind, n, share)
+                assert math.isfinite(S[0][1]) if kind == "sparse_nonfinite" else math.isnan(S[0][1])
+            elif kind == "inf_sparse":
+                assert share[0] == 0 and share[2] == 0 and 0.025 < share[1] < 0.085
+            else:
+                at = [HR.list_index(n, x, y) for x, y in HR.INF_TIES_PAIRS]
+                assert [i for i, v in enumerate(upper) if v == math.inf] == at                  # (row-major: the list's order)
+                assert len({i % 64 for i in at}) == len(at) and all(b - a > 64 for a, b in zip(at, at[1:]))
+                assert [i for i, v in enumerate(upper) if v != v] == [HR.list_index(n, *HR.INF_TIES_NAN)] == [1]
+            nan_count += int(np.isnan(upper).sum())
+            inf_count += int(np.isinf(upper).sum())
+    assert nan_count and inf_count
+
+
+def test_the_new_rows_reach_every_new_event():
+    """Together: ties among more than 64 entries, in another lane and in the same lane; NaN at index 0 and elsewhere at a pick;
+    p NaN, >= 1 and exactly 0; pruned and kept pairs; visits with 0, 1 and 2 connections; both endings."""
+    runs = _new_row_events()
+    total = {}
+    for events, _ in runs.values():
+        for key, count in events.items():
+            total[key] = total.get(key, 0) + count
+    wanted = ("pick_tie_gt64", "pick_tie_other_lane", "pick_tie_same_lane", "pick_nan_index0", "pick_nan_elsewhere", "p_nan", "p_ge1", "p_zero",
+              "pruned", "kept_pair", "visit_0", "visit_1", "visit_2", "refused_q")
+    assert all(total.get(key, 0) > 0 for key in wanted), total
+    flags = {r["flags"] for _, out in runs.values() for r in out}
+    assert HR.NO_SIMILARITY in flags and HR.ONE_CLUSTER | HR.NO_SIMILARITY in flags
+    # the rows of finite ties and the one non-finite matrix whose average is not NaN do both: cut and keep, every visit count
+    for name in ("n33_ties", "n64_ties", "n33_ties_bound2", "n33_inf_sparse", "n33_inf_sparse_alpha0", "n33_inf_sparse_alpha2"):
+        ev = runs[name][0]
+        assert all(ev.get(key, 0) > 0 for key in ("pruned", "kept_pair", "visit_0", "visit_1", "visit_2", "pick_tie_other_lane")), (name, ev)
+    for name in ("n33_inf_sparse", "n33_inf_sparse_alpha0", "n33_inf_sparse_alpha2"):
+        assert all(runs[name][0].get(key, 0) > 0 for key in ("p_nan", "p_ge1", "p_zero")), name
+    # a NaN among the initial similarities makes their average NaN: every visit keeps (alpha != 1) or prunes (alpha = 1: pow(1, NaN) = 1)
+    for name in ("n33_sparse", "n33_nan_first", "n33_inf_ties", "n33_sparse_alpha0", "n33_sparse_alpha2", "n64_inf_ties"):
+        ev, out = runs[name]
+        assert ev["p_nan"] == ev["kept_pair"] == ev["visit_2"] and not ev.get("pruned") and all(r["merges"] == len(r["masks"]) - 1 for r in out), name
+    ev, out = runs["n33_sparse_alpha1"]
+    assert ev["p_ge1"] == ev["pruned"] and not ev.get("kept_pair") and all(r["merges"] == len(r["masks"]) // 2 for r in out)
+    assert runs["n33_ties_alpha0"][0]["p_zero"] == runs["n33_ties_alpha0"][0]["kept_pair"] and not runs["n33_ties_alpha0"][0].get("pruned")
+    # the first picks the matrices were built for
+    first = {name: [r["merge_trace"][0] for r in out] for name, (_, out) in runs.items()}
+    assert all(HR.canonical_bits(v) == HR.bits(math.nan) and {p, c} == {0, 1} for p, c, v, _ in first["n33_nan_first"])
+    for name in ("n33_inf_ties", "n64_inf_ties"):
+        for r in runs[name][1]:
+            (p0, c0, v0, _), (p1, c1, v1, _) = r["merge_trace"][:2]
+            assert {p0, c0} == set(HR.INF_TIES_PAIRS[0]) and v0 == HR.bits(math.inf)     # the first +inf in list order
+            assert {p1, c1} == set(HR.INF_TIES_NAN) and HR.canonical_bits(v1) == HR.bits(math.nan)   # then the NaN, moved to index 0
+    assert runs["n33_ties_bound2"][0]["refused_q"] > 0 and all(bin(m).count("1") <= 2 for r in runs["n33_ties_bound2"][1] for m in r["masks"])
+    assert any(bin(m).count("1") == 2 for r in runs["n33_ties_bound2"][1] for m in r["masks"])
