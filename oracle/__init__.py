@@ -4,7 +4,8 @@ Only tests/, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg
 package.  ``bp_run`` / ``lw_run`` call the plain-C restatement in ``liboracle.so``
 (``bp_oracle.c`` / ``lw_oracle.c``); ``ref_bp`` / ``ref_lw`` execute ``_ref/ref_driver``,
 the unmodified reference headers compiled where they lie (exists only in the container
-that has ``/root/reference``).
+that has ``/root/reference``); ``ref_learn`` executes ``_ref/ref_learn_driver``, the reference's CPT fitting, AIC / MDL and
+structure searches compiled the same way.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 REF_DRIVER = os.path.join(_HERE, "_ref", "ref_driver")
+REF_LEARN_DRIVER = os.path.join(_HERE, "_ref", "ref_learn_driver")
 
 
 def build(quiet: bool = True) -> None:
@@ -123,7 +125,7 @@ def rs_run(model, ev_state, n_accept: int, seed: int, max_draw: int = 1 << 34, s
 
 
 def make_cpt(model, patterns, counts):
-    """Restated sampler::make_cpt (oracle_make_cpt; parity unpinned: the reference file needs Boost)."""
+    """Restated sampler::make_cpt (oracle_make_cpt; its bits are the reference's: tests/test_reference_learning_golden.py)."""
     L = lib()
     L.oracle_make_cpt.restype = ctypes.c_int
     patterns = np.ascontiguousarray(patterns, dtype=np.uint8).reshape(-1, model.n)
@@ -335,3 +337,41 @@ def ref_rs(model, cond_state, num: int, seed: int, timeout: float = 3600):
     """The reference's own rejection_sampling::operator(), engine reseeded mt19937(seed)."""
     text = model.to_bnflat_text() + f"rs {num} {seed}\n" + _pairs_text(cond_state)
     return _run_ref(text, timeout)
+
+
+# ---- the real reference's CPT fitting, scores and structure searches (ref_learn_driver.cpp) ----------
+
+def ref_learn_available() -> bool:
+    return os.path.exists(REF_LEARN_DRIVER)
+
+
+def ref_learn(k, parents, patterns, counts, command, timeout: float = 3600):
+    """One command of ``_ref/ref_learn_driver`` on the start graph `parents` (parent lists per node) over the pattern table
+    (`patterns` [P][n], `counts` [P]), which the reference reads through its own ``sampler::load_sample``.  `command`: the
+    tokens after the sample path (see ref_learn_driver.cpp), e.g. ``["greedy", "mdl", 7, "all"]`` or
+    ``["k2", "aic", 3, 1, 4, 2, 0, 1]``.  Returns the driver's JSON: ``cpt`` for make_cpt; for a search ``value``,
+    ``final_edges`` (flat parent, child pairs), ``evals`` (every graph the search had scored, in order, with the score) and
+    the calls stepwise_structure made to its inner and between learners."""
+    if not ref_learn_available():
+        raise RuntimeError(f"{REF_LEARN_DRIVER} is missing: it is built by `make -C oracle` only where the reference "
+                           "(oracle/Makefile's REF) is present")
+    k = [int(x) for x in k]
+    patterns = np.asarray(patterns).reshape(-1, len(k))
+    with tempfile.NamedTemporaryFile("w", suffix=".samples", delete=False) as f:
+        for row, c in zip(patterns.tolist(), np.asarray(counts).tolist()):
+            f.write(" ".join(str(int(x)) for x in [c] + row) + "\n")
+        samples = f.name
+    text = f"BNLEARN1 {len(k)}\n" + " ".join(map(str, k)) + "\n" + \
+        "".join(" ".join(str(int(x)) for x in [len(p)] + list(p)) + "\n" for p in parents) + samples + "\n" + \
+        " ".join(str(x) for x in command) + "\n"
+    with tempfile.NamedTemporaryFile("w", suffix=".bnlearn", delete=False) as f:
+        f.write(text)
+        path = f.name
+    try:
+        p = subprocess.run([REF_LEARN_DRIVER, path], capture_output=True, text=True, timeout=timeout)
+    finally:
+        os.unlink(path)
+        os.unlink(samples)
+    if p.returncode != 0:
+        raise RuntimeError(f"ref_learn_driver exit {p.returncode}: {p.stderr[-500:]}")
+    return json.loads(p.stdout)

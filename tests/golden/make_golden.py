@@ -2,11 +2,17 @@
 """Generate tests/golden/*.npz from the UNMODIFIED reference (oracle/_ref/ref_driver).
 
 Run in the container that has /root/reference:   python tests/golden/make_golden.py [--big]
+                                                  python tests/golden/make_golden.py --learning [--only n5]
 Each fixture is data only: the flat model (inputs), the evidence sets, and what the
 reference's own ``bn::inference::belief_propagation`` / ``likelihood_weighting`` returned
 (marginals, sweep count, per-sweep residual, for small graphs every final message).
 The teacher vectors of libs/bayesian/test/belief_propagation.cpp:67-72,96-101,186,211,234,
 259,282 are stored beside the reference's 17-digit outputs.
+
+--learning writes learn_<input>.npz instead: what the reference's own sampler::make_cpt, aic / mdl, greedy, k2_algorithm,
+brute_force and stepwise_structure (oracle/_ref/ref_learn_driver) did on the fixed inputs of tests/reference_learning.py --
+arities, patterns with counts, start graphs, seeds, preconditions, hints, the reference's CPTs, every graph its Eval was asked
+about with the returned double, final graphs and stepwise's calls.  Run times are printed, not stored: a rerun gives equal arrays.
 """
 from __future__ import annotations
 
@@ -225,12 +231,45 @@ def rs_cases():
                                "ref_marginals": np.concatenate([np.asarray(x) for x in r["marginals"]])})
 
 
+LEARNING_INPUTS = ("n5", "n6", "bd12", "alarm2k_mdl")
+
+
+def learning_cases(only=""):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reference_learning as RL
+    for name in LEARNING_INPUTS:
+        if only and only != name:
+            continue
+        table, specs = RL.run_specs(name)
+        d = {"k": table.k, "patterns": table.pats, "counts": table.counts, "n_runs": np.int32(len(specs))}
+        total = 0.0
+        for i, spec in enumerate(specs):
+            t = time.time()
+            out = oracle.ref_learn(table.k, spec["start"], table.pats, table.counts, RL.command_of(spec))
+            wall = time.time() - t
+            total += wall
+            if spec["kind"] == "make_cpt":
+                print(f"    {name} run{i} make_cpt: {len(out['cpt'])} entries ({out['run_s']:.3f}s)", flush=True)
+            else:
+                print(f"    {name} run{i} {spec['kind']} {spec['criterion']} seed={spec['seed']}: {len(out['evals'])} evaluations, "
+                      f"value {out['value']:.6f} ({out['run_s']:.2f}s)", flush=True)
+            for key, val in RL.pack_run(spec, out).items():
+                d[f"run{i}_{key}"] = val
+        path = os.path.join(OUT, f"learn_{name}.npz")
+        np.savez_compressed(path, **d)
+        print(f"  wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB), reference time {total:.1f}s", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also the minutes-long cases (32x32 grid, 1000-node DAG)")
     ap.add_argument("--only", default="")
+    ap.add_argument("--learning", action="store_true", help="write learn_*.npz (CPT fitting, AIC / MDL, the structure searches) and nothing else")
     a = ap.parse_args()
     oracle.build()
+    if a.learning:
+        learning_cases(a.only)
+        sys.exit(0)
     assert oracle.ref_available(), "oracle/_ref/ref_driver missing: /root/reference is needed"
     if a.only in ("", "tests"):
         reference_test_cases()

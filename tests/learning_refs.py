@@ -215,6 +215,29 @@ def graph_bound(table: Table, parents, criterion) -> float:
     return (8 * U + gamma(M + table.n + 2)) * (mags + abs(p))
 
 
+def reference_bound(table: Table, parents, criterion, vertexes=None) -> float:
+    """B_ref(G) = (8u + gamma_{M+n+2} + gamma_{M+2}) * (sum |t| + |p|): bounds |a score of this project (the learner's, or
+    score_arith over libm terms) - what the reference's aic / mdl return for G with the CPTs its make_cpt fits|.
+
+    graph_bound's gamma_{M+n+2} covers ONE computation whose terms each pass through at most M + n + 2 roundings (a family's
+    partial sums and folds, the n subtractions in node order, the penalty's product and addition); it compares two
+    computations only where the other side adds in the same stated order (AIC / MDL of evaluation.py do).  The reference
+    (basic_info_criteria.hpp:51-89) keeps ONE running sum over all M non-zero terms of all nodes, in the iteration order of
+    an unordered_map: an arbitrary order in which a term can pass through M - 1 additions, then the penalty's product and
+    its addition, so its own distance to the exact sum of the same terms is at most gamma_{M+2} * (sum |t| + |p|), whatever
+    the order.  The two errors add; 8u is graph_bound's allowance for the terms themselves (logarithm and product on either
+    side).  `vertexes`: the likelihood runs over these nodes only (eval_(graph, vertex_list)); the penalty is always the
+    whole graph's."""
+    mags, M = 0.0, 0
+    for v in (range(table.n) if vertexes is None else vertexes):
+        _, mag, m = table.family(int(v), parents[int(v)])
+        mags += mag
+        M += m
+    params = sum(family_params(table.k, v, ps) for v, ps in enumerate(parents))
+    p = float(params) * penalty_factor(criterion, table.total)
+    return (8 * U + gamma(M + table.n + 2) + gamma(M + 2)) * (mags + abs(p))
+
+
 def margins(table: Table, L: RefLearner):
     """Per recorded decision of the public-API loop: (|score_next - score_now|, B(next) + B(now))."""
     out = []
