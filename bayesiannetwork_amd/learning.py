@@ -21,6 +21,7 @@ candidate beyond them is not added; the returned model carries CPTs fitted to th
 the last rejected candidate in the graph); `seed=` / `orders=` make the shuffles reproducible."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -78,6 +79,23 @@ def _csr(lists):
     return ptr, idx
 
 
+@contextlib.contextmanager
+def _forced_splits(splits: int):
+    """BN_LEARN_SPLITS = splits for the calls inside (the library reads it per call); splits <= 0 leaves the environment alone."""
+    if splits <= 0:
+        yield
+        return
+    old = os.environ.get("BN_LEARN_SPLITS")
+    os.environ["BN_LEARN_SPLITS"] = str(int(splits))
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ["BN_LEARN_SPLITS"]
+        else:
+            os.environ["BN_LEARN_SPLITS"] = old
+
+
 def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0, criterion=None):
     """groups: [(child, base parents (strictly increasing), candidates), ...].  Returns per group the list of family terms
     [ll(base), ll(base + u_0), ...]; counts=True: (that, per group the list of uint64 count arrays in the fitted layout).
@@ -105,22 +123,13 @@ def score_groups(table: InfoTable, groups, counts: bool = False, splits: int = 0
         N = np.zeros(max(sum(map(sum, sizes)) if sizes else 1, 1), dtype=np.uint64)
         if sizes is not None and N.size > (1 << 28):
             raise ValueError("the counts of this batch need more than 2 GiB")
-    old = os.environ.get("BN_LEARN_SPLITS")
-    if splits > 0:
-        os.environ["BN_LEARN_SPLITS"] = str(int(splits))
-    try:
+    with _forced_splits(splits):
         args = (len(groups), _p(child, ctypes.c_int32), _p(bptr, ctypes.c_int32), _p(bidx, ctypes.c_int32), _p(cptr, ctypes.c_int32),
                 _p(cidx, ctypes.c_int32), _p(ll, ctypes.c_double), _p(N, ctypes.c_uint64) if counts else None)
         if spec is None:
             _lib.check(_lib.lib().bn_learn_score_groups(table._h, *args))
         else:
             _lib.check(_lib.lib().bn_learn_score_groups_spec(table._h, ctypes.byref(spec), *args))
-    finally:
-        if splits > 0:
-            if old is None:
-                del os.environ["BN_LEARN_SPLITS"]
-            else:
-                os.environ["BN_LEARN_SPLITS"] = old
     out, at = [], 0
     for c, b, u in groups:
         out.append(ll[at:at + 1 + len(u)].tolist())
@@ -159,22 +168,13 @@ def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False
         if total > (1 << 25):
             sizes, total = None, 1   # (over the limit: the library says so)
         N = np.zeros(max(total, 1), dtype=np.uint64)
-    old = os.environ.get("BN_LEARN_SPLITS")
-    if splits > 0:
-        os.environ["BN_LEARN_SPLITS"] = str(int(splits))
-    try:
+    with _forced_splits(splits):
         args = (int(child), len(base), _p(base, ctypes.c_int32), m, _p(cand, ctypes.c_int32), _p(ll, ctypes.c_double),
                 _p(N, ctypes.c_uint64) if counts else None)
         if spec is None:
             _lib.check(_lib.lib().bn_learn_score_subsets(table._h, *args))
         else:
             _lib.check(_lib.lib().bn_learn_score_subsets_spec(table._h, ctypes.byref(spec), *args))
-    finally:
-        if splits > 0:
-            if old is None:
-                del os.environ["BN_LEARN_SPLITS"]
-            else:
-                os.environ["BN_LEARN_SPLITS"] = old
     if not counts:
         return ll.tolist()
     blocks, at = [], 0

@@ -5,6 +5,8 @@
 #   * liboracle_san.so (make -C oracle SAN=1): the checker, exercised by tests/test_oracle_golden.py;
 #   * the header-only drop-in (flatten, DSC loader) in tests/cpp/test_dropin.cpp --flatten / --dsc ... --flatten, over include/compat and,
 #     where /root/reference exists, over the reference's own graph.hpp / matrix.hpp / serializer.
+#   * the learner's host-only planner (bn_learn_plan.cpp: families, chunks, passes, launch order, lattice steps) in
+#     tests/cpp/test_learn_plan.cpp, a program of its own over seeded random batches with scratch limits of a few hundred cells.
 # No GPU is touched and none is needed (GPU sanitizers do not exist on this pool).  Log: the first argument, default profiles/san_cpu.log.
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -37,6 +39,10 @@ echo "== bench_dropin --checksum (graph_t / cpt_t construction of BASELINE confi
 g++ -std=c++14 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I include -I include/compat \
     tests/cpp/bench_dropin.cpp -L bayesiannetwork_amd -lbn_mi355x_san -Wl,-rpath,$ROOT/bayesiannetwork_amd -Wl,-rpath,/opt/rocm/lib -o build/san/bench_dropin \
     && build/san/bench_dropin --checksum > /dev/null && echo "   ok" || { echo "FAILED: bench_dropin --checksum"; rc=1; }
+echo "== tests/cpp/test_learn_plan.cpp with bn_learn_plan.cpp (the learner's planner on random batches, many passes)"
+g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I bayesiannetwork_amd/csrc -I include \
+    tests/cpp/test_learn_plan.cpp bayesiannetwork_amd/csrc/bn_learn_plan.cpp -o build/san/test_learn_plan \
+    && build/san/test_learn_plan > /dev/null && echo "   ok" || { echo "FAILED: test_learn_plan"; rc=1; }
 echo "== result: $([ $rc = 0 ] && echo CLEAN || echo FAILED)"
 } 2>&1 | tee "$LOG"
 grep -q "== result: CLEAN" "$LOG"

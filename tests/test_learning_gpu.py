@@ -356,3 +356,70 @@ def test_error_paths_name_the_group(bnlib):
             # the over-limit candidate is skipped, not an error: 27 <- 23, 24, 25, 26 is at the cap
         with Learner(t, [[]] * 27 + [[23, 24, 25, 26]] + [[]] * 2, "aic") as L:
             assert L.try_parents(27, [0, 28]).tolist() == [False, False] and L.info("passes") == 1
+
+
+# ---- a batch whose passes cut THROUGH its groups ----------------------------------------------------
+
+def _passes_of(ks, groups):
+    """The pass of every family of a batch, family by family in input order, by the rule bn_learn.hpp states: a family of at most
+    4 096 cells is counted in LDS (chunks of <= 32 candidates and <= 4 096 cells), the others in device memory (chunks of <= 8
+    candidates); a group's LDS chunks come first; a pass is a run of whole chunks of at most 2^25 cells."""
+    chunks = []                                                              # (cells, [family indices])
+    fam = 0
+    for c, b, us in groups:
+        base = ks[c] * math.prod(ks[x] for x in b)
+        cells = [base] + [base * ks[u] for u in us]
+        for lds in (True, False):
+            cur = None
+            for j, x in enumerate(cells):
+                if (x <= 4096) != lds:
+                    continue
+                n_cand = sum(1 for f in cur[1] if f != fam) if cur else 0
+                if cur is None or n_cand >= (32 if lds else 8) or (lds and cur[0] + x > 4096):
+                    cur = [0, []]
+                    chunks.append(cur)
+                cur[0] += x
+                cur[1].append(fam + j)
+        fam += len(cells)
+    passes, at, p = [0] * fam, 0, 0
+    for cells, fams in chunks:
+        if at > 0 and at + cells > (1 << 25):
+            p, at = p + 1, 0
+        at += cells
+        for f in fams:
+            passes[f] = p
+    return passes
+
+
+def test_a_group_scored_by_more_than_one_pass_has_the_bits_of_its_families_scored_alone(bnlib):
+    """200 patterns over 120 variables: 0-9 of arity 4 (1-9 mostly in state 0, so that rows hold several patterns), 10-49 of
+    arity 1, 50-83 of arity 255 (three states in use), 84-119 of arity 4.  One call scores three groups of child 0:
+    A: base 1..9 (4^10 = 2^20 cells, exactly the per-family limit) and the 40 candidates of arity 1: 41 families of 2^20 cells in
+       device-memory chunks of 9, 8, 8, 8, 8 families; the 2^25-cell scratch ends the first pass after A's third chunk.
+    B: base 1..5 (4 096 cells, the last LDS size), candidates alternately of arity 1 (LDS chunks, which come first) and of arity
+       255 (1 044 480 cells, device memory): a pass ends inside B's device-memory chunks, so B's families do NOT go to the passes
+       in input order and their scores come back through the reorder.
+    C: base 1..8 (2^18 cells) and 37 candidates of arity 4 (2^20 cells each, every one another function of the data).
+    Five passes; each group has families in two of them.  Expected: every family as a group of its own, one pass each."""
+    from bayesiannetwork_amd.learning import score_groups
+    ks = [4] * 10 + [1] * 40 + [255] * 34 + [4] * 36
+    A = (0, list(range(1, 10)), list(range(10, 50)))
+    B = (0, list(range(1, 6)), flat([[10 + j, 50 + j] for j in range(34)]))
+    C = (0, list(range(1, 9)), [9] + list(range(84, 120)))
+    groups = [A, B, C]
+    passes = _passes_of(ks, groups)
+    pa, pb, pc = passes[:41], passes[41:110], passes[110:]
+    assert len(pc) == 38 and max(passes) + 1 >= 2 and all(len(set(p)) >= 2 for p in (pa, pb, pc))
+    assert pa == sorted(pa) and pb != sorted(pb)                             # A goes in input order; B is reordered
+    alone = [(c, p, []) for c, p in families_of(groups)]
+    assert all(max(_passes_of(ks, [g])) == 0 for g in alone)
+    r = np.random.default_rng(41)
+    pats = random_patterns(ks, 200, seed=42)
+    pats[:, 1:10] *= (r.random((200, 9)) < 0.2).astype(np.uint8)
+    pats[:, 50:84] = 100 * r.integers(0, 3, (200, 34)).astype(np.uint8)
+    with info_table(pats, weights(200, 43), ks) as t:
+        got = score_groups(t, groups)
+        want = [score_groups(t, [g])[0][0] for g in alone]
+        assert [len(x) for x in got] == [41, 69, 38]
+        assert np.array_equal(bits(flat(got)), bits(want))
+        assert len(set(bits(want).tolist())) >= 60                           # (a misplaced score would show: the families differ)
