@@ -232,9 +232,9 @@ static int enqueue_batch_resident_chunk(bn_engine* e, double eps, int32_t max_sw
         bt.gen_base = 0;
     }
     ResidentArgs a{batch_buffers_of(e, first), eps, max_sweeps, begin, kResidentBudget, e->run_id, bt.gen_base, 5000000ull, bt.d_sync,
-                   bt.h_ctl_dev + first, e->grid_resident, e->resident_waves, count, mask, p.rec_total_doubles, p.node_doubles,
+                   bt.h_ctl_dev + first, e->shape.blocks, e->shape.waves, count, mask, p.rec_total_doubles, p.node_doubles,
                    int64_t(std::max(p.n_slots, 1)), p.node_off[p.n], e->res_cap, nullptr, nullptr, nullptr, 0, nullptr, 1, 0, e->h_abort_dev};
-    if (int code = launch_bp_resident(a, e->grid_resident + resident_service_blocks(e->grid_resident), e->resident_lean, s))
+    if (int code = launch_bp_resident(a, e->shape.blocks + resident_service_blocks(e->shape.blocks), e->shape.lean, s))
         return fail(BN_ERR_HIP, std::string("bp_resident launch failed: ") + hipGetErrorString(hipError_t(code)));
     bt.gen_base += kResidentBudget + 1;
     return BN_OK;
@@ -267,8 +267,7 @@ static int collect_batch_resident_chunk(bn_engine* e, int32_t first, int32_t cou
 static int run_batch_resident(bn_engine* e, double eps, int32_t max_sweeps) {
     bn_engine::Batch& bt = e->batch;
     hipStream_t s = e->stream;
-    ++e->run_id;
-    if (e->run_id == 0) e->run_id = 1;
+    next_run_id(e);
     int32_t launches = 0;
     double dev_ticks = 0.0;
     float ms = 0.f;
@@ -340,8 +339,7 @@ static int run_batch_launches(bn_engine* e, double eps, int32_t max_sweeps) {
     bn_engine::Batch& bt = e->batch;
     const Plan& p = e->plan;
     hipStream_t s = e->stream;
-    ++e->run_id;
-    if (e->run_id == 0) e->run_id = 1;
+    next_run_id(e);
     const int32_t B = bt.n_sets;
     if (!bt.rows_clean) {  // an earlier batched run did not end through its finish kernel
         for (int32_t q = 0; q < bt.cap_sets; ++q)
@@ -399,8 +397,7 @@ static int run_batch_small(bn_engine* e, double eps, int32_t max_sweeps) {
     bn_engine::Batch& bt = e->batch;
     const Plan& p = e->plan;
     hipStream_t s = e->stream;
-    ++e->run_id;
-    if (e->run_id == 0) e->run_id = 1;
+    next_run_id(e);
     const int32_t B = bt.n_sets;
     const SetStrides st{p.rec_total_doubles, p.node_doubles, int64_t(std::max(p.n_slots, 1)), p.node_off[p.n], e->res_cap};
     const int64_t state_stride = 2 * int64_t(e->small.M) + 2 * int64_t(e->small.N);
@@ -463,8 +460,7 @@ static int run_batch_small(bn_engine* e, double eps, int32_t max_sweeps) {
 static int run_batch_mid(bn_engine* e, double eps, int32_t max_sweeps) {
     bn_engine::Batch& bt = e->batch;
     const Plan& p = e->plan;
-    ++e->run_id;
-    if (e->run_id == 0) e->run_id = 1;
+    next_run_id(e);
     const int32_t B = bt.n_sets, nparts = int32_t(e->mid.parts.size());
     const int32_t per_launch = std::max(1, std::min(B, (e->n_cus * 9 / 10) / nparts));
     int rc;
@@ -592,8 +588,7 @@ static int enqueue_batch_dag_chunk(bn_engine* e, double eps, int32_t max_sweeps,
         bt.dag_sync_dirty = false;
         bt.dag_gen_base = 0;
     }
-    ++e->run_id;
-    if (e->run_id == 0) e->run_id = 1;
+    next_run_id(e);
     chunk = DagChunk{first, count, e->run_id};
     DagArgs a{};
     a.b = buffers_of(e);
@@ -738,7 +733,7 @@ static bool batch_mid_wanted(const bn_engine* e) { return !batch_small_wanted(e)
 static bool batch_resident_wanted(const bn_engine* e) {
     constexpr int64_t kResidentBatchMinTiles = 900;
     if (batch_small_wanted(e)) return false;
-    return e->resident_ok && (e->multisweep == 2 || (e->multisweep == 1 && int64_t(e->plan.tiles.size()) >= kResidentBatchMinTiles));
+    return e->shape.resident_ok && (e->multisweep == 2 || (e->multisweep == 1 && int64_t(e->plan.tiles.size()) >= kResidentBatchMinTiles));
 }
 static int run_batch_small_d(bn_engine* e, double eps, int32_t max_sweeps, double*) { return run_batch_small(e, eps, max_sweeps); }
 static int run_batch_dag_d(bn_engine* e, double eps, int32_t max_sweeps, double*) { return run_batch_dag(e, eps, max_sweeps); }

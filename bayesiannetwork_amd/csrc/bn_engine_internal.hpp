@@ -1,8 +1,11 @@
 // bn_engine_internal.hpp -- what the translation units of the C ABI (include/bn_mi355x.h) share: the engine object and the helpers
-// that more than one of them uses.  bn_engine.cpp: creation, evidence, the run of a single query (steps, the one-launch paths and
-// their dispatch), options, read-out; bn_engine_batch.cpp: several evidence sets per call; bn_engine_shard.cpp: RCCL communicator
-// and the in-kernel exchange of sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and
-// the fit's entry points.  No CPU compute path exists in any of them: every result comes from the kernels.
+// that more than one of them uses.  bn_engine.cpp: evidence, the steps of a run with one launch per sweep, options, info, read-out,
+// messages; bn_engine_create.cpp: bn_create / bn_destroy, the device set-up one step per path, the stream pool, ensure_dag;
+// bn_engine_paths.cpp: the one-launch paths of a single query, their dispatch (run_device_impl) and "autotune";
+// bn_engine_policy.hpp / .cpp: which path runs a query, as pure host functions of a few facts (no HIP: checked stand-alone on a
+// CPU); bn_engine_batch.cpp: several evidence sets per call; bn_engine_shard.cpp: RCCL communicator and the in-kernel exchange of
+// sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and the fit's entry points.  No
+// CPU compute path exists in any of them: every result comes from the kernels.
 #ifndef BN_ENGINE_INTERNAL_HPP
 #define BN_ENGINE_INTERNAL_HPP
 #include <hip/hip_runtime_api.h>
@@ -29,6 +32,7 @@
 #include "bn_small.hpp"
 #include "bn_dag.hpp"
 #include "bn_buffer.hpp"
+#include "bn_engine_policy.hpp"
 
 using namespace bnmi;
 
@@ -162,7 +166,8 @@ struct bn_engine {
     bool nontemporal = false;
     bool timing = false;            // HIP events around each batch of sweeps (bn_bp_stats.sweep_kernel_ms); opt-in:
                                     // an event record between two launches opens a ~6 us bubble in the queue
-    bool resident_ok = false;       // every tile register-resident and co-resident: the whole run in one launch (bn_resident.hip)
+    bn_policy::PathFacts facts;     // what the path choice reads of the plans below (path_facts_of: bn_create, and wherever a plan is rebuilt)
+    bn_policy::ResidentShape shape; // the resident kernel's launch shape and eligibility on this device (plan_resident, at bn_create)
     // A launch of the resident kernel that gives up a bounded wait (its blocks were not all co-resident: another
     // process or engine held CUs) sends this and the next `resident_cooldown` runs down the per-sweep launches;
     // after that the resident path is tried again, and a repeated abort doubles the pause (<= 1024 runs).
@@ -179,16 +184,12 @@ struct bn_engine {
     std::vector<uint32_t> ev_seen;  // check_evidence: epoch stamp per node (no per-call allocation)
     uint32_t ev_epoch = 0;
     bool ev_upload_pending = false; // an evidence H2D from h_ev may still be in flight (no sync since)
-    int resident_lean = 0;          // ... and every node has this arity (2, 3 or 4) and <= 2 children; else 0
-    int grid_resident = 0;
-    int resident_waves = kResidentWaves;  // tiles per block of the resident kernel (8, or 4 on networks small enough)
     int resident_poll_margin = 30;  // direct form: 10 ns ticks between the predicted arrival of the last block and a block's first poll (BN_RESIDENT_DELAY)
     int resident_direct = 1;        // option "direct" / BN_RESIDENT_DIRECT: the grid barrier without a service block (bn_resident.hip wait_verdict);
                                     // measured against the service block, us per sweep: 32 x 32 grid 6.98 -> 6.46, 128 x 128 7.25 -> 6.80, 316 x 316 11.46 -> 11.04
     DeviceBuf<ResidentSync> d_rsync;
     bool rsync_dirty = true;        // the sync block must be zeroed before the next launch
     // dataflow form of the resident kernel (no grid barrier; single evidence set, more than one tile block)
-    bool flow_ok = false;           // every tile has <= 64 neighbour tiles
     int poll_sleep = 2;             // option "poll_sleep" / BN_POLL_SLEEP: pause between two polls of a waiting tile (x 512 cycles)
     int flow = 0;                   // option "flow" / BN_RESIDENT_FLOW: 1 = dataflow form where eligible, 0 = grid barrier per sweep
                                     // (the default on one GPU: measured equal per sweep, and the lagging stop decision costs one
@@ -198,7 +199,6 @@ struct bn_engine {
     uint32_t flow_gen_base = 0;
     DeviceBuf<int32_t> d_nbr;
     // sharded engines: halo exchange inside the resident kernel (bn_peer_export / bn_peer_import)
-    bool shard_shapes_ok = false;   // this shard's tiles are what the resident kernel runs (uniform arity, <= 2 parents, <= 8 children)
     bool shard_flow_ok = false;     // ... on every rank, and the peers' buffers are mapped: the dataflow form exchanges in-kernel
     bool fine_grained = false;      // record buffers / sync block allocated fine-grained (peers store into them)
     uint32_t shard_run_seq = 0;     // bn_bp_run_device calls on this sharded engine: every rank counts alike -> same generations
@@ -376,6 +376,13 @@ inline int dalloc(DeviceBuf<T>& dst, size_t count) {
 }
 
 
+bn_policy::PathFacts path_facts_of(const Plan& p, const SmallPlan& small, const MidPlan& mid, const DagPlan& dag);
+inline bn_policy::PathOks oks_of(const bn_engine* e) { return {e->small_ok, e->mid_ok, e->dag_ok, e->shard_flow_ok}; }
+inline bn_policy::PathModes modes_of(const bn_engine* e) { return {e->multisweep, e->small_mode, e->mid_mode, e->dag_mode}; }
+inline void next_run_id(bn_engine* e) {   // 0 is what a control block holds that no run has written
+    ++e->run_id;
+    if (e->run_id == 0) e->run_id = 1;
+}
 bool dag_applies(const bn_engine* e);
 int ensure_dag(bn_engine* e);
 SmallArgs small_args_of(bn_engine* e, const BpBuffers& b, double eps, int32_t max_sweeps, int32_t begin, Ctl* host_ctl);
@@ -393,6 +400,11 @@ int check_evidence(const Plan& p, int32_t ne, const int32_t* ev_node, const int3
                           std::vector<uint32_t>& seen, uint32_t& epoch);
 void free_engine(bn_engine* e);
 int small_gave_up(bn_engine*);
+// the run of a single query: bn_engine_paths.cpp dispatches, bn_engine.cpp has the evidence and the per-sweep launches
+int flush_evidence(bn_engine* e);
+void note_run_result(bn_engine* e);
+int run_per_sweep(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to);
+int run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_t* sweeps_out, double* residual_out, double* copy_to);
 void resident_ran_ok(bn_engine* e);
 }  // namespace bn_eng
 

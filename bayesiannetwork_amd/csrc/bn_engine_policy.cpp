@@ -1,0 +1,132 @@
+// bn_engine_policy.cpp -- the shape of a resident launch and the choice between the one-launch paths (bn_engine_policy.hpp).  Host
+// arithmetic only; the thresholds below were measured on MI355X (the comments carry the figures).
+#include "bn_engine_policy.hpp"
+
+namespace bn_policy {
+
+namespace {
+// blocks a launch of `w` waves per block needs (single engines round up to a multiple of 8 for the XCD-contiguous
+// mapping; shards keep the CUs for each other)
+int64_t resident_blocks(const PathFacts& f, int w) {
+    int64_t b = (f.n_tiles + w - 1) / w;
+    if (b > 1 && f.nranks == 1) b = (b + 7) & ~int64_t(7);
+    return b;
+}
+// ... + the barrier's service block must fit 0.9 x CUs: decided on the ROUNDED count (a 239 x 240 grid
+// has 898 tiles = 225 blocks of four, 232 after rounding: too many -- it keeps 8 waves per block)
+bool resident_fits(const PathFacts& f, int n_cus, int w) {
+    const int64_t b = resident_blocks(f, w);
+    return b + 1 <= int64_t(n_cus) * 9 / 10 && b <= kResidentMaxBlocks;
+}
+}  // namespace
+
+// resident path (bn_resident.hip): one-lane tiles (<= 2 parents, <= 8 children per node), one wave per tile, every block co-resident (one 512-thread block of <= 256 VGPRs per CU)
+ResidentShape plan_resident(const PathFacts& f, int n_cus, int forced_waves) {
+    ResidentShape r;
+    const int64_t nt = f.n_tiles;
+    // One 8-wave block per CU is two waves per SIMD sharing its issue slots.  A network whose tiles fit the chip at
+    // FOUR waves per block (the CPT slots in LDS keep it at one block per CU) gives every wave a SIMD of its own.
+    // BN_RESIDENT_WAVES=8 / 4 forces either (A/B).
+    r.waves = kResidentWaves;
+    if (nt > kResidentWaves && resident_fits(f, n_cus, kResidentWaves / 2)) r.waves = kResidentWaves / 2;
+    const int v = forced_waves;
+    if (v == kResidentWaves || (v == kResidentWaves / 2 && resident_fits(f, n_cus, v)) || (v == 2 && nt > 2 && resident_fits(f, n_cus, v))) r.waves = v;
+    r.blocks = int(resident_blocks(f, r.waves));
+    const bool shapes = f.all_uniform && resident_fits(f, n_cus, r.waves) &&
+                        f.rec_total_doubles * 8 < (int64_t(1) << 31) &&  // 32-bit byte offsets into a record buffer
+                        f.tile_cmax <= 8 && f.tile_m <= 2;
+    r.resident_ok = shapes && f.nranks == 1 && nt > 0 && !f.any_in_ref;
+    r.shard_shapes_ok = shapes && f.nranks > 1 && f.nranks <= kMaxRanks;
+    r.lean = (r.resident_ok || r.shard_shapes_ok) && nt > 0 && !f.any_cmax_gt2 ? f.tile_kv : 0;
+    r.flow_ok = r.resident_ok && r.blocks > 1 && !f.nbr_empty && nt <= kFlowMaxTiles;
+    return r;
+}
+
+bool mid_fits(const PathFacts& f, int n_cus) {
+    // the workgroups of a run wait for each other: one per CU, with room to spare
+    return !(n_cus > 0 && int64_t(f.mid.parts) > int64_t(n_cus) * 9 / 10);
+}
+
+int32_t dag_cap(int n_cus) { return int32_t((int64_t(n_cus) * 9 / 10) & ~int64_t(7)); }
+
+// resident tiles pay on one block (no grid barrier at all) and on large networks (the CPT traffic saved outweighs the barrier); with 8
+// waves per block the crossover was measured at ~600 tiles (160x160 grid, 402 tiles: 8.2 vs 8.9 us per sweep; 200x200, 627: 9.5 vs
+// 9.2); at 4 waves per block (networks up to ~900 tiles: every wave has a SIMD of its own) it is faster than the launches from the
+// smallest multi-block network on (32x32 grid 7.2 vs 7.4-7.8, 128x128 7.7 vs 8.0, 200x200 8.7 vs 9.5).  Shards: the in-kernel exchange
+// wherever every rank's tiles qualify and the peers are mapped ("multisweep" 0 = per-sweep launches + one RCCL all-gather per sweep).
+bool resident_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    constexpr int64_t kResidentMinTiles = 600;
+    if (f.nranks > 1) return ok.shard_flow && m.multisweep != 0;
+    const bool pays = r.blocks == 1 || r.waves < kResidentWaves || f.n_tiles >= kResidentMinTiles;
+    return r.resident_ok && (m.multisweep == 2 || (m.multisweep == 1 && pays));
+}
+
+// The one-workgroup path is taken wherever the network fits, except where the resident-tile kernel runs the network in ONE block and
+// was measured faster (scripts/experiments/small_vs_resident.py, us per sweep small / resident): chains and trees (one parent per
+// node) beyond ~128 nodes or one round of entry items (200-node chain, k = 4: 5.2 / 2.8; 100 nodes: 2.9 / 2.6), and networks that
+// need two rounds of accumulator or product items (16 x 16 grid, k = 2: 4.3 / 3.5).  With two parents per node the tile kernel's
+// 64-entry contraction costs more than the items (8 x 8 grid, k = 4: 4.2 / 5.1; 40-node DAG: 2.6 / 6.4).
+bool small_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    if (!ok.small || m.multisweep == 0 || m.small == 0) return false;
+    if (m.small == 2) return true;
+    return !(r.resident_ok && r.blocks == 1) ||
+           (f.small.rb == 1 && f.small.rc == 1 && (f.small.mmax >= 2 || (f.small.re == 1 && f.small.n <= 128)));
+}
+
+// the mid-size kernel is the path of choice for this engine (measured: grids, chains and trees run faster on the resident tiles)
+bool mid_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    if (!ok.mid || m.multisweep == 0 || m.mid == 0) return false;
+    if (m.mid == 2 || !r.resident_ok) return true;
+    // Networks the resident tiles cover as well (scripts/experiments/mid_path.py, us per sweep resident / this path): with two
+    // parents per node and four states the tile's 64-entry contraction costs more than the items (16 x 16 grid 5.9 / 4.3,
+    // 32 x 32 7.0 / 6.4, 200-node DAG 6.7 / 4.3); chains, trees and smaller tables stay on the tiles (400-node chain 3.2 / 4.3,
+    // 12 x 12 grid of k = 3: 3.7 / 4.3).
+    // ... up to the size of the 40 x 40 grid (6.6 against 6.6-6.9); larger ones stay on the tiles (64 x 64: 6.4)
+    // (mmax over all parts: the first one may hold a grid's first row only)
+    return f.mid.mmax >= 2 && f.kmax >= 4 && f.mid.est_total <= 580000;
+}
+
+// k = 4 networks with up to 5 parents per node whose size puts them beyond the item kernels (BASELINE configs[1]): the
+// register-resident DAG path (bn_dag.hip) where no other one-launch path takes the network; "dag" 2 = wherever eligible
+bool dag_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    if (!ok.dag || m.multisweep == 0 || m.dag == 0) return false;
+    if (m.dag == 2) return true;
+    // Networks the one-workgroup path (state in LDS) takes as well, us per query (profiles/r05_paths.json), that path / this one: one
+    // round of entry items (ALARM-sized) 48.6 / 68.7, Pearl's four nodes 19.3 / 24.5 -- but 8 x 8 grid, k = 4 (four rounds) 86.0 / 64.4,
+    // 60 nodes of mixed arity with <= 3 parents (three rounds) 72.3 / 64.6.  Chains and trees the resident tiles run in ONE block
+    // stay there (200-node chain: 71.9 resident, 81.6 this path, 113.6 one workgroup).
+    if (ok.small && f.small.re <= 2) return false;   // (two rounds: not measured; the one-workgroup path also keeps the reference's order for >= 3 parents)
+    // ... and where the two paths' BITS differ -- some node has >= 3 parents: lane groups re-associate, the one-workgroup path keeps the
+    // reference's order -- the small network stays on the one-workgroup path whatever its rounds: a batch of such a network runs one
+    // workgroup per set (bn_engine_batch.cpp), and a set's answer must not depend on whether it was asked alone or in a batch
+    // (scripts/soak_gpu.py found a 30-node network where the two differed by 2e-16; round 6).  Price: 60 nodes of mixed arity, <= 3
+    // parents: 72 instead of 65 us per query.
+    if (ok.small && f.dag.has_groups) return false;
+    if (ok.small && f.small.mmax <= 1 && r.resident_ok && r.blocks == 1) return false;
+    // Arities below 4 (padded form), us per sweep, this path / the default before (scripts/time_dag_mixed.py): mixed arities 2-4 with
+    // <= 3 parents 300 / 3 000 / 10 000 nodes 4.6 / 5.4, 5.7 / 7.1, 6.5 / 9.2 (item kernels); <= 4 parents, 10 000 nodes (723 k entries:
+    // beyond the item kernels) 6.5 / 32.5; binary, <= 4 parents, 10 000 nodes 6.2 / 7.7; k = 3 grid 64 x 64 5.0 / 6.1 -- but k = 2 grid
+    // 128 x 128 6.4 / 5.5 (resident tiles): an eighth of every padded table is real there.
+    if (!f.dag.uniform4 && !f.dag.has_groups && f.dag.fill < 0.25) return false;
+    // Measured, us per query (evidence staged, profiles/r04_paths.json), this path / the best of the others:
+    //   lane-group tiles (some node has 3-5 parents): 200 nodes 76 / 122, 1 000 nodes 87 / 165, 3 000 nodes 101 / 182, 10 000 nodes
+    //   (BASELINE configs[1]) 117 / 215; nodes of <= 2 parents: 16 x 16 grid 86 / 95, 40 x 40 117 / 135, 64 x 64 113 / 139, 128 x 128
+    //   133 / 146, 3 000-node DAG 106 / 119, 200-node chain 74 / 74 -- but 200 x 200 grid 283 / 151, 316 x 316 634 / 234: there the
+    //   network no longer fits the chip at one tile per wave (stream form) and the resident tiles keep it.
+    // stream form re-reads the padded image every sweep: not where less than a quarter of it is real (a padded binary network
+    // with 5-parent nodes is 64x its model), whatever the parent counts -- only <= 10 k-node networks were measured in that form
+    if (f.dag.stream && f.dag.fill < 0.25) return false;
+    if (f.dag.has_groups) return true;
+    return !f.dag.stream;
+}
+
+// the register-resident DAG path AHEAD of the one-workgroup path: forced ("dag" 2), or a small network of three or more rounds of
+// entry items (dag_applies has the measurements)
+bool dag_first_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    return (m.dag == 2 || (ok.small && m.small != 2)) && dag_applies(f, r, ok, m);
+}
+bool dag_later_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
+    return !dag_first_wanted(f, r, ok, m) && dag_applies(f, r, ok, m);
+}
+
+}  // namespace bn_policy

@@ -1,0 +1,64 @@
+// bn_engine_policy.hpp -- which kernel runs a query: the shape of a resident launch and the choice between the one-launch paths, as
+// pure functions of a few facts about the plans, the device's CU count and the options.  No HIP, no engine, no plan headers, no
+// environment: tests/cpp/test_engine_policy.cpp compiles this with bn_engine_policy.cpp alone and checks both sides of every
+// threshold on a CPU.  bn_engine_create.cpp fills the facts (path_facts_of) and mirrors the constants below with static_asserts.
+#ifndef BN_ENGINE_POLICY_HPP
+#define BN_ENGINE_POLICY_HPP
+#include <cstdint>
+
+namespace bn_policy __attribute__((visibility("hidden"))) {   // (not part of the library's exported surface)
+
+// (bn_device.hpp has the originals: kResidentWaves, kResidentMaxBlocks, kFlowMaxTiles, kMaxRanks)
+constexpr int kResidentWaves = 8;
+constexpr int kResidentMaxBlocks = 256;
+constexpr int kFlowMaxTiles = kResidentWaves * kResidentMaxBlocks;
+constexpr int kMaxRanks = 16;
+
+// What the choice reads of an engine's plans (bn_plan.hpp Plan, bn_small.hpp SmallPlan / MidPlan, bn_dag.hpp DagPlan).
+struct PathFacts {
+    int32_t nranks = 1;
+    int64_t n_tiles = 0;
+    bool all_uniform = true;        // every tile is the uniform variant (and Plan::variants says so)
+    int32_t tile_cmax = 0;          // maxima over the tiles of TileDesc::cmax and TileDesc::m
+    int32_t tile_m = 0;
+    bool any_in_ref = false;        // some tile has in_ref_base >= 0
+    int32_t tile_kv = 0;            // the tiles' common kv, 0 if mixed (or no tile)
+    bool any_cmax_gt2 = false;      // some tile has cmax > 2
+    int64_t rec_total_doubles = 0;
+    bool nbr_empty = true;          // Plan::nbr
+    int32_t kmax = 0;               // largest arity of a node
+    struct Small { bool ok = false; int32_t n = 0, re = 0, rb = 0, rc = 0, mmax = 0; } small;
+    struct Mid { bool ok = false; int32_t parts = 0, mmax = 0; int64_t est_total = 0; } mid;   // mmax: over all parts
+    struct Dag { bool ok = false, uniform4 = false, has_groups = false; double fill = 0.0; bool stream = false; int32_t blocks = 0; } dag;
+};
+
+// The launch shape of the resident kernel (bn_resident.hip) and what the network is eligible for on it.
+struct ResidentShape {
+    int waves = kResidentWaves;     // tiles per block of the resident kernel (8, or 4 on networks small enough)
+    int blocks = 0;                 // tile blocks of a launch ("resident_blocks")
+    bool resident_ok = false;       // every tile register-resident and co-resident: the whole run in one launch (bn_resident.hip)
+    bool shard_shapes_ok = false;   // this shard's tiles are what the resident kernel runs (uniform arity, <= 2 parents, <= 8 children)
+    int lean = 0;                   // ... and every node has this arity (2, 3 or 4) and <= 2 children; else 0
+    bool flow_ok = false;           // dataflow form: more than one tile block, every tile has <= 64 neighbour tiles
+};
+// forced_waves: BN_RESIDENT_WAVES (0: not set); 8 is always honoured, 4 and 2 only where the blocks fit
+ResidentShape plan_resident(const PathFacts& f, int n_cus, int forced_waves);
+
+// the options "multisweep", "small", "mid", "dag" (0 never, 1 where measured faster, 2 wherever eligible)
+struct PathModes { int multisweep = 1, small = 1, mid = 1, dag = 1; };
+// what only the device side of an engine knows: the path's tables are uploaded and its kernel prepared (shard_flow: the peers are mapped)
+struct PathOks { bool small = false, mid = false, dag = false, shard_flow = false; };
+
+bool mid_fits(const PathFacts& f, int n_cus);   // the several-workgroup plan's parts within 0.9 x CUs (n_cus 0: unknown, fits)
+int32_t dag_cap(int n_cus);                     // block cap of the DAG plan: 0.9 x CUs, a multiple of 8
+
+bool resident_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+bool small_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+bool mid_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+bool dag_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+bool dag_first_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+bool dag_later_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+
+}  // namespace bn_policy
+
+#endif  // BN_ENGINE_POLICY_HPP

@@ -90,10 +90,10 @@ extern "C" int bn_peer_export(bn_engine* e, void* blob, int64_t cap) {
     h.device = e->host_only ? -1 : e->device;
     h.pid = int64_t(getpid());
     h.n_boundary = int32_t(e->plan.boundary_node.size());
-    h.shapes_ok = (e->host_only || e->shard_shapes_ok) ? 1 : 0;
+    h.shapes_ok = (e->host_only || e->shape.shard_shapes_ok) ? 1 : 0;
     h.g_base = e->plan.g_base;
     h.rec_bytes = e->plan.rec_total_doubles * 8;
-    if (!e->host_only && e->shard_shapes_ok) {
+    if (!e->host_only && e->shape.shard_shapes_ok) {
         ON_DEVICE(e);
         h.flow_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_flow.get()));
         h.rec0_ptr = uint64_t(reinterpret_cast<uintptr_t>(e->d_rec[0].get()));
@@ -149,7 +149,7 @@ extern "C" int bn_peer_import(bn_engine* e, const void* const* blobs, const int6
     if (!err.empty()) all_ok = false;
     e->shard_flow_ok = false;
     if (e->host_only) return BN_OK;  // tables only (tests)
-    if (!all_ok || !e->shard_shapes_ok) return BN_OK;  // stays on the per-sweep launches + RCCL
+    if (!all_ok || !e->shape.shard_shapes_ok) return BN_OK;  // stays on the per-sweep launches + RCCL
     ON_DEVICE(e);
     HIPCHK(hipStreamSynchronize(e->stream));
     std::vector<PeerTable> peers(n);

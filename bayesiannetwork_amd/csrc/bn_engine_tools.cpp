@@ -131,6 +131,7 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
         if (e->small.ok) e->small = std::move(n_small);
         if (e->mid.ok) e->mid = std::move(n_mid);
         if (e->dag.ok) e->dag = std::move(n_dag);
+        e->facts = path_facts_of(p, e->small, e->mid, e->dag);
         if (e->dense) { free_engine(e->dense); e->dense = nullptr; e->batch_on_dense = false; }   // (rebuilt from the new tables on demand)
         e->score.ready = false;   // (the log table of bn_score_*: taken again from the new values at the next call)
         if (e->host_only) return BN_OK;
@@ -144,10 +145,10 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
             if ((rc = reupload(e->d_s_init, e->small.npi_init, e->small.npi_init.size(), s, "initial pi"))) return rc;
         }
         if (e->mid_ok) {
-            std::vector<double> all;
-            for (const SmallPlan& sp : e->mid.parts) all.insert(all.end(), sp.ent_cpt.begin(), sp.ent_cpt.end());
-            if ((rc = reupload(e->d_m_cpt, all, all.size(), s, "entry tables"))) return rc;
-            HIPCHK(hipStreamSynchronize(s));   // `all` is a local
+            MidTables t;
+            build_mid_tables(e->mid, p, t);
+            if ((rc = reupload(e->d_m_cpt, t.ent_cpt, t.ent_cpt.size(), s, "entry tables"))) return rc;
+            HIPCHK(hipStreamSynchronize(s));   // `t` is a local
             if ((rc = reupload(e->d_m_init, e->mid.parts[0].npi_init, e->mid.parts[0].npi_init.size(), s, "initial pi"))) return rc;
         }
         if (e->dag_ready) {

@@ -158,6 +158,18 @@ struct MidArgs {
     int32_t set_base, slot_base;
     int64_t state_stride;
 };
+// The flat tables the mid kernel reads, from the plan's parts: each part's tables back to back (MidPart has the offsets), and the first
+// message element of every node's in-edges.  What bn_create uploads; bn_reload_cpt takes the new ent_cpt from it.
+struct MidTables {
+    std::vector<MidPart> parts;
+    std::vector<SmallEntry> ent;
+    std::vector<double> ent_cpt;
+    std::vector<uint32_t> term;
+    std::vector<uint16_t> clist;
+    std::vector<SmallSlot> bslot, cslot;
+    std::vector<int32_t> msg_first;   // [n + 1]
+};
+void build_mid_tables(const MidPlan& mp, const Plan& p, MidTables& t);
 int prepare_bp_mid();
 int launch_bp_mid(const MidArgs& a, int waves, int rounds, size_t lds_bytes, int n_sets, void* stream);
 

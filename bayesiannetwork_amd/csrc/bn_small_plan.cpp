@@ -379,4 +379,21 @@ void build_mid_plan(const Plan& p, MidPlan& mp) {
     no(mp.why.empty() ? std::string("does not fit ") + std::to_string(kMidMaxParts) + " workgroups" : mp.why);
 }
 
+void build_mid_tables(const MidPlan& mp, const Plan& p, MidTables& t) {
+    t = MidTables();
+    for (const SmallPlan& sp : mp.parts) {
+        MidPart pt{sp.v0, sp.v1, int32_t(t.ent.size()), int32_t(t.term.size()), int32_t(t.clist.size()), int32_t(t.bslot.size()), int32_t(t.cslot.size()),
+                   sp.re, sp.rb, sp.rc, sp.T, sp.TT, sp.CL, sp.waves * kWave};
+        t.parts.push_back(pt);
+        t.ent.insert(t.ent.end(), sp.ent.begin(), sp.ent.end());
+        t.ent_cpt.insert(t.ent_cpt.end(), sp.ent_cpt.begin(), sp.ent_cpt.end());
+        t.term.insert(t.term.end(), sp.term.begin(), sp.term.end());
+        t.clist.insert(t.clist.end(), sp.clist.begin(), sp.clist.end());
+        t.bslot.insert(t.bslot.end(), sp.bslot.begin(), sp.bslot.end());
+        t.cslot.insert(t.cslot.end(), sp.cslot.begin(), sp.cslot.end());
+    }
+    t.msg_first.resize(size_t(p.n) + 1);
+    for (int v = 0; v <= p.n; ++v) t.msg_first[v] = int32_t(p.msg_off[v < p.n ? p.in_ptr[v] : p.in_ptr[p.n]]);
+}
+
 }  // namespace bnmi
