@@ -81,8 +81,9 @@ static void debug_segv_handler(int sig) {
 }
 // bn_engine_policy.hpp restates these without including a device header: they must not drift apart
 static_assert(bn_policy::kResidentWaves == kResidentWaves && bn_policy::kResidentMaxBlocks == kResidentMaxBlocks &&
-              bn_policy::kFlowMaxTiles == kFlowMaxTiles && bn_policy::kMaxRanks == kMaxRanks,
-              "bn_engine_policy.hpp: a constant differs from bn_device.hpp");
+              bn_policy::kFlowMaxTiles == kFlowMaxTiles && bn_policy::kMaxRanks == kMaxRanks &&
+              bn_policy::kResidentMaxSets == kResidentMaxSets && bn_policy::kDagMaxSets == kDagMaxSets,
+              "bn_engine_policy.hpp: a constant differs from bn_device.hpp / bn_dag.hpp");
 
 // What the path choice reads of the plans (bn_engine_policy.hpp).  Filled at bn_create and again wherever a plan it summarises is
 // rebuilt: the DAG plan for another block cap or in full (ensure_dag), the several-workgroup plan refused for the device's CU count,
@@ -95,6 +96,7 @@ static bn_policy::PathFacts::Dag dag_facts_of(const DagPlan& dag) {
 bn_policy::PathFacts bn_eng::path_facts_of(const Plan& p, const SmallPlan& small, const MidPlan& mid, const DagPlan& dag) {
     bn_policy::PathFacts f;
     f.nranks = p.nranks;
+    f.latency_rules_applied = p.latency_rules_applied;
     f.n_tiles = int64_t(p.tiles.size());
     f.all_uniform = p.tiles.empty() || p.variants == (1 << kVariantUniform);
     f.tile_kv = p.tiles.empty() ? 0 : int(p.tiles[0].kv);

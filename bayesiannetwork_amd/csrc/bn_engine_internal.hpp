@@ -3,9 +3,11 @@
 // messages; bn_engine_create.cpp: bn_create / bn_destroy, the device set-up one step per path, the stream pool, ensure_dag;
 // bn_engine_paths.cpp: the one-launch paths of a single query, their dispatch (run_device_impl) and "autotune";
 // bn_engine_policy.hpp / .cpp: which path runs a query, as pure host functions of a few facts (no HIP: checked stand-alone on a
-// CPU); bn_engine_batch.cpp: several evidence sets per call; bn_engine_shard.cpp: RCCL communicator and the in-kernel exchange of
-// sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and the fit's entry points.  No
-// CPU compute path exists in any of them: every result comes from the kernels.
+// CPU), for one query and for a batch; bn_engine_batch.cpp: several evidence sets per call -- buffers, evidence staging, the second
+// (dense) engine, the entry points and their dispatch; bn_engine_batch_paths.cpp: the five runs of a batch and what they share;
+// bn_batch_stage.hpp / .cpp: the layout of a batch's evidence staging block (no HIP either); bn_engine_shard.cpp: RCCL communicator
+// and the in-kernel exchange of sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and
+// the fit's entry points.  No CPU compute path exists in any of them: every result comes from the kernels.
 #ifndef BN_ENGINE_INTERNAL_HPP
 #define BN_ENGINE_INTERNAL_HPP
 #include <hip/hip_runtime_api.h>
@@ -33,6 +35,7 @@
 #include "bn_dag.hpp"
 #include "bn_buffer.hpp"
 #include "bn_engine_policy.hpp"
+#include "bn_batch_stage.hpp"
 
 using namespace bnmi;
 
@@ -234,15 +237,15 @@ struct bn_engine {
         bool ev_deferred = false;     // the sets' evidence sits in d_ev only (read there by that kernel); d_ev_meta: per set {count, first node / offset / value}
         int32_t* d_ev_meta = nullptr;   // (inside the staging block)
         PinnedBuf<char> h_ev;           // small networks: the staging block is page-locked host memory the kernels read in place
-        char* ev_base = nullptr;        // the staging block as the device sees it: d_ev, or h_ev mapped
+        char* h_ev_dev = nullptr;       // ... as the device sees it
+        char* ev_base = nullptr;        // the staging block of the batch in force as the device sees it: d_ev, or h_ev_dev
         size_t h_ev_cap = 0;
         PinnedBuf<double> h_beliefs;    // small networks, bn_bp_run_batch: the kernel writes every set's marginals here (mapped) ...
         double* h_beliefs_dev = nullptr;
         size_t h_beliefs_cap = 0;
         bool direct_out = false;        // ... when this is set for the run at hand
         bool beliefs_on_host = false;   // the last run's marginals are in h_beliefs, not d_beliefs
-        size_t ev_b_node = 0, ev_b_off = 0, ev_b_val = 0;  // where the three arrays start inside d_ev
-        std::vector<int64_t> ev_node_at, ev_off_at, ev_val_at;
+        bn_stage::BatchLayout ev_layout;   // where the arrays and each set's entries start inside the staging block
         DeviceBuf<Ctl> d_ctl;       // per-sweep launches: one control block per set
         bool rows_clean = true;     // ... and every set's residual slots are zero
         int32_t predicted_sweeps = 0;
@@ -351,7 +354,8 @@ struct PathDriver {
     int id;                                             // bn_bp_last_path
     bool (*wanted)(const bn_engine*);
     int (*run)(bn_engine*, double eps, int32_t max_sweeps, double* copy_to);
-    int (*gave_up)(bn_engine*);                         // BN_OK: go on with the next path
+    int (*gave_up)(bn_engine*, const char* what);       // BN_OK: go on with the next path
+    const char* what;                                   // ... the kernel's name in the one line on stderr
     void (*ran_ok)(bn_engine*);                         // may be null
     int32_t bn_engine::*cooldown;                       // runs left before the path is tried again
     bool reads_tile_evidence;                           // flush_evidence() first
@@ -391,7 +395,15 @@ MidArgs mid_args_of(bn_engine* e, const BpBuffers& b0, const SetStrides& st, Ctl
                            int32_t begin, int32_t set_base, int32_t slot_base);
 bool mid_applies(const bn_engine* e);
 BpBuffers buffers_of(bn_engine* e);
-int run_dag(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to);
+// the evidence a run of the DAG path applies and where its marginals go: the engine's own (a single query), or one set of a batch
+// (own = false: the engine's state arrays hold foreign evidence afterwards, so the evidence in force is applied again at its next run)
+struct DagQuery {
+    bn_stage::SetView ev;
+    double* beliefs = nullptr;   // nullptr: where buffers_of(e) says
+    bool own = true;
+};
+int run_dag(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to);   // the evidence in force
+int run_dag_query(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to, const DagQuery& q);
 int resident_service_blocks(int tile_blocks);
 void report_abort_once(bn_engine* e, const char* what, int pause_runs);
 int mid_reserve_slots(bn_engine* e, int32_t slots);
@@ -399,7 +411,21 @@ int ensure_events(bn_engine* e, size_t count);
 int check_evidence(const Plan& p, int32_t ne, const int32_t* ev_node, const int32_t* ev_off,
                           std::vector<uint32_t>& seen, uint32_t& epoch);
 void free_engine(bn_engine* e);
-int small_gave_up(bn_engine*);
+int small_gave_up(bn_engine*, const char*);
+int dag_gave_up(bn_engine* e, const char* what);
+int mid_gave_up(bn_engine* e, const char* what);
+int resident_gave_up(bn_engine* e, const char* what);
+// several evidence sets per call: bn_engine_batch.cpp dispatches, bn_engine_batch_paths.cpp has the runs
+BpBuffers batch_buffers_of(bn_engine* e, int32_t q);
+inline SetStrides strides_of(const bn_engine* e) {
+    const Plan& p = e->plan;
+    return SetStrides{p.rec_total_doubles, p.node_doubles, int64_t(std::max(p.n_slots, 1)), p.node_off[p.n], e->res_cap};
+}
+int run_batch_launches(bn_engine* e, double eps, int32_t max_sweeps);
+int run_batch_small(bn_engine* e, double eps, int32_t max_sweeps, double*);
+int run_batch_dag(bn_engine* e, double eps, int32_t max_sweeps, double*);
+int run_batch_mid(bn_engine* e, double eps, int32_t max_sweeps, double*);
+int run_batch_resident(bn_engine* e, double eps, int32_t max_sweeps, double*);
 // the run of a single query: bn_engine_paths.cpp dispatches, bn_engine.cpp has the evidence and the per-sweep launches
 int flush_evidence(bn_engine* e);
 void note_run_result(bn_engine* e);

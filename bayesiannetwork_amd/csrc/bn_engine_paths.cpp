@@ -242,30 +242,35 @@ static int run_mid(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to
 }
 
 // The evidence in force (staging block) -> the state arrays of the DAG path: marks of this set's own value, vectors in both buffers.
-static int flush_dag_evidence(bn_engine* e) {
+static int flush_dag_evidence(bn_engine* e, const DagQuery& q) {
     if (int rc = ensure_dag(e)) return rc;
-    if (e->dag_ev_applied) return BN_OK;
+    if (q.own && e->dag_ev_applied) return BN_OK;
+    e->dag_ev_applied = false;
     if (e->dag_mark == 255) {  // the mark values are used up: start over
         HIPCHK(hipMemsetAsync(e->dag_img.frz, 0, size_t(e->dag.n), e->stream));
         e->dag_mark = 0;
     }
     ++e->dag_mark;
-    DagEvidenceArgs ea{e->ev_ne, e->dag.n, e->dag.E, e->d_ev_node, e->d_ev_off, e->d_ev_val, e->dag_img.state, e->dag_img.frz, e->dag_mark, e->dag_img.k, e->dag_img.nperm};
+    DagEvidenceArgs ea{q.ev.ne, e->dag.n, e->dag.E, q.ev.node, q.ev.off, q.ev.val, e->dag_img.state, e->dag_img.frz, e->dag_mark, e->dag_img.k, e->dag_img.nperm};
     if (int code = launch_dag_evidence(ea, e->stream))
         return fail(BN_ERR_HIP, std::string("dag_evidence launch failed: ") + hipGetErrorString(hipError_t(code)));
-    e->dag_ev_applied = true;
-    e->ev_upload_pending = e->ev_ne > 0;
+    e->dag_ev_applied = q.own;
+    e->ev_upload_pending = q.ev.ne > 0;
     return BN_OK;
 }
 
 // One launch runs the whole query (more only beyond kDagBudget iterations).  BN_ERR_STATE: a grid wait gave up.
 int bn_eng::run_dag(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to) {
+    return run_dag_query(e, eps, max_sweeps, copy_to, DagQuery{{e->ev_ne, e->d_ev_node, e->d_ev_off, e->d_ev_val}, nullptr, true});
+}
+int bn_eng::run_dag_query(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to, const DagQuery& q) {
     hipStream_t s = e->stream;
     if (int rc = ensure_dag(e)) return rc;   // (first use of the path on this engine: full plan, device tables, upload)
     const DagPlan& dp = e->dag;
-    if (int rc = flush_dag_evidence(e)) return rc;
+    if (int rc = flush_dag_evidence(e, q)) return rc;
     OneLaunchRun run(e);
-    const BpBuffers b = buffers_of(e);
+    BpBuffers b = buffers_of(e);
+    if (q.beliefs) b.beliefs = q.beliefs;
     if (!dp.uniform4) {   // arities below 4: the run's initial state stands in memory (zeros in the padding), bn_dag_plan.cpp
         DagInitArgs ia{dp.n, dp.E, e->dag_img.inptr, e->dag_img.inidx, e->dag_img.k, e->dag_img.init, e->dag_img.state, e->dag_img.frz, e->dag_mark, e->dag_img.eperm, e->dag_img.nperm};
         if (int code = launch_dag_init(ia, s))
@@ -388,7 +393,7 @@ static bool small_wanted(const bn_engine* e) { return bn_policy::small_wanted(e-
 static bool dag_first_wanted(const bn_engine* e) { return bn_policy::dag_first_wanted(e->facts, e->shape, oks_of(e), modes_of(e)); }
 static bool dag_later_wanted(const bn_engine* e) { return bn_policy::dag_later_wanted(e->facts, e->shape, oks_of(e), modes_of(e)); }
 
-static int resident_gave_up(bn_engine* e) {
+int bn_eng::resident_gave_up(bn_engine* e, const char* what) {
     ++e->resident_aborts;
     if (e->plan.nranks > 1) {
         // Sharded engines: NO unilateral fall-back inside the library.  A peer whose service block had already published the
@@ -403,31 +408,32 @@ static int resident_gave_up(bn_engine* e) {
     // this run and the next few go down the per-sweep launches (8, 16, ... 1 024 runs), then the path is tried again
     e->resident_cooldown = e->resident_backoff;
     e->resident_backoff = std::min(e->resident_backoff * 2, 1024);
-    report_abort_once(e, "the resident-tile kernel (bn_resident.hip)", e->resident_cooldown);
+    report_abort_once(e, what, e->resident_cooldown);
     return BN_OK;
 }
 void bn_eng::resident_ran_ok(bn_engine* e) { e->resident_backoff = 8; }
 
-int bn_eng::small_gave_up(bn_engine*) { return BN_OK; }   // (one workgroup: it waits for nobody)
-static int dag_gave_up(bn_engine* e) {
+int bn_eng::small_gave_up(bn_engine*, const char*) { return BN_OK; }   // (one workgroup: it waits for nobody)
+int bn_eng::dag_gave_up(bn_engine* e, const char* what) {
     ++e->dag_aborts;
     e->dag_cooldown = 64;   // something else holds CUs: the other paths for a while
-    report_abort_once(e, "the register-resident DAG kernel (bn_dag.hip)", 64);
+    report_abort_once(e, what, 64);
     return BN_OK;
 }
-static int mid_gave_up(bn_engine* e) {
+int bn_eng::mid_gave_up(bn_engine* e, const char* what) {
     ++e->mid_aborts;
     e->mid_cooldown = 64;
-    report_abort_once(e, "the several-workgroup item kernel (bn_mid.hip)", 64);
+    report_abort_once(e, what, 64);
     return BN_OK;
 }
 
+static const char kDagName[] = "the register-resident DAG kernel (bn_dag.hip)";
 static const PathDriver kOneLaunchPaths[] = {
-    {5, dag_first_wanted, run_dag, dag_gave_up, nullptr, &bn_engine::dag_cooldown, false},
-    {3, small_wanted, run_small, small_gave_up, nullptr, &bn_engine::small_cooldown, false},
-    {5, dag_later_wanted, run_dag, dag_gave_up, nullptr, &bn_engine::dag_cooldown, false},   // (its place by default: behind the one-workgroup path)
-    {4, mid_applies, run_mid, mid_gave_up, nullptr, &bn_engine::mid_cooldown, false},
-    {2, resident_wanted, run_resident, resident_gave_up, resident_ran_ok, &bn_engine::resident_cooldown, true},
+    {5, dag_first_wanted, run_dag, dag_gave_up, kDagName, nullptr, &bn_engine::dag_cooldown, false},
+    {3, small_wanted, run_small, small_gave_up, "", nullptr, &bn_engine::small_cooldown, false},
+    {5, dag_later_wanted, run_dag, dag_gave_up, kDagName, nullptr, &bn_engine::dag_cooldown, false},   // (its place by default: behind the one-workgroup path)
+    {4, mid_applies, run_mid, mid_gave_up, "the several-workgroup item kernel (bn_mid.hip)", nullptr, &bn_engine::mid_cooldown, false},
+    {2, resident_wanted, run_resident, resident_gave_up, "the resident-tile kernel (bn_resident.hip)", resident_ran_ok, &bn_engine::resident_cooldown, true},
 };
 
 int bn_eng::run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_t* sweeps_out, double* residual_out, double* copy_to) {
@@ -471,7 +477,7 @@ int bn_eng::run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_
             return BN_OK;
         }
         if (rc != BN_ERR_STATE) return rc;
-        if ((rc = d.gave_up(e)) != BN_OK) return rc;   // counters, pause, one line on stderr (a shard: an error, see resident_gave_up)
+        if ((rc = d.gave_up(e, d.what)) != BN_OK) return rc;   // counters, pause, one line on stderr (a shard: an error, see resident_gave_up)
     }
     if (!evidence_flushed && (rc = flush_evidence(e))) return rc;
     e->last_path = 0;

@@ -1,6 +1,8 @@
-// bn_engine_policy.cpp -- the shape of a resident launch and the choice between the one-launch paths (bn_engine_policy.hpp).  Host
-// arithmetic only; the thresholds below were measured on MI355X (the comments carry the figures).
+// bn_engine_policy.cpp -- the shape of a resident launch and the choice between the one-launch paths, for one query and for a batch
+// (bn_engine_policy.hpp).  Host arithmetic only; the thresholds below were measured on MI355X (the comments carry the figures).
 #include "bn_engine_policy.hpp"
+
+#include <algorithm>
 
 namespace bn_policy {
 
@@ -128,5 +130,70 @@ bool dag_first_wanted(const PathFacts& f, const ResidentShape& r, const PathOks&
 bool dag_later_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m) {
     return !dag_first_wanted(f, r, ok, m) && dag_applies(f, r, ok, m);
 }
+
+// ---- a batch of evidence sets ----
+// Which way a batch goes (measured, scripts/time_batch.py, us per set-sweep at the best batch size of either path): a small network runs one
+// workgroup per set; otherwise the register-resident DAG path and the several-workgroup item kernel where their single-query policy
+// chooses them; the resident tiles from ~900 tiles up -- per-sweep launches with one set per blockIdx.y share the launch latency among
+// the sets, which is what smaller networks pay for (128x128 grid: 1.8 vs 7.7 resident, 200x200: 5.0 vs 8.0); on larger ones the CPT
+// traffic the resident kernel saves weighs more (250x250: 9.1 vs 8.2, 316x316: 14.6 vs 8.6).  "multisweep" 2 forces the resident
+// kernel wherever eligible, 0 the launches; "dag" 2 puts the DAG path in front of the one-workgroup path, as for single queries.
+bool batch_small_wanted(const PathFacts&, const ResidentShape&, const PathOks& ok, const PathModes& m, const BatchDevice& d) {
+    return ok.small && m.small != 0 && m.multisweep != 0 && d.small_state && !(m.dag == 2 && ok.dag);
+}
+bool batch_dag_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d) {
+    return !batch_small_wanted(f, r, ok, m, d) && dag_applies(f, r, ok, m) && d.staged && f.nranks == 1;
+}
+bool batch_mid_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d) {
+    return !batch_small_wanted(f, r, ok, m, d) && mid_applies(f, r, ok, m) && d.staged;
+}
+bool batch_resident_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d) {
+    constexpr int64_t kResidentBatchMinTiles = 900;
+    if (batch_small_wanted(f, r, ok, m, d)) return false;
+    return r.resident_ok && (m.multisweep == 2 || (m.multisweep == 1 && f.n_tiles >= kResidentBatchMinTiles));
+}
+
+// Batches want throughput; a layout built for the latency of one query (wide lane groups, any-arity tiles for nodes with many
+// children: bn_plan.cpp) has up to 4x the wavefronts.  Such an engine answers batches of two or more sets through a second engine
+// built from the same model with the dense layout -- except on the paths where the layout plays no part: one workgroup per set
+// (bn_small.hip), a few per set (bn_mid.hip), the register-resident DAG path (bn_dag.hip).
+bool batch_wants_dense(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, int32_t n_sets) {
+    if (!f.latency_rules_applied || f.nranks > 1 || n_sets < 2) return false;
+    if (ok.small && m.small != 0 && m.multisweep != 0) return false;
+    return !mid_applies(f, r, ok, m) && !dag_applies(f, r, ok, m);
+}
+
+// "each set gets exactly the result its single query gives it" (bn_mi355x.h): the two layouts may put a node on DIFFERENT tile
+// variants (the latency layout gives nodes with many children the any-arity tiles), and for tables beyond 128 entries -- >= 3
+// parents, or two parents of arity >= 6 -- the variants sum in different orders (each within 1e-12 of the reference, but not the
+// same bits; scripts/soak_gpu.py, round 6: a 200-node network of arities {4, 6} differed by 1e-16 between a batch and its single
+// queries).  Where that happens to some node the batch runs on the engine's own layout.
+bool dense_keeps_bits(const NodeLayout* own, int32_t n_own, const NodeLayout* dense, int32_t n_dense) {
+    if (n_own != n_dense) return false;
+    for (int32_t v = 0; v < n_own; ++v) {
+        if (own[v].cls < 0 || dense[v].cls < 0) continue;
+        if ((own[v].variant != dense[v].variant || own[v].G != dense[v].G) && own[v].entries > 128) return false;
+    }
+    return true;
+}
+
+std::vector<int32_t> resident_batch_chunks(int32_t n_sets) {
+    const int32_t n_chunks = (n_sets + kResidentMaxSets - 1) / kResidentMaxSets;
+    std::vector<int32_t> counts;
+    for (int32_t c = 0, first = 0; c < n_chunks; ++c) {
+        counts.push_back((n_sets - first + (n_chunks - c) - 1) / (n_chunks - c));
+        first += counts.back();
+    }
+    return counts;
+}
+
+// as many sets per launch as fit the chip with a workgroup per CU (the grid barrier needs every workgroup of a set resident)
+int32_t mid_sets_per_launch(int n_cus, int32_t parts, int32_t n_sets) { return std::max(1, std::min(n_sets, (n_cus * 9 / 10) / parts)); }
+
+// Config 2, us per set-sweep at B = 16: 8.7 / 6.9 / 6.2 / 5.9 with 1 / 2 / 4 / 8 sets per launch in round 4; round 5 (a turn's arrival
+// behind the next turn's loads, one evidence launch per chunk, one host wait): 4.65 with 8, 4.49 with 16 -- the pace inside the kernel
+// is a wave's set-turn, but a launch's ramp, its evidence launch and the tail where few sets are left come once instead of twice
+// (scripts/time_dag_batch.py)
+int32_t dag_sets_per_launch(int forced) { return forced == 0 ? kDagMaxSets : std::max(1, std::min(kDagMaxSets, forced)); }
 
 }  // namespace bn_policy

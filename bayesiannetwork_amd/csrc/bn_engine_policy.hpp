@@ -1,22 +1,27 @@
 // bn_engine_policy.hpp -- which kernel runs a query: the shape of a resident launch and the choice between the one-launch paths, as
-// pure functions of a few facts about the plans, the device's CU count and the options.  No HIP, no engine, no plan headers, no
-// environment: tests/cpp/test_engine_policy.cpp compiles this with bn_engine_policy.cpp alone and checks both sides of every
-// threshold on a CPU.  bn_engine_create.cpp fills the facts (path_facts_of) and mirrors the constants below with static_asserts.
+// pure functions of a few facts about the plans, the device's CU count and the options; the same for a batch of evidence sets, with
+// the chunks its sets are launched in.  No HIP, no engine, no plan headers, no environment: tests/cpp/test_engine_policy.cpp and
+// tests/cpp/test_batch_plan.cpp compile this with bn_engine_policy.cpp alone and check both sides of every threshold on a CPU.
+// bn_engine_create.cpp fills the facts (path_facts_of) and mirrors the constants below with static_asserts.
 #ifndef BN_ENGINE_POLICY_HPP
 #define BN_ENGINE_POLICY_HPP
 #include <cstdint>
+#include <vector>
 
 namespace bn_policy __attribute__((visibility("hidden"))) {   // (not part of the library's exported surface)
 
-// (bn_device.hpp has the originals: kResidentWaves, kResidentMaxBlocks, kFlowMaxTiles, kMaxRanks)
+// (bn_device.hpp has the originals: kResidentWaves, kResidentMaxBlocks, kFlowMaxTiles, kMaxRanks, kResidentMaxSets; bn_dag.hpp: kDagMaxSets)
 constexpr int kResidentWaves = 8;
 constexpr int kResidentMaxBlocks = 256;
 constexpr int kFlowMaxTiles = kResidentWaves * kResidentMaxBlocks;
 constexpr int kMaxRanks = 16;
+constexpr int kResidentMaxSets = 4;
+constexpr int kDagMaxSets = 16;
 
 // What the choice reads of an engine's plans (bn_plan.hpp Plan, bn_small.hpp SmallPlan / MidPlan, bn_dag.hpp DagPlan).
 struct PathFacts {
     int32_t nranks = 1;
+    bool latency_rules_applied = false;   // Plan: the layout trades wavefront count for the latency of one query
     int64_t n_tiles = 0;
     bool all_uniform = true;        // every tile is the uniform variant (and Plan::variants says so)
     int32_t tile_cmax = 0;          // maxima over the tiles of TileDesc::cmax and TileDesc::m
@@ -58,6 +63,27 @@ bool mid_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, 
 bool dag_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
 bool dag_first_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
 bool dag_later_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
+
+// ---- a batch of evidence sets (bn_bp_run_batch_device): the same questions for the batch forms of the paths ----
+// what only the device side knows of a batch: the per-set state of the one-workgroup path is allocated (Batch::d_s_state), a staging
+// block holds the sets' evidence (Batch::ev_base)
+struct BatchDevice { bool small_state = false, staged = false; };
+bool batch_small_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d);
+bool batch_dag_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d);
+bool batch_mid_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d);
+bool batch_resident_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, const BatchDevice& d);
+
+// the batch belongs on a second engine with the dense layout (bn_engine_batch.cpp, dense_engine_for_batch)
+bool batch_wants_dense(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m, int32_t n_sets);
+// ... unless that layout gives some node's sums another order.  One entry per node of a layout: the node's class (negative: not in
+// this plan, skipped), the class's tile variant and lanes per node, the entries of its table.
+struct NodeLayout { int32_t cls = -1, variant = 0, G = 0; int64_t entries = 0; };
+bool dense_keeps_bits(const NodeLayout* own, int32_t n_own, const NodeLayout* dense, int32_t n_dense);
+
+// how many sets share a launch
+std::vector<int32_t> resident_batch_chunks(int32_t n_sets);              // balanced chunks of at most kResidentMaxSets, the larger first
+int32_t mid_sets_per_launch(int n_cus, int32_t parts, int32_t n_sets);   // a workgroup per CU within 0.9 x CUs, at least one set
+int32_t dag_sets_per_launch(int forced);                                 // forced: BN_DAG_SETS (0: not set) -> 1..kDagMaxSets
 
 }  // namespace bn_policy
 

@@ -270,6 +270,62 @@ def test_dag_batch_shares_launches(Engine, oracle_mod):
             assert long["sweeps"][q] == 1030 == r["sweeps"] and np.array_equal(long["beliefs"][q], r["beliefs"])
 
 
+def test_dag_batch_leftovers_keep_the_single_query_evidence(Engine):
+    """Single-query evidence A is staged, then a batch of two OTHER sets runs 1 030 sweeps each: both exceed one launch's budget of
+    1 024 iterations and are finished on their own, through the single query's run.  Every set has the sweeps, the bits and the
+    residual history of its single run (one shared launch + two launches per left-over set), and a bn_bp_run_device after the
+    batch answers A alone: the left-over route leaves the evidence in force as it found it."""
+    from bayesiannetwork_amd import synth
+    g = synth.random_dag(200, 4, 64, 4, seed=200)
+    ev_a = synth.random_evidence(g, 0.05, seed=31)
+    sets = [synth.random_evidence(g, 0.03, seed=32), synth.random_evidence(g, 0.1, seed=33)]
+    with Engine(g) as eng:
+        eng.set_option("dag", 2)
+        singles, hists = [], []
+        for ev in sets:
+            singles.append(eng.bp_run(ev, 0.0, 1030))
+            hists.append(eng.bp_residuals().copy())
+        a_alone = eng.bp_run(ev_a, 1e-6)
+        assert eng.last_path() == 5
+        eng.bp_set_evidence(ev_a)
+        out = eng.bp_run_batch(sets, 0.0, 1030)
+        assert eng.last_path() == 5 and eng.info("dag_aborts") == 0 and eng.bp_stats()["sweep_launches"] == 5
+        for q, r in enumerate(singles):
+            assert out["sweeps"][q] == 1030 == r["sweeps"] and np.array_equal(out["beliefs"][q], r["beliefs"]), q
+            assert out["residual"][q] == r["residual"] and np.array_equal(eng.bp_residuals_batch(q), hists[q]), q
+            assert len(hists[q]) == 1030
+        after = eng.bp_run_device(1e-6)
+        assert eng.last_path() == 5 and after["sweeps"] == a_alone["sweeps"] and after["residual"] == a_alone["residual"]
+        assert np.array_equal(eng.bp_beliefs(), a_alone["beliefs"])
+        assert not np.array_equal(a_alone["beliefs"], singles[0]["beliefs"])
+
+
+def test_dag_batch_after_a_batch_staged_in_device_memory(Engine):
+    """Where a batch's evidence is staged follows the options: device memory and an evidence launch per set when only the tile kernels
+    can run the batch, page-locked host memory that the kernels read in place when a one-launch path may.  A batch on the
+    per-sweep launches ("multisweep" 0) followed by a smaller one on the DAG path must read the SECOND batch's block, not what the
+    first left in device memory: every set has the bits of its single run."""
+    from bayesiannetwork_amd import synth
+    g = synth.grid(128, 128, 2, seed=1)      # no one-workgroup and no several-workgroup plan: only "dag" decides where the block lives
+    evs = [synth.random_evidence(g, 0.02, seed=60 + q) for q in range(5)]
+    with Engine(g) as eng:
+        assert eng.info("small_eligible") == 0 and eng.info("mid_eligible") == 0 and eng.info("dag_eligible") == 1
+        eng.set_option("dag", 2)
+        singles = [eng.bp_run(ev, 1e-6) for ev in evs]
+        assert eng.last_path() == 5
+        first = eng.bp_run_batch(evs[2:], 1e-6)      # three sets, the DAG path: the host block comes to hold three sets' arrays
+        eng.set_option("multisweep", 0)
+        eng.bp_run_batch(evs[:3], 1e-6)              # per-sweep launches: staged in device memory
+        assert eng.last_path() == 0
+        eng.set_option("multisweep", 1)
+        out = eng.bp_run_batch(evs[:2], 1e-6)        # the DAG path again, fewer sets: the host block is large enough as it is
+        assert eng.last_path() == 5 and eng.info("dag_aborts") == 0
+        for q in range(2):
+            assert out["sweeps"][q] == singles[q]["sweeps"] and np.array_equal(out["beliefs"][q], singles[q]["beliefs"]), q
+        for q in range(3):
+            assert np.array_equal(first["beliefs"][q], singles[2 + q]["beliefs"]), q
+
+
 def test_dag_batch_rerun_on_staged_evidence(Engine):
     """bn_bp_run_batch_device again and again on ONE bn_bp_set_evidence_batch (what a caller with standing evidence sets does, and what
     bench.py times): a batch that fits one launch leaves its evidence in the state slots between runs (an observed node's vectors are
