@@ -98,6 +98,11 @@ SYMBOLS = [
     ("bn_bp_copy_beliefs_batch", ctypes.c_int, [ctypes.c_void_p, f64p]),
     ("bn_bp_residual_history_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
     ("bn_bp_messages", ctypes.c_int, [ctypes.c_void_p, f64p, f64p]),
+    ("bn_mpe_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, f64p, ctypes.c_double, ctypes.c_int32, f64p, i32p, i32p, f64p, i32p]),
+    ("bn_mpe_run_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, f64p, ctypes.c_double, ctypes.c_int32, f64p, i32p,
+                                        i32p, f64p, i32p]),
+    ("bn_mpe_residual_history", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
+    ("bn_mpe_messages", ctypes.c_int, [ctypes.c_void_p, f64p, f64p]),
     ("bn_set_option", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),
     ("bn_bp_last_path", ctypes.c_int, [ctypes.c_void_p]),
     ("bn_get_info", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),

@@ -336,6 +336,11 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
     if (std::strcmp(name, "poll_sleep") == 0) { e->poll_sleep = std::max(0, std::min(value, 64)); return BN_OK; }
     if (std::strcmp(name, "multisweep") == 0) { e->multisweep = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
     if (std::strcmp(name, "score_splits") == 0) { e->score.splits = std::max(0, std::min(value, 65535)); return BN_OK; }
+    if (std::strncmp(name, "mpe_", 4) == 0) {   // max-product: "mpe_form", "mpe_group" (bn_engine_mpe.cpp)
+        bool known = false;
+        const int rc = mpe_set_option(e, name, value, &known);
+        if (known) return rc;
+    }
     return fail(BN_ERR_ARG, std::string("unknown option ") + name);
 }
 // Introspection for tests and tools: a named integer property of the engine / its last run.
@@ -395,6 +400,11 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strcmp(name, "small_eligible") == 0) return e->small.ok ? 1 : 0;
     if (std::strcmp(name, "small_waves") == 0) return e->small.ok ? e->small.waves : 0;
     if (std::strcmp(name, "small_lds_bytes") == 0) return e->small.ok ? int64_t(e->small.lds_bytes) : 0;
+    if (std::strncmp(name, "mpe_", 4) == 0) {   // max-product: "mpe_form", "mpe_last_form", ... (bn_engine_mpe.cpp)
+        bool known = false;
+        const int64_t v = mpe_get_info(e, name, &known);
+        if (known) return v;
+    }
     return fail(BN_ERR_ARG, std::string("unknown info ") + name);
 }
 // 0 per-sweep launches, 2 resident tiles (bn_resident.hip), 3 one workgroup with the state in LDS (bn_small.hip), 4 the same items over several workgroups (bn_mid.hip)

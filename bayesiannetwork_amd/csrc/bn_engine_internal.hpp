@@ -36,6 +36,7 @@
 #include "bn_buffer.hpp"
 #include "bn_engine_policy.hpp"
 #include "bn_batch_stage.hpp"
+#include "bn_maxprod.hpp"
 
 using namespace bnmi;
 
@@ -122,6 +123,51 @@ struct ScoreState {
     DeviceBuf<int32_t> d_k, d_in_ptr, d_in_idx;
     DeviceBuf<int64_t> d_cpt_off;
     float last_rows_ms = 0.0f, last_count_ms = 0.0f, last_nodes_ms = 0.0f;   // device-event times of the last calls' kernels
+};
+
+// Max-product (bn_engine_mpe.cpp, bn_maxprod.hip): everything its runs need beyond the item tables of the sum-product paths, allocated at
+// the first run.  Nothing here is read or written by a bn_bp_* call, and a bn_mpe_* call touches nothing else of the engine.
+struct MpeState {
+    int form_option = 0;            // option "mpe_form": 0 the rule (bn_policy::mpe_form), 1 one workgroup, 2 several workgroups
+    int group = kMpeDefaultGroup;   // option "mpe_group": sweep launches between two reads of the control record (several-workgroup form)
+    bool small_ready = false, mid_ready = false;   // the form's kernels are prepared, its state allocated
+    DeviceBuf<int32_t> d_elem_node; // [N] node of a node-vector element (the lanes that decode a node's state)
+    int32_t cap_sets = 0, res_cap = 0;   // what the per-set buffers below were sized for
+    PinnedBuf<double> h_mm;         // [cap_sets][N] max-marginals: mapped, the kernels write them here themselves (no copy command
+    double* h_mm_dev = nullptr;     //   behind the run: the results are there when the run's one synchronisation returns)
+    PinnedBuf<int32_t> h_states;    // [cap_sets][n], the same
+    int32_t* h_states_dev = nullptr;
+    DeviceBuf<double> d_res_hist;   // [cap_sets][res_cap]
+    PinnedBuf<MpeCtl> h_ctl;        // [cap_sets], mapped: the kernels write it themselves
+    MpeCtl* h_ctl_dev = nullptr;
+    PinnedBuf<char> h_ev;           // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
+    char* h_ev_dev = nullptr;
+    size_t h_ev_cap = 0;
+    DeviceBuf<double> d_s_state;    // one workgroup: [small_state_sets][2 M + 2 N] the state each set's run stopped in
+    int32_t small_state_sets = 0;
+    DeviceBuf<double> d_m_state;    // several workgroups: pi[2][M], lam[2][M], npi[2][N], nlam[2][N]
+    DeviceBuf<uint8_t> d_m_frz;
+    DeviceBuf<MpeMidSync> d_m_sync;
+    // A network the engine has no several-workgroup plan for because ONE workgroup holds it (bn_create builds that plan only for the
+    // others, and the sum-product path choice must not see one here): option "mpe_form" 2 builds a plan and tables of the max-product
+    // run's own at its first use; bn_reload_cpt drops them.
+    MidPlan own_mid;
+    bool own_tried = false, own_uploaded = false;
+    DeviceBuf<MidPart> d_o_parts;
+    DeviceBuf<SmallEntry> d_o_ent;
+    DeviceBuf<double> d_o_cpt;
+    DeviceBuf<uint32_t> d_o_term;
+    DeviceBuf<uint16_t> d_o_clist;
+    DeviceBuf<SmallSlot> d_o_bslot, d_o_cslot;
+    DeviceBuf<double> d_o_init;
+    DeviceBuf<int32_t> d_o_nodeoff;
+    uint32_t run_id = 0;
+    // the last call
+    bool have_run = false, last_single = false;
+    int last_form = 0;
+    int32_t n_sets = 0, last_groups = 0;
+    int64_t last_device_ns = 0;
+    std::vector<int32_t> sweeps;
 };
 
 struct bn_engine {
@@ -343,6 +389,7 @@ struct bn_engine {
     int grid_tiles = 0;              // blocks for one-wave-per-tile kernels without remap
     LwState lw;
     ScoreState score;
+    MpeState mpe;
 };
 
 
@@ -432,6 +479,10 @@ void note_run_result(bn_engine* e);
 int run_per_sweep(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to);
 int run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_t* sweeps_out, double* residual_out, double* copy_to);
 void resident_ran_ok(bn_engine* e);
+// the "mpe_*" names of bn_set_option / bn_get_info (bn_engine_mpe.cpp); *known = false: not one of them
+int mpe_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
+int64_t mpe_get_info(bn_engine* e, const char* name, bool* known);
+void mpe_cpt_reloaded(bn_engine* e);   // bn_reload_cpt: what max-product built from the old tables is dropped
 }  // namespace bn_eng
 
 #endif  // BN_ENGINE_INTERNAL_HPP

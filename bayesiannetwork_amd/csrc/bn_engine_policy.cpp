@@ -196,4 +196,15 @@ int32_t mid_sets_per_launch(int n_cus, int32_t parts, int32_t n_sets) { return s
 // (scripts/time_dag_batch.py)
 int32_t dag_sets_per_launch(int forced) { return forced == 0 ? kDagMaxSets : std::max(1, std::min(kDagMaxSets, forced)); }
 
+// Max-product (bn_mpe_run, bn_maxprod.hip): the one-workgroup form wherever the one-workgroup plan exists, else the several-workgroup
+// form where its plan exists and its workgroups fit 0.9 x CUs (one launch per sweep needs no co-residency, but the same bound keeps a
+// sweep one wave of workgroups), else none.  forced: option "mpe_form" -- 1 / 2 give that form where the network is eligible for it,
+// else none.
+int mpe_form(const PathFacts& f, int n_cus, int forced) {
+    const bool one = f.small.ok, several = f.mid.ok && mid_fits(f, n_cus);
+    if (forced == 1) return one ? 1 : 0;
+    if (forced == 2) return several ? 2 : 0;
+    return one ? 1 : (several ? 2 : 0);
+}
+
 }  // namespace bn_policy

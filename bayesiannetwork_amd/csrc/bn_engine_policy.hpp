@@ -85,6 +85,10 @@ std::vector<int32_t> resident_batch_chunks(int32_t n_sets);              // bala
 int32_t mid_sets_per_launch(int n_cus, int32_t parts, int32_t n_sets);   // a workgroup per CU within 0.9 x CUs, at least one set
 int32_t dag_sets_per_launch(int forced);                                 // forced: BN_DAG_SETS (0: not set) -> 1..kDagMaxSets
 
+// ---- max-product (bn_mpe_run): which form of bn_maxprod.hip runs a network.  0 none, 1 one workgroup, 2 several workgroups.
+// forced: option "mpe_form" (0: the rule, 1 / 2: that form or none)
+int mpe_form(const PathFacts& f, int n_cus, int forced);
+
 }  // namespace bn_policy
 
 #endif  // BN_ENGINE_POLICY_HPP

@@ -165,6 +165,47 @@ class Engine:
         _lib.check(_lib.lib().bn_bp_messages(self._h, _p(pi, ctypes.c_double), _p(lam, ctypes.c_double)))
         return pi[:nm], lam[:nm]
 
+    # ---- most probable explanation: max-product belief propagation (bn_mpe_*) -----------------
+    def mpe_run(self, evidence: Evidence | None = None, eps: float = 0.001, max_sweeps: int = 0):
+        """bn_mpe_run: evidence in; the decoded joint assignment ("states", int32 [n]), every node's normalised max-marginal
+        ("max_marginals", node-major [sum k]), "sweeps", "residual" and "converged" out.  max_sweeps = 0 is a cap of 10 000
+        sweeps, not unbounded: "converged" is False for a run the cap cut."""
+        ev = evidence if evidence is not None else Evidence.none()
+        sweeps, conv, res = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(0.0)
+        mm = np.empty(self._nbel, dtype=np.float64)
+        st = np.empty(self.model.n, dtype=np.int32)
+        _lib.check(_lib.lib().bn_mpe_run(self._h, ev.ne, _p(ev.node, ctypes.c_int32), _p(ev.off, ctypes.c_int32), _p(ev.val, ctypes.c_double),
+                                         float(eps), int(max_sweeps), _p(mm, ctypes.c_double), _p(st, ctypes.c_int32), ctypes.byref(sweeps),
+                                         ctypes.byref(res), ctypes.byref(conv)))
+        return {"states": st, "max_marginals": mm, "sweeps": sweeps.value, "residual": res.value, "converged": bool(conv.value)}
+
+    def mpe_run_batch(self, evidences, eps: float = 0.001, max_sweeps: int = 0):
+        """bn_mpe_run_batch: several evidence sets in one call; set q gets exactly what mpe_run(evidences[q]) returns.
+        "states" [n_sets, n], "max_marginals" [n_sets, sum k], "sweeps" / "residual" / "converged" [n_sets]."""
+        ne, node, off, val = self._pack_sets(evidences)
+        B = int(ne.size)
+        mm = np.empty((B, self._nbel), dtype=np.float64)
+        st = np.empty((B, self.model.n), dtype=np.int32)
+        sweeps, conv, res = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float64)
+        _lib.check(_lib.lib().bn_mpe_run_batch(self._h, B, _p(ne, ctypes.c_int32), _p(node, ctypes.c_int32), _p(off, ctypes.c_int32),
+                                               _p(val, ctypes.c_double), float(eps), int(max_sweeps), _p(mm, ctypes.c_double),
+                                               _p(st, ctypes.c_int32), _p(sweeps, ctypes.c_int32), _p(res, ctypes.c_double),
+                                               _p(conv, ctypes.c_int32)))
+        return {"states": st, "max_marginals": mm, "sweeps": sweeps, "residual": res, "converged": conv.astype(bool)}
+
+    def mpe_residuals(self, set: int = 0, cap: int = 65536) -> np.ndarray:
+        """Per-sweep maximum_difference of evidence set `set` of the last mpe_run / mpe_run_batch."""
+        out = np.zeros(cap, dtype=np.float64)
+        cnt = _lib.check(_lib.lib().bn_mpe_residual_history(self._h, int(set), _p(out, ctypes.c_double), cap))
+        return out[:cnt].copy()
+
+    def mpe_messages(self):
+        """Final pi- and lambda-messages of the last mpe_run, laid out as bp_messages()."""
+        nm = int(self.model.k[self.model.in_idx].sum()) if self.model.n_edges else 0
+        pi, lam = np.zeros(max(nm, 1)), np.zeros(max(nm, 1))
+        _lib.check(_lib.lib().bn_mpe_messages(self._h, _p(pi, ctypes.c_double), _p(lam, ctypes.c_double)))
+        return pi[:nm], lam[:nm]
+
     def bp_stats(self) -> dict:
         st = _lib.BpStats()
         _lib.check(_lib.lib().bn_bp_last_stats(self._h, ctypes.byref(st)))
@@ -540,6 +581,54 @@ class BeliefPropagation:
         for b in range(0, len(evs), _lib.BN_MAX_BATCH_SETS):
             self.last = self.engine.bp_run_batch(evs[b:b + _lib.BN_MAX_BATCH_SETS], epsilon)
             out += [_split(self.model, bel) for bel in self.last["beliefs"]]
+        return out
+
+
+class MaxProduct:
+    """Most probable explanation by max-product belief propagation -- not in the reference; the surface of
+    ``BeliefPropagation``: ``mp = MaxProduct(model); states, logp = mp.mpe({node: state})``.
+
+    ``mp(precondition, epsilon, max_sweeps)`` returns the list of per-node max-marginal vectors (normalised), ``mp.mpe(...)``
+    the decoded joint assignment and its log probability.  Exact on polytrees; on loopy networks an approximation that may not
+    converge: ``max_sweeps = 0`` is a cap of 10 000 sweeps, and ``self.last["converged"]`` tells."""
+
+    def __init__(self, model: FlatModel, device: int = _lib.BN_DEVICE_CURRENT):
+        self.engine = Engine(model, device)
+        self.model = model
+        self.last = None
+
+    def _evidence(self, precondition):
+        return Evidence.from_dict(self.model, precondition) if isinstance(precondition, dict) else precondition
+
+    def __call__(self, precondition=None, epsilon: float = 0.001, max_sweeps: int = 0):
+        self.last = self.engine.mpe_run(self._evidence(precondition), epsilon, max_sweeps)
+        return _split(self.model, self.last["max_marginals"])
+
+    def log_probability(self, states) -> float:
+        """log P(states): sum over the nodes, in node order, of log cpt_v[row(states)][states_v] (fp64, on the host) -- the log
+        joint of a complete assignment, evidence nodes included."""
+        m, total = self.model, 0.0
+        for v in range(m.n):
+            row = 0
+            for u in m.parents(v):   # first parent most significant, own state fastest (FlatModel)
+                row = row * int(m.k[u]) + int(states[u])
+            with np.errstate(divide="ignore"):
+                total += float(np.log(m.cpt[int(m.cpt_off[v]) + row * int(m.k[v]) + int(states[v])]))
+        return total
+
+    def mpe(self, precondition=None, epsilon: float = 0.001, max_sweeps: int = 0):
+        """(states, log_probability): the decoded assignment (int32 [n]) and its log joint probability."""
+        self.last = self.engine.mpe_run(self._evidence(precondition), epsilon, max_sweeps)
+        return self.last["states"], self.log_probability(self.last["states"])
+
+    def run_batch(self, preconditions, epsilon: float = 0.001, max_sweeps: int = 0):
+        """Several evidence sets in one call: a list of (states, log_probability), entry q exactly what
+        ``self.mpe(preconditions[q], ...)`` returns.  Lists longer than BN_MAX_BATCH_SETS go in slices."""
+        evs = [self._evidence(p) for p in preconditions]
+        out = []
+        for b in range(0, len(evs), _lib.BN_MAX_BATCH_SETS):
+            self.last = self.engine.mpe_run_batch(evs[b:b + _lib.BN_MAX_BATCH_SETS], epsilon, max_sweeps)
+            out += [(st, self.log_probability(st)) for st in self.last["states"]]
         return out
 
 

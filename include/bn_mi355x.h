@@ -184,6 +184,45 @@ int bn_bp_residual_history_batch(bn_engine *eng, int32_t set, double *out, int32
 int bn_bp_residual_history(bn_engine *eng, double *out, int32_t cap);
 int bn_bp_messages(bn_engine *eng, double *pi_msg_out, double *lambda_msg_out);
 
+/*
+ * Most probable explanation (MPE / MAP, Pearl's belief revision): MAX-PRODUCT belief propagation -- an extension beside the
+ * drop-in, the reference has no such functor.  The loop is belief_propagation.hpp:33-158 with one line changed: pi(v) (:174-200)
+ * and the lambda-message to a parent (:240-266) take the LARGEST term over the parent assignments where sum-product adds them;
+ * products, normalisation, evidence, residual, the strict `<` of the stop decision and belief = normalize(pi % lambda) are
+ * unchanged.  Exact on polytrees once the messages have crossed the graph; on loopy networks an approximation that may oscillate.
+ *   The fold:   acc = +0.0; for every term x: acc = (acc < x) ? x : acc -- a NaN term never replaces acc, the order of the
+ *               terms does not matter.
+ *   The state:  of the node's normalised max-marginal vector b: idx = 0, best = b[0]; for i = 1..k-1: if (b[i] > best) take i
+ *               -- the LOWEST index holding the largest element; a vector of NaNs (all-zero evidence: 0 / 0) gives state 0.
+ *   max_sweeps: 0 means a cap of 10 000 sweeps, NOT unbounded as in bn_bp_run: a loopy max-product run need not converge, and
+ *               a loop without an end on the device is a hang.  converged_out: 1 = maximum_difference < eps, 0 = cut by the cap.
+ * Evidence arguments and their checks are those of bn_bp_run / bn_bp_run_batch (layout of the batch arrays: see there).
+ *   max_marginals_out : [sum k] (batch: [n_sets][sum k]) node-major, each node's vector normalised
+ *   states_out        : [n]     (batch: [n_sets][n])     the decoded state of every node, evidence nodes included
+ *   sweeps_out / residual_out / converged_out : one value (batch: [n_sets]); may be NULL
+ * Two forms (bn_get_info "mpe_form": the one the next run takes, 0 none; "mpe_last_form"): 1 = networks that fit ONE workgroup
+ * (the "small" plan: the whole run in one launch, state in LDS; a batch runs one workgroup per set), 2 = networks of the "mid"
+ * plan (several workgroups, state in device memory, one launch per sweep, stop decision on the device; a batch runs set after
+ * set).  Networks with neither plan -- a node with more than 8 parents, more than 224 workgroups' worth -- sharded engines and
+ * BN_DEVICE_HOST_ONLY engines: BN_ERR_STATE, bn_last_error names the limit.  bn_set_option "mpe_form" 0 (default: form 1 where
+ * eligible, else 2) / 1 / 2: forcing a form the network is not eligible for gives BN_ERR_STATE at the run (2 on a network that
+ * fits one workgroup: the engine keeps no "mid" plan for those, max-product builds one of its own at the first use;
+ * bn_get_info "mpe_parts": the workgroups of form 2); "mpe_group" 1..64: form 2 enqueues that many sweeps between two reads of
+ * its control record (default 16, chosen by measurement: DESIGN 4.16).
+ * A bn_mpe_* call leaves everything the bn_bp_* calls use as it was -- evidence in force, batch staging, bn_bp_messages,
+ * bn_bp_last_path -- and the other way round; bn_reload_cpt reaches the tables of both.
+ * bn_mpe_residual_history: per-sweep maximum_difference of set `set` of the last bn_mpe_run* (returns the count written);
+ * bn_mpe_messages: final pi / lambda messages of the last bn_mpe_run (not of a batch), laid out as by bn_bp_messages.
+ */
+int bn_mpe_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int32_t *ev_off, const double *ev_val, double eps,
+               int32_t max_sweeps, double *max_marginals_out, int32_t *states_out, int32_t *sweeps_out, double *residual_out,
+               int32_t *converged_out);
+int bn_mpe_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const int32_t *ev_node, const int32_t *ev_off,
+                     const double *ev_val, double eps, int32_t max_sweeps, double *max_marginals_out, int32_t *states_out,
+                     int32_t *sweeps_out, double *residual_out, int32_t *converged_out);
+int bn_mpe_residual_history(bn_engine *eng, int32_t set, double *out, int32_t cap);
+int bn_mpe_messages(bn_engine *eng, double *pi_msg_out, double *lambda_msg_out);
+
 /* Options: "timing" 1/0 -- HIP events on the engine's stream around every batch of sweep launches
  * (bn_bp_stats.sweep_kernel_ms).  Default 0 (BN_TIMING=1 in the environment turns it on): an event
  * record between two launches opens a bubble of several microseconds in the queue, so a timed run is
