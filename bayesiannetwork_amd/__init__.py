@@ -10,7 +10,8 @@ from . import synth  # noqa: F401
 _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters")
 _LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure", "TermTable",
              "SimulatedAnnealing", "StepwiseStructureHC")
-__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING]
+_EM = ("MISSING", "em_expected_counts", "em_fit")
+__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING, *_EM]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in _LEARNING:
         from . import learning
         return getattr(learning, name)
+    if name in _EM:   # expectation-maximisation (engine.py): CPTs from a table with unobserved cells
+        from . import engine
+        return getattr(engine, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,6 +16,7 @@ _LIB = None
 BN_OK, BN_ERR_ARG, BN_ERR_HIP, BN_ERR_NO_DEVICE, BN_ERR_ALLOC, BN_ERR_COMM, BN_ERR_STATE = 0, -1, -2, -3, -4, -5, -6
 BN_DEVICE_HOST_ONLY, BN_DEVICE_CURRENT = -2, -1
 BN_MAX_BATCH_SETS = 256  # include/bn_mi355x.h
+BN_EM_MISSING = 255
 
 i32p = ctypes.POINTER(ctypes.c_int32)
 i64p = ctypes.POINTER(ctypes.c_int64)
@@ -44,6 +45,11 @@ class AnnealParams(ctypes.Structure):
 class HcParams(ctypes.Structure):
     _fields_ = [("alpha", ctypes.c_double), ("max_parents", ctypes.c_int32), ("trace_run", ctypes.c_int32),
                 ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class EmOptions(ctypes.Structure):   # bn_em_options
+    _fields_ = [("max_iters", ctypes.c_int32), ("tol", ctypes.c_double), ("bp_eps", ctypes.c_double), ("bp_max_sweeps", ctypes.c_int32),
+                ("prior", ctypes.c_double)]
 
 
 class ScoreSpec(ctypes.Structure):
@@ -103,6 +109,10 @@ SYMBOLS = [
                                         i32p, f64p, i32p]),
     ("bn_mpe_residual_history", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
     ("bn_mpe_messages", ctypes.c_int, [ctypes.c_void_p, f64p, f64p]),
+    ("bn_em_expected_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_double, ctypes.c_int32,
+                                             f64p, i32p]),
+    ("bn_em_fit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(EmOptions), f64p, f64p, i32p,
+                                 f64p, ctypes.c_int32]),
     ("bn_set_option", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),
     ("bn_bp_last_path", ctypes.c_int, [ctypes.c_void_p]),
     ("bn_get_info", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),

@@ -341,6 +341,11 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
         const int rc = mpe_set_option(e, name, value, &known);
         if (known) return rc;
     }
+    if (std::strncmp(name, "em_", 3) == 0) {   // expectation-maximisation: "em_scratch_cells" (bn_engine_em.cpp)
+        bool known = false;
+        const int rc = em_set_option(e, name, value, &known);
+        if (known) return rc;
+    }
     return fail(BN_ERR_ARG, std::string("unknown option ") + name);
 }
 // Introspection for tests and tools: a named integer property of the engine / its last run.
@@ -403,6 +408,11 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strncmp(name, "mpe_", 4) == 0) {   // max-product: "mpe_form", "mpe_last_form", ... (bn_engine_mpe.cpp)
         bool known = false;
         const int64_t v = mpe_get_info(e, name, &known);
+        if (known) return v;
+    }
+    if (std::strncmp(name, "em_", 3) == 0) {   // expectation-maximisation: "em_eligible", "em_last_iters", ... (bn_engine_em.cpp)
+        bool known = false;
+        const int64_t v = em_get_info(e, name, &known);
         if (known) return v;
     }
     return fail(BN_ERR_ARG, std::string("unknown info ") + name);

@@ -37,6 +37,7 @@
 #include "bn_engine_policy.hpp"
 #include "bn_batch_stage.hpp"
 #include "bn_maxprod.hpp"
+#include "bn_em.hpp"
 
 using namespace bnmi;
 
@@ -168,6 +169,33 @@ struct MpeState {
     int32_t n_sets = 0, last_groups = 0;
     int64_t last_device_ns = 0;
     std::vector<int32_t> sweeps;
+};
+
+// Expectation-maximisation (bn_engine_em.cpp, bn_em.hip): its own images of the CPT values (the entry items' table, the roots' initial
+// pi(v)), the index maps between them and the flat array, the table, the scratch of family posteriors and the sums -- allocated at the
+// first call.  Nothing here is read or written by a bn_bp_* / bn_mpe_* call, and a bn_em_* call touches nothing else of the engine.
+struct EmState {
+    int64_t scratch_cells = bn_policy::kEmScratchCells;   // option "em_scratch_cells": doubles of the posteriors' scratch array
+    bool ready = false;                 // kernels prepared, maps uploaded, images and sums allocated
+    std::vector<int32_t> slot_of;       // [entries] flat CPT entry -> its slot in the entry items' table
+    std::vector<int32_t> init_of;       // [entries] flat CPT entry -> element of the initial pi(v) (a root's), -1: none
+    DeviceBuf<int32_t> d_ent_flat;      // [slots] the inverse | (first entry of its family) << 16, -1: no entry
+    DeviceBuf<int32_t> d_slot_of, d_init_of;
+    DeviceBuf<uint32_t> d_row;          // [entries] first entry of the CPT row | arity << 16
+    DeviceBuf<double> d_cpt, d_init;    // the images the E-step kernel reads, rewritten by every M-step
+    DeviceBuf<double> d_theta;          // [entries] flat
+    DeviceBuf<double> d_E, d_partial;   // [entries] the sum, and the 256-block in hand
+    DeviceBuf<unsigned long long> d_words;   // [0] runs cut by the cap, [1] skipped families, [2] delta's bit pattern
+    DeviceBuf<uint8_t> d_patterns;      // the table of the call
+    DeviceBuf<unsigned long long> d_counts;
+    DeviceBuf<int32_t> d_sweeps;        // [patterns] of the last E-step
+    int64_t cap_patterns = 0;
+    DeviceBuf<double> d_b;              // [chunk][entries] family posteriors of the launch in hand
+    int64_t cap_b = 0;
+    EventOwner ev[3];                   // E-step begins, E-step ends, M-step ends
+    // the last call
+    int32_t last_iters = 0;
+    int64_t capped = 0, skipped = 0, estep_ns = 0, mstep_ns = 0;
 };
 
 struct bn_engine {
@@ -390,6 +418,7 @@ struct bn_engine {
     LwState lw;
     ScoreState score;
     MpeState mpe;
+    EmState em;
 };
 
 
@@ -483,6 +512,9 @@ void resident_ran_ok(bn_engine* e);
 int mpe_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t mpe_get_info(bn_engine* e, const char* name, bool* known);
 void mpe_cpt_reloaded(bn_engine* e);   // bn_reload_cpt: what max-product built from the old tables is dropped
+// the "em_*" names (bn_engine_em.cpp)
+int em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
+int64_t em_get_info(bn_engine* e, const char* name, bool* known);
 }  // namespace bn_eng
 
 #endif  // BN_ENGINE_INTERNAL_HPP

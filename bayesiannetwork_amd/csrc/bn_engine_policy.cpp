@@ -207,4 +207,25 @@ int mpe_form(const PathFacts& f, int n_cus, int forced) {
     return one ? 1 : (several ? 2 : 0);
 }
 
+// Expectation-maximisation: as many rows per launch as the scratch array holds (at least one, at most kEmMaxChunk and the table).
+EmPlan em_plan(int64_t n_patterns, int32_t entries, int64_t scratch_cells) {
+    EmPlan p;
+    const int64_t fit = scratch_cells / std::max<int64_t>(entries, 1);
+    p.chunk = int32_t(std::max<int64_t>(1, std::min<int64_t>({fit, int64_t(kEmMaxChunk), n_patterns})));
+    p.n_chunks = (n_patterns + p.chunk - 1) / p.chunk;
+    p.n_blocks = (n_patterns + kEmBlock - 1) / kEmBlock;
+    p.scratch = int64_t(p.chunk) * entries;
+    return p;
+}
+
+EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c) {
+    EmChunk k;
+    k.first = c * p.chunk;
+    k.count = int32_t(std::min<int64_t>(p.chunk, n_patterns - k.first));
+    const int64_t end = k.first + k.count;   // one past the chunk's last row
+    k.closes = int32_t(end / kEmBlock - k.first / kEmBlock) + (end == n_patterns && end % kEmBlock != 0 ? 1 : 0);
+    k.opens_inside = k.first % kEmBlock != 0;
+    return k;
+}
+
 }  // namespace bn_policy

@@ -89,6 +89,29 @@ int32_t dag_sets_per_launch(int forced);                                 // forc
 // forced: option "mpe_form" (0: the rule, 1 / 2: that form or none)
 int mpe_form(const PathFacts& f, int n_cus, int forced);
 
+// ---- expectation-maximisation (bn_em_*, bn_em.hpp): how the pattern rows of an E-step are cut into launches, and where the sums of
+// the 256-blocks of the E sum close.  A launch runs `chunk` rows, one workgroup each, and leaves chunk x entries family posteriors in a
+// scratch array of at most scratch_cells doubles (option "em_scratch_cells"); chunk boundaries need not fall on block boundaries -- the
+// accumulating kernel carries the block in hand across them -- so the result does not depend on the cut.
+constexpr int32_t kEmBlock = 256;                 // (bn_em.hpp has the original)
+constexpr int64_t kEmScratchCells = 1ll << 22;    // 32 MiB of doubles: 4 096 rows of an ALARM-sized network in one launch
+constexpr int32_t kEmMaxChunk = 1 << 16;          // workgroups of one launch
+struct EmPlan {
+    int32_t chunk = 0;        // rows per launch (the last launch may have fewer)
+    int64_t n_chunks = 0;
+    int64_t n_blocks = 0;     // block sums added into E
+    int64_t scratch = 0;      // doubles of the scratch array: chunk x entries
+};
+struct EmChunk {
+    int64_t first = 0;        // global index of the chunk's first row
+    int32_t count = 0;
+    int32_t closes = 0;       // block sums that close inside the chunk (a block closes at its 256th row, the last one at the table's last row)
+    bool opens_inside = false;   // the chunk's first row is not the first of a block: it continues the sum the chunk before left
+};
+// n_patterns >= 1, entries >= 1; scratch_cells < entries still gives one row per launch
+EmPlan em_plan(int64_t n_patterns, int32_t entries, int64_t scratch_cells);
+EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c);
+
 }  // namespace bn_policy
 
 #endif  // BN_ENGINE_POLICY_HPP

@@ -17,6 +17,9 @@ from . import _lib
 from .flat import Evidence, FlatModel
 
 
+MISSING = _lib.BN_EM_MISSING   # a pattern cell that is not observed (em_expected_counts, em_fit)
+
+
 def _p(a, ct):
     return a.ctypes.data_as(ctypes.POINTER(ct))
 
@@ -205,6 +208,46 @@ class Engine:
         pi, lam = np.zeros(max(nm, 1)), np.zeros(max(nm, 1))
         _lib.check(_lib.lib().bn_mpe_messages(self._h, _p(pi, ctypes.c_double), _p(lam, ctypes.c_double)))
         return pi[:nm], lam[:nm]
+
+    # ---- expectation-maximisation: CPTs from a table with unobserved cells (bn_em_*) ------------
+    def _em_table(self, patterns, counts):
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8).reshape(-1, max(self.model.n, 1))
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.shape[0] != patterns.shape[0]:
+            raise ValueError("one count per pattern")
+        return patterns, counts
+
+    def em_expected_counts(self, patterns, counts, bp_eps: float = 1e-3, bp_max_sweeps: int = 0):
+        """bn_em_expected_counts: ONE E-step under the engine's current tables.  patterns [P][n] uint8 with MISSING (255) for an
+        unobserved cell, counts [P].  Returns (E [entries], the expected family counts in the flat CPT layout; sweeps int32 [P], the
+        belief-propagation sweeps of each row's run).  bp_max_sweeps == 0: a cap of 10 000 sweeps."""
+        patterns, counts = self._em_table(patterns, counts)
+        E = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        sweeps = np.zeros(max(patterns.shape[0], 1), dtype=np.int32)
+        _lib.check(_lib.lib().bn_em_expected_counts(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64),
+                                                    float(bp_eps), int(bp_max_sweeps), _p(E, ctypes.c_double), _p(sweeps, ctypes.c_int32)))
+        return E, sweeps[:patterns.shape[0]]
+
+    def em_fit(self, patterns, counts, max_iters: int = 100, tol: float = 1e-6, bp_eps: float = 1e-3, bp_max_sweeps: int = 0,
+               prior: float = 0.0, cpt_init=None, reload: bool = False):
+        """bn_em_fit: expectation-maximisation from cpt_init (flat, the model's layout; None: the engine's current tables) until the
+        largest change of a table entry is below tol or max_iters iterations have run.  Returns (cpt [entries], iterations,
+        delta_history [iterations]).  The engine's tables are not touched unless reload=True, which applies the result with
+        reload_cpt()."""
+        patterns, counts = self._em_table(patterns, counts)
+        opt = _lib.EmOptions(int(max_iters), float(tol), float(bp_eps), int(bp_max_sweeps), float(prior))
+        init = None if cpt_init is None else np.ascontiguousarray(cpt_init, dtype=np.float64)
+        if init is not None and init.shape[0] != int(self.model.cpt_off[-1]):
+            raise ValueError("cpt_init must have one value per CPT entry")
+        cpt = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        cap = max(1, min(int(max_iters), 10000))
+        hist = np.zeros(cap, dtype=np.float64)
+        iters = ctypes.c_int32(0)
+        _lib.check(_lib.lib().bn_em_fit(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), ctypes.byref(opt),
+                                        None if init is None else _p(init, ctypes.c_double), _p(cpt, ctypes.c_double), ctypes.byref(iters), _p(hist, ctypes.c_double), cap))
+        if reload:
+            self.reload_cpt(cpt)
+        return cpt, int(iters.value), hist[:iters.value].copy()
 
     def bp_stats(self) -> dict:
         st = _lib.BpStats()
@@ -447,6 +490,20 @@ def fit_cpt(model: FlatModel, patterns, counts, device: int = _lib.BN_DEVICE_CUR
     _lib.check(_lib.lib().bn_fit_cpt(ctypes.byref(d), patterns.shape[0], _p(patterns, ctypes.c_uint8),
                                      _p(counts, ctypes.c_uint64), _p(out, ctypes.c_double)))
     return out
+
+
+def em_expected_counts(model: FlatModel, patterns, counts, bp_eps: float = 1e-3, bp_max_sweeps: int = 0,
+                       device: int = _lib.BN_DEVICE_CURRENT):
+    """Engine.em_expected_counts on an engine made for the call: one E-step under model.cpt."""
+    with Engine(model, device=device) as eng:
+        return eng.em_expected_counts(patterns, counts, bp_eps, bp_max_sweeps)
+
+
+def em_fit(model: FlatModel, patterns, counts, device: int = _lib.BN_DEVICE_CURRENT, **kw):
+    """Engine.em_fit on an engine made for the call: (cpt, iterations, delta_history), starting from model.cpt unless cpt_init is given."""
+    kw.pop("reload", None)
+    with Engine(model, device=device) as eng:
+        return eng.em_fit(patterns, counts, **kw)
 
 
 class Sampler:

@@ -223,6 +223,53 @@ int bn_mpe_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const in
 int bn_mpe_residual_history(bn_engine *eng, int32_t set, double *out, int32_t cap);
 int bn_mpe_messages(bn_engine *eng, double *pi_msg_out, double *lambda_msg_out);
 
+/*
+ * Expectation-maximisation: CPTs fitted from a table with UNOBSERVED cells -- an extension beside the drop-in (sampler::make_cpt and
+ * bn_fit_cpt count complete rows only).  The E-step is belief propagation: every pattern row is one sum-product query with the
+ * observed cells as hard evidence, one workgroup per row on the one-workgroup path, and from the state each run stops in the family
+ * posteriors P(x_v, pa(v) | e) are taken and added, weighted by the row's count; the M-step normalises.  All in fp64.
+ *   patterns [n_patterns][n_nodes] uint8 and counts [n_patterns] uint64 are bn_fit_cpt's layout; a cell of BN_EM_MISSING (255) is
+ *   "not observed".  A row may be fully observed, fully missing or have count 0.  BN_ERR_ARG (checked on the host, before any device
+ *   work): a cell >= k[v] that is not 255 (the text names the pattern and the node), n_patterns < 1, a null pointer, a zero total.
+ * E-step, per pattern, under the current tables: one-hot evidence on the observed nodes; the loop of bn_bp_run with (bp_eps,
+ *   bp_max_sweeps) -- bp_max_sweeps == 0 means a cap of 10 000 sweeps, NOT unbounded (as bn_mpe_run); a run cut by the cap is used as
+ *   it stands and counted -- with the bits of bn_bp_run on the one-workgroup path; then for every node v, parent assignment a (first
+ *   parent most significant) and own state i
+ *       t'[a,i] = cpt[a,i] x the parents' final pi-messages at a, ascending parents   (the term pi(v)[i]'s sum adds)
+ *       r[i] = sum_a t'[a,i] in table order;  s = sum_i r[i] x lambda(v)[i];  b[a,i] = (t'[a,i] x lambda(v)[i]) / s
+ *   (all sums front to back from +0.0).  Where `s > 0` is false -- the evidence has probability 0 under the tables -- the family
+ *   contributes nothing and is counted.  E[q] = sum_p double(counts[p]) x b_p[q], added in blocks of 256 consecutive patterns:
+ *   inside a block in increasing p from +0.0, the block sums in increasing order from +0.0.  E therefore depends on the ORDER of the
+ *   rows, not on how the call cuts them into launches.  On a complete table with strictly positive tables E is the exact counts.
+ * M-step: E'[q] = E[q] + prior; per CPT row tot = sum_i E'[a,i] left to right; theta_new = E' / tot, or 1.0 / k[v] for the whole row
+ *   where `tot > 0` is false.  With prior = 0 on a complete table: bn_fit_cpt's bits.
+ * Loop: delta = max_q |theta_new[q] - theta[q]|; stop after the iteration where delta < tol (strict: tol = 0 never stops early) or
+ *   after max_iters (1..10 000) iterations.  Starts from cpt_init (flat, bn_model_desc.cpt's layout) or, if NULL, from the engine's
+ *   current tables.  The engine's own tables are never written: apply cpt_out with bn_reload_cpt if wanted.
+ *   bn_em_fit: cpt_out [n_entries]; iters_out, delta_hist_out [hist_cap] (the first hist_cap deltas) may be NULL.  BN_ERR_ARG:
+ *   max_iters out of range, prior negative or not finite, tol or bp_eps NaN, bp_max_sweeps < 0.
+ *   bn_em_expected_counts: ONE E-step under the engine's current tables: ecounts_out [n_entries], sweeps_out [n_patterns] or NULL.
+ * Eligible: networks with a one-workgroup plan (bn_get_info "em_eligible"; the "small" option does not matter).  Without one, and on
+ * sharded engines: BN_ERR_STATE, bn_last_error gives the planner's reason.  BN_DEVICE_HOST_ONLY engines: BN_ERR_NO_DEVICE, after the
+ * argument checks.  A bn_em_* call leaves everything the bn_bp_* / bn_mpe_* calls use as it was.
+ * bn_get_info: "em_last_iters"; "em_capped" / "em_skipped": pattern-runs cut by the cap / pattern-families with s not > 0 in the last
+ * call, summed over its iterations; "em_estep_ns" / "em_mstep_ns": device time of the last call's E-step / M-step kernels.
+ * bn_set_option "em_scratch_cells": doubles of the scratch array that holds one launch's posteriors (0: the default, 2^22); it
+ * bounds the rows per launch and changes no result.
+ */
+#define BN_EM_MISSING 255
+typedef struct bn_em_options {
+    int32_t max_iters;
+    double tol;
+    double bp_eps;
+    int32_t bp_max_sweeps;
+    double prior;
+} bn_em_options;
+int bn_em_expected_counts(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const uint64_t *counts, double bp_eps,
+                          int32_t bp_max_sweeps, double *ecounts_out, int32_t *sweeps_out);
+int bn_em_fit(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const uint64_t *counts, const bn_em_options *opt,
+              const double *cpt_init, double *cpt_out, int32_t *iters_out, double *delta_hist_out, int32_t hist_cap);
+
 /* Options: "timing" 1/0 -- HIP events on the engine's stream around every batch of sweep launches
  * (bn_bp_stats.sweep_kernel_ms).  Default 0 (BN_TIMING=1 in the environment turns it on): an event
  * record between two launches opens a bubble of several microseconds in the queue, so a timed run is
