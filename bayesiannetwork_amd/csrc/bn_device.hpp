@@ -103,6 +103,34 @@ struct EvidenceArgs {
     const double* ev_val;
 };
 
+// The first-sweep image of the resident path (bn_kernels.hip memo0_node): what sweep 0 of a run leaves behind -- message records and
+// node vectors in the layout of rec1 / node1, the buffers sweep 1 reads -- computed once per CPT image for the network without
+// evidence and patched per evidence set: the nodes of the new set are recomputed as evidence nodes, the nodes that were in the set
+// before and are not any more as ordinary ones.  A node's slots are written by that node's lane only, the two lists are disjoint.
+// ... as the resident kernel reads it: one record per patch word (device memory, written when the image is built)
+struct Memo0Image {
+    double* rec;
+    const double* node;
+    const unsigned long long* word;   // bit pattern of sweep 0's residual for the evidence the image holds (res_hist[0])
+};
+struct Memo0Args {
+    BpBuffers b;
+    int32_t ne;                   // the set to apply (also written to the tile buffers: marks + vectors, as bp_evidence_kernel does)
+    const int32_t* ev_node;
+    const int32_t* ev_off;
+    const double* ev_val;
+    int32_t n_restore;            // nodes that lose their evidence
+    const int32_t* restore;
+    double* rec;                  // the image: records, node vectors
+    double* node;
+    double* cv;                   // build only: [n] the node's own residual contribution in sweep 0
+    int32_t n;                    // build only: nodes
+    unsigned long long* word;     // the sweep-0 residual's bit pattern: max(seed, the evidence nodes' contributions); zero before the launch
+    unsigned long long* word_next;  // ... the word of the NEXT patch launch, left zero by this one
+    unsigned long long seed;      // largest contribution among the nodes WITHOUT evidence (bit pattern; the host knows it)
+    int32_t spread;               // patch: one node per 2^spread lanes (0..6)
+};
+
 // The whole run in one launch with every tile resident in registers (bn_resident.hip).
 constexpr int kResidentWaves = 8;       // 512 threads per block, one tile per wave, <= 256 VGPRs
 constexpr int kResidentLdsSlots = 18;   // double2 slots per lane of CPT kept in LDS (36 of the 64 entries of a k = 4, two-parent table)
@@ -189,11 +217,17 @@ struct ResidentArgs {
     unsigned* host_abort;             // pinned: set by whoever gives up a bounded wait
     int32_t direct;                   // grid-barrier form, one evidence set: every tile block reads all blocks' granules itself (no service block)
     int32_t first_poll_delay;         // direct form: margin, in 10 ns ticks, between the predicted arrival of the last block and a block's first poll
+    // grid-barrier form, one evidence set: the launch begins at sweep 1, and that sweep reads the first-sweep image instead of rec1 /
+    // node1; nullptr: no image in use.  ONE pointer to a record in device memory: the tile code is inlined once per tile shape, and
+    // every use of a kernel argument there counts (the compiler gives up splitting the argument block beyond a number of uses).
+    const Memo0Image* memo;
 };
 int launch_bp_resident(const ResidentArgs& a, int grid_blocks, int lean_k, void* stream);  // a.flow != nullptr: the dataflow form  // lean_k: uniform arity with <= 2 children per node, else 0
 
 // launchers (bn_kernels.hip)
 int launch_bp_evidence(const EvidenceArgs& a, void* stream);  // bn_bp_set_evidence: marks + vectors
+int launch_bp_memo0_build(const Memo0Args& a, void* stream);   // the first-sweep image of the network without evidence + cv
+int launch_bp_memo0_patch(const Memo0Args& a, void* stream);   // marks + vectors + the image's slots of the new set and of the nodes it drops
 int launch_bp_reset(const BpBuffers& b, void* stream);         // residual slots; after an abnormal end only
 // n_sets > 1: the batched instantiation, one evidence set per blockIdx.y (a.sets valid)
 int launch_bp_sweep(const SweepArgs& a, int grid_blocks, int n_sets, bool nontemporal, bool light, int variants, void* stream);

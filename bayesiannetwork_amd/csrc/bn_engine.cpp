@@ -105,6 +105,7 @@ int bn_eng::ensure_events(bn_engine* e, size_t count) {
 int bn_eng::flush_evidence(bn_engine* e) {
     if (!e->ev_deferred) return BN_OK;
     const Plan& p = e->plan;
+    if (e->ev_applied_dirty) memo0_invalidate(e);  // (what the failed launch left of the first-sweep image is unknown too)
     if (e->frozen_mark == 255 || e->ev_applied_dirty) {  // the mark values are used up (or a launch failed half-way): start over
         HIPCHK(hipMemsetAsync(e->d_frozen, 0, std::max<size_t>(p.n_slots, 1), e->stream));
         e->frozen_mark = 0;
@@ -112,6 +113,13 @@ int bn_eng::flush_evidence(bn_engine* e) {
     ++e->frozen_mark;
     e->ev_applied_dirty = false;
     e->ev_deferred = false;
+    if (e->memo.valid) {  // the same ONE launch also keeps the first-sweep image right for this set (bn_engine_memo.cpp)
+        if (int rc = memo0_patch(e)) {
+            e->ev_applied_dirty = true;
+            return rc;
+        }
+        return BN_OK;
+    }
     EvidenceArgs ea{buffers_of(e), e->ev_ne, e->d_ev_node, e->d_ev_off, e->d_ev_val};
     if (int code = launch_bp_evidence(ea, e->stream)) {
         e->ev_applied_dirty = true;
@@ -260,6 +268,7 @@ void bn_eng::note_run_result(bn_engine* e) {
     e->have_run = true;
     e->predicted_sweeps = e->last_ctl.n_sweeps;
     e->stats.sweeps = e->last_ctl.n_sweeps;
+    e->stats.memo_sweeps = 0;   // (run_resident says otherwise behind this)
     // device clock (100 MHz): start of sweep 0 -> start of the launch after the last executed sweep
     const unsigned long long t0 = e->last_ctl.t_first, t1 = e->last_ctl.t_last;
     e->stats.sweep_devclock_ms = t1 > t0 ? float(double(t1 - t0) * 1e-5) : 0.f;
@@ -328,6 +337,7 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
     if (std::strcmp(name, "beliefs_direct") == 0) { e->beliefs_direct = value != 0; return BN_OK; }
     if (std::strcmp(name, "flow") == 0) { e->flow = value != 0; return BN_OK; }
     if (std::strcmp(name, "direct") == 0) { e->resident_direct = value != 0; return BN_OK; }
+    if (std::strcmp(name, "memo0") == 0) { e->memo.enabled = value != 0; return BN_OK; }   // (the image, once built, is kept right either way)
     if (std::strcmp(name, "mid") == 0) { e->mid_mode = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
     if (std::strcmp(name, "dagflow") == 0) { e->dag_flow = value != 0; return BN_OK; }
     if (std::strcmp(name, "dag") == 0) { e->dag_mode = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
@@ -384,6 +394,9 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strcmp(name, "resident_blocks") == 0) return e->shape.blocks;
     if (std::strcmp(name, "resident_waves") == 0) return e->shape.waves;
     if (std::strcmp(name, "resident_aborts") == 0) return e->resident_aborts;
+    if (std::strcmp(name, "memo0_active") == 0) return e->memo.enabled != 0 && e->memo.valid ? 1 : 0;   // the first-sweep image exists and runs may start from it
+    if (std::strcmp(name, "memo0_bytes") == 0)   // device memory the image takes (0: not built)
+        return e->memo.d_rec ? int64_t(8) * (e->plan.rec_total_doubles + e->plan.node_doubles + e->plan.n + 4) : 0;
     if (std::strcmp(name, "mid_eligible") == 0) return e->mid.ok ? 1 : 0;
     if (std::strcmp(name, "mid_parts") == 0) return e->mid.ok ? int64_t(e->mid.parts.size()) : 0;
     if (std::strcmp(name, "mid_aborts") == 0) return e->mid_aborts;

@@ -364,6 +364,7 @@ static int setup_resident(bn_engine* e, DevLap& dev_lap) {
     }
     if (const char* f = std::getenv("BN_RESIDENT_FLOW")) e->flow = std::atoi(f) != 0;
     if (const char* f = std::getenv("BN_RESIDENT_DIRECT")) e->resident_direct = std::atoi(f) != 0;
+    if (const char* f = std::getenv("BN_MEMO0")) e->memo.enabled = std::atoi(f) != 0;
     if (const char* f = std::getenv("BN_RESIDENT_DELAY")) e->resident_poll_margin = std::max(-1, std::min(std::atoi(f), 1000));
     if (const char* z = std::getenv("BN_POLL_SLEEP")) e->poll_sleep = std::max(0, std::min(std::atoi(z), 64));
     dev_lap("resident setup");

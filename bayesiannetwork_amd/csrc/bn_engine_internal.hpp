@@ -266,6 +266,27 @@ struct bn_engine {
                                     // measured against the service block, us per sweep: 32 x 32 grid 6.98 -> 6.46, 128 x 128 7.25 -> 6.80, 316 x 316 11.46 -> 11.04
     DeviceBuf<ResidentSync> d_rsync;
     bool rsync_dirty = true;        // the sync block must be zeroed before the next launch
+    // First-sweep image of the resident path (option "memo0" / BN_MEMO0; bn_device.hpp Memo0Args, bn_engine_memo.cpp): what sweep 0
+    // leaves behind, built at the first run that can use it, kept right per evidence set by the evidence launch (flush_evidence)
+    struct Memo0 {
+        int enabled = 1;
+        bool valid = false;             // built from the CPT image in force; the slots of `applied` hold those nodes as evidence nodes
+        DeviceBuf<double> d_rec, d_node, d_cv;   // records and node vectors in the layout of rec1 / node1; [n] contributions
+        DeviceBuf<unsigned long long> d_words;   // [0], [1]: sweep 0's residual, written by the patch launches in turn (each leaves the
+                                                 // other zero); [2]: the largest contribution of all (no evidence, nothing to restore)
+        DeviceBuf<Memo0Image> d_img;    // [3] what the resident kernel reads: the two buffers and word q
+        int word = 2;                   // the word that holds sweep 0's residual for the evidence the image holds
+        int next_word = 0;              // the (zero) word of the next patch launch
+        PinnedBuf<int32_t> h_restore;   // [n] mapped: the nodes that lose their evidence, read in place by the patch launch
+        int32_t* h_restore_dev = nullptr;
+        std::vector<double> cv;         // [n] host copy of the contributions
+        std::vector<int32_t> order;     // nodes by descending contribution
+        std::vector<int32_t> applied;   // the evidence set the image holds
+        std::vector<int32_t> restore;
+        std::vector<uint32_t> stamp;    // membership of the set in hand (bn_policy::memo0_stamp)
+        uint32_t epoch = 0;
+        double const_residual = 0.0;    // largest contribution among the nodes outside `applied`
+    } memo;
     // dataflow form of the resident kernel (no grid barrier; single evidence set, more than one tile block)
     int poll_sleep = 2;             // option "poll_sleep" / BN_POLL_SLEEP: pause between two polls of a waiting tile (x 512 cycles)
     int flow = 0;                   // option "flow" / BN_RESIDENT_FLOW: 1 = dataflow form where eligible, 0 = grid barrier per sweep
@@ -504,6 +525,11 @@ int run_batch_mid(bn_engine* e, double eps, int32_t max_sweeps, double*);
 int run_batch_resident(bn_engine* e, double eps, int32_t max_sweeps, double*);
 // the run of a single query: bn_engine_paths.cpp dispatches, bn_engine.cpp has the evidence and the per-sweep launches
 int flush_evidence(bn_engine* e);
+// the first-sweep image (bn_engine_memo.cpp)
+bool memo0_possible(const bn_engine* e);          // the option is on and the network runs the grid-barrier form of the resident kernel
+int memo0_ensure(bn_engine* e);                   // builds the image if there is none: one launch over all nodes, then the set in force
+int memo0_patch(bn_engine* e);                    // ONE launch: marks + vectors of the set in force, its slots of the image, the dropped nodes' slots
+void memo0_invalidate(bn_engine* e);              // the CPTs changed, or a launch failed: rebuilt at the next run that can use it
 void note_run_result(bn_engine* e);
 int run_per_sweep(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to);
 int run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_t* sweeps_out, double* residual_out, double* copy_to);

@@ -75,6 +75,15 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
     OneLaunchRun run(e);
     const bool shard = e->plan.nranks > 1;  // (only called with shard_flow_ok then)
     const bool flow = shard || (rs.flow_ok && e->flow != 0);
+    // The grid-barrier form starts from the stored first sweep where that is known to be safe (bn_engine_memo.cpp; the choice:
+    // bn_policy::memo0_applies): the first launch begins at sweep 1 and reads the image instead of rec1 / node1.  The image is built
+    // by the first run that could use it.
+    bool memo = false;
+    if (!flow && max_sweeps != 1 && memo0_possible(e)) {
+        if (int rc = memo0_ensure(e)) return rc;
+        memo = bn_policy::memo0_applies({true, e->memo.valid, flow, max_sweeps, eps, e->memo.const_residual});
+    }
+    if (memo) run.sweep_begin = 1;
     while (!run.done) {
         // polled words: generations count on from launch to launch, so they are zeroed only at creation, after an
         // aborted launch and before the 30-bit generation would wrap
@@ -96,12 +105,14 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
             e->gen_base = 0;
         }
         *e->h_abort = 0;
-        ResidentArgs a{buffers_of(e), eps, max_sweeps, run.sweep_begin, kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
+        const bool from_image = memo && run.launches == 0;   // (one iteration less: the launches of a long run end where they always did)
+        ResidentArgs a{buffers_of(e), eps, max_sweeps, run.sweep_begin, from_image ? kResidentBudget - 1 : kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
                        // one wait: 50 ms of the 100 MHz clock; shards: 2 s (the ranks' launches start up to a host hiccup apart)
                        shard ? 200000000ull : 5000000ull, e->d_rsync, e->h_ctl_dev,
                        rs.blocks, rs.waves, 1, 1u, 0, 0, 0, 0, 0, flow ? e->d_flow.get() : nullptr,
                        shard ? e->d_peers.get() : nullptr, shard ? e->d_pub_mask.get() : nullptr, shard ? e->plan.n_interior_tiles : 0,
-                       e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort_dev, (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin};
+                       e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort_dev, (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin,
+                       from_image ? e->memo.d_img + e->memo.word : nullptr};
         if (int rc = run.begin()) return rc;
         if (int code = launch_bp_resident(a, rs.blocks + (shard ? 1 : resident_service_blocks(rs.blocks)), rs.lean, s))
             return fail(BN_ERR_HIP, std::string("bp_resident launch failed: ") + hipGetErrorString(hipError_t(code)));
@@ -134,6 +145,7 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         if (int rc = run.after_sync(BN_ERR_STATE, "resident kernel did not report (stale control block)")) return rc;
     }
     run.finish(2);
+    e->stats.memo_sweeps = memo ? 1 : 0;
     e->last_flow = flow ? 1 : 0;
     return BN_OK;
 }

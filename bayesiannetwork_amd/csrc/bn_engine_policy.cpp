@@ -44,6 +44,32 @@ ResidentShape plan_resident(const PathFacts& f, int n_cus, int forced_waves) {
     return r;
 }
 
+bool memo0_applies(const Memo0Run& r) {
+    if (!r.enabled || !r.image_valid || r.flow) return false;
+    if (r.max_sweeps == 1) return false;   // the run ends behind sweep 0: it has to be executed
+    // (written so that a NaN on either side says no)
+    return r.const_residual > 0.0 && r.const_residual <= 1.7976931348623157e308 && r.eps <= r.const_residual;
+}
+
+void memo0_stamp(const int32_t* ev_node, int32_t ne, int32_t n, std::vector<uint32_t>& stamp, uint32_t& epoch) {
+    if (stamp.size() != size_t(n > 0 ? n : 0) || epoch == 0xffffffffu) { stamp.assign(size_t(n > 0 ? n : 0), 0u); epoch = 0; }
+    ++epoch;
+    for (int32_t j = 0; j < ne; ++j)
+        if (ev_node[j] >= 0 && ev_node[j] < n) stamp[size_t(ev_node[j])] = epoch;
+}
+
+void memo0_restore_list(const std::vector<int32_t>& applied, const std::vector<uint32_t>& stamp, uint32_t epoch, std::vector<int32_t>& out) {
+    out.clear();
+    for (int32_t v : applied)
+        if (v >= 0 && size_t(v) < stamp.size() && stamp[size_t(v)] != epoch) out.push_back(v);
+}
+
+double memo0_const_residual(const std::vector<int32_t>& order, const std::vector<double>& cv, const std::vector<uint32_t>& stamp, uint32_t epoch) {
+    for (int32_t v : order)
+        if (size_t(v) >= stamp.size() || stamp[size_t(v)] != epoch) return cv[size_t(v)];
+    return 0.0;
+}
+
 bool mid_fits(const PathFacts& f, int n_cus) {
     // the workgroups of a run wait for each other: one per CU, with room to spare
     return !(n_cus > 0 && int64_t(f.mid.parts) > int64_t(n_cus) * 9 / 10);

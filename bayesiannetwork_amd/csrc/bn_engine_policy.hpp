@@ -64,6 +64,29 @@ bool dag_applies(const PathFacts& f, const ResidentShape& r, const PathOks& ok, 
 bool dag_first_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
 bool dag_later_wanted(const PathFacts& f, const ResidentShape& r, const PathOks& ok, const PathModes& m);
 
+// ---- the first-sweep image of the resident path (option "memo0"; bn_device.hpp Memo0Args): sweep 0 of a run reads no message, so
+// what it leaves is stored once per CPT image, patched per evidence set, and a run starts at sweep 1 ----
+// Whether a run of the resident kernel starts from the image.
+struct Memo0Run {
+    bool enabled = false;       // option "memo0"
+    bool image_valid = false;   // the image exists and holds the evidence in force
+    bool flow = false;          // the launch is the dataflow form (shards included)
+    int32_t max_sweeps = 0;     // 0: unbounded
+    double eps = 0.0;
+    double const_residual = 0.0;   // largest sweep-0 contribution among the nodes without evidence (memo0_const_residual)
+};
+// sweep 0 must be known not to end the run without looking at the evidence nodes: max_sweeps is 0 or >= 2, and eps is at most the
+// constant part of its residual (the stop test is residual < eps), which must be finite and positive
+bool memo0_applies(const Memo0Run& r);
+// Membership of the new evidence set: stamp[v] == epoch.  Stamps the `ne` nodes of the set (a fresh epoch; the array is cleared when
+// it has another size than n or the epoch would wrap).
+void memo0_stamp(const int32_t* ev_node, int32_t ne, int32_t n, std::vector<uint32_t>& stamp, uint32_t& epoch);
+// the nodes whose slots of the image go back to "no evidence": in the set applied before and not in the stamped one; order of `applied`
+void memo0_restore_list(const std::vector<int32_t>& applied, const std::vector<uint32_t>& stamp, uint32_t epoch, std::vector<int32_t>& out);
+// the constant part of sweep 0's residual: `order` lists the nodes by descending contribution cv[]; the first one outside the stamped
+// set decides (usually the very first).  0.0 when every node carries evidence.
+double memo0_const_residual(const std::vector<int32_t>& order, const std::vector<double>& cv, const std::vector<uint32_t>& stamp, uint32_t epoch);
+
 // ---- a batch of evidence sets (bn_bp_run_batch_device): the same questions for the batch forms of the paths ----
 // what only the device side knows of a batch: the per-set state of the one-workgroup path is allocated (Batch::d_s_state), a staging
 // block holds the sets' evidence (Batch::ev_base)

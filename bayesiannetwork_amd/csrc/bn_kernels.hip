@@ -77,6 +77,205 @@ __global__ __launch_bounds__(kBlockThreads) void bp_evidence_kernel(EvidenceArgs
     b.frozen[td.slot_base + nl] = b.frozen_mark;
 }
 
+// ---- the first-sweep image of the resident path (bn_device.hpp Memo0Args) ----------------------------------------------------
+// Sweep 0 of a run reads no message (every message, pi(v) of a node with parents and lambda(v) start at 1.0, a root's pi(v) at its
+// CPT row, an evidence node's two vectors at its evidence), so what a node's lane leaves behind -- its pi-messages to its children,
+// its lambda-messages to its parents, its new pi(v) / lambda(v), its share of the residual -- is a function of its own CPT and its own
+// evidence alone.  memo0_node computes exactly that for ONE node and writes it into the image: the slots this node's lane writes in
+// sweep 0 of bn_resident.hip's resident_tile, nothing else.  `frozen`: the node carries the evidence vector `ev`.  Every sum and
+// product keeps resident_tile's association and order of terms for first == true (multiplications by the synthesised 1.0 are exact
+// and left out; roots keep 0.0 + cpt; normalisation is unguarded), so the image holds the very bits sweep 0 would have written.
+// Covers what the barrier form of the resident kernel admits: one lane per node, uniform arity 2..4, at most two parents, at most 8
+// children.  Returns the node's residual contribution: max |new - 1.0| over its outgoing messages, NaN terms dropped (res_acc).
+// One instantiation per shape (K, M): the patch launch stands in front of every query that changes the evidence, and with run-time
+// loops a lane's 64 table reads followed each other one memory latency apart (~60 us per launch on the 316 x 316 grid); unrolled,
+// the table and the references are requested together and waited for once.
+template <int K, int M>
+__device__ __forceinline__ double memo0_node_t(const BpBuffers& b, const TileDesc& td, int nl, bool frozen, const double (&ev)[4], double* rec,
+                                               double* node) {
+    constexpr int KP = (K + 1) & ~1, H = KP / 2, C = ipow(K, M), S = K * C, SP = (S + 1) & ~1;
+    const double2_t* cp = reinterpret_cast<const double2_t*>(b.cpt + td.cpt_base) + nl;  // entry e of the i-major image: chunk e / 2 (bn_plan.hpp)
+    double cpt[SP];
+#pragma unroll
+    for (int q = 0; q < SP / 2; ++q) {
+        const double2_t x = cp[q * kWave];
+        cpt[2 * q] = x.x;
+        cpt[2 * q + 1] = x.y;
+    }
+    const MsgRef* orf = b.out_refs + td.out_base + nl;
+    MsgRef oref[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        oref[c] = MsgRef{-1, 0};
+        if (c < td.cmax) oref[c] = orf[c * kWave];
+    }
+    auto put = [&](double* base, int64_t at2, const double (&x)[K], int h) {  // chunk h of a vector as one double2, padding zero
+        double2_t y;
+        y.x = x[2 * h];
+        y.y = (2 * h + 1 < K) ? x[(2 * h + 1 < K) ? 2 * h + 1 : 0] : 0.0;
+        reinterpret_cast<double2_t*>(base)[at2] = y;
+    };
+    double piv[K], lav[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        piv[i] = frozen ? ev[i] : (M == 0 ? cpt[i] : 1.0);
+        lav[i] = frozen ? ev[i] : 1.0;
+    }
+    double res = 0.0;
+    // parent role: lambda(v) = the product of the children's lambda-messages (all 1.0), normalised; the pi-message to each child =
+    // pi(v) times the other children's lambda-messages (1.0), normalised: the same vector for every child
+    double lan[K], u[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) { lan[i] = 1.0; u[i] = piv[i]; }
+    normalize_k<K>(lan);
+    normalize_k<K>(u);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const Loc l = decode_ref(oref[c], H);
+        if (l.has) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) res = res_acc(res, fabs(u[i] - 1.0));
+#pragma unroll
+            for (int h = 0; h < H; ++h) put(rec, l.pi + int64_t(h) * l.stride, u, h);
+        }
+    }
+    // child role: pi(v)[ib] = the sum of the own state's CPT entries in assignment order (the parents' pi-messages are 1.0);
+    // lambda-message to parent j, entry u = sum over own states (outer) and the other parent's states (inner) of lambda(v)[ib] * cpt
+    double pin[K], out[M > 0 ? M : 1][K];
+#pragma unroll
+    for (int j = 0; j < (M > 0 ? M : 1); ++j)
+#pragma unroll
+        for (int i = 0; i < K; ++i) out[j][i] = 0.0;
+#pragma unroll
+    for (int ib = 0; ib < K; ++ib) {
+        if constexpr (M == 0) {
+            pin[ib] = 0.0 + cpt[ib];
+        } else {
+            double acc = 0.0;
+            if constexpr (M == 2) {
+#pragma unroll
+                for (int u0 = 0; u0 < K; ++u0)
+#pragma unroll
+                    for (int u1 = 0; u1 < K; ++u1) {
+                        const double r = cpt[ib * C + u0 * K + u1];
+                        acc += r;
+                        const double tt = lav[ib] * r;
+                        out[0][u0] += tt;
+                        out[1][u1] += tt;
+                    }
+            } else {
+#pragma unroll
+                for (int x = 0; x < K; ++x) acc += cpt[ib * C + x];
+#pragma unroll
+                for (int x = 0; x < K; ++x) out[0][x] += lav[ib] * cpt[ib * C + x];
+            }
+            pin[ib] = acc;
+        }
+    }
+    normalize_k<K>(pin);
+    const int64_t rbase = td.rec_base / 2 + nl;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        normalize_k<K>(out[j]);
+#pragma unroll
+        for (int i = 0; i < K; ++i) res = res_acc(res, fabs(out[j][i] - 1.0));
+#pragma unroll
+        for (int h = 0; h < H; ++h) put(rec, rbase + int64_t((j * 2 + 1) * H + h) * kWave, out[j], h);
+    }
+    // the node's new vectors; an evidence node keeps its evidence
+    if (!frozen) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) { piv[i] = pin[i]; lav[i] = lan[i]; }
+    }
+    const int64_t nbase = td.node_base / 2 + nl;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        put(node, nbase + int64_t(h) * kWave, piv, h);
+        put(node, nbase + int64_t(H + h) * kWave, lav, h);
+    }
+    return res;
+}
+
+__device__ __forceinline__ double memo0_node(const BpBuffers& b, int v, bool frozen, const double (&ev)[4], double* rec, double* node) {
+    const int t = b.node_tile[v];
+    if (t < 0) return 0.0;
+    const TileDesc td = b.tiles[t];
+    if (td.variant != kVariantUniform || td.npt != kWave || td.cmax > 8) return 0.0;  // (the host builds no image for such a plan)
+    const int nl = b.node_nl[v];
+    switch (td.kv * 4 + td.m) {
+        case 2 * 4 + 0: return memo0_node_t<2, 0>(b, td, nl, frozen, ev, rec, node);
+        case 2 * 4 + 1: return memo0_node_t<2, 1>(b, td, nl, frozen, ev, rec, node);
+        case 2 * 4 + 2: return memo0_node_t<2, 2>(b, td, nl, frozen, ev, rec, node);
+        case 3 * 4 + 0: return memo0_node_t<3, 0>(b, td, nl, frozen, ev, rec, node);
+        case 3 * 4 + 1: return memo0_node_t<3, 1>(b, td, nl, frozen, ev, rec, node);
+        case 3 * 4 + 2: return memo0_node_t<3, 2>(b, td, nl, frozen, ev, rec, node);
+        case 4 * 4 + 0: return memo0_node_t<4, 0>(b, td, nl, frozen, ev, rec, node);
+        case 4 * 4 + 1: return memo0_node_t<4, 1>(b, td, nl, frozen, ev, rec, node);
+        case 4 * 4 + 2: return memo0_node_t<4, 2>(b, td, nl, frozen, ev, rec, node);
+        default: return 0.0;
+    }
+}
+
+// the image of the network without evidence, and every node's own residual contribution
+__global__ __launch_bounds__(kBlockThreads) void bp_memo0_build_kernel(Memo0Args a) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= a.n) return;
+    const double none[4] = {0.0, 0.0, 0.0, 0.0};
+    a.cv[v] = memo0_node(a.b, v, false, none, a.rec, a.node);
+}
+
+// One launch per evidence set: what bp_evidence_kernel does (marks, vectors in both node buffers) for the nodes of the new set, their
+// slots of the image recomputed as evidence nodes, and the slots of the nodes that lose their evidence recomputed as ordinary nodes.
+// The evidence nodes' residual contributions and the seed go into *word (bit patterns of non-negative doubles order like unsigned
+// integers), which the previous patch launch left zero; this one leaves the next launch's word zero.
+__global__ __launch_bounds__(kWave) void bp_memo0_patch_kernel(Memo0Args a) {
+    const BpBuffers& b = a.b;
+    // one node per 2^spread lanes: a node's table is 32 scattered lines, and a wave of 64 such nodes keeps one CU's address path busy
+    // for microseconds -- spread out, the launch's few thousand nodes use the whole chip
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = (g & ((1 << a.spread) - 1)) == 0 ? (g >> a.spread) : 0x7fffffff;
+    // The lists are read in place from page-locked host memory: a read is a trip over the bus.  Everything that depends on j alone is
+    // requested at once (node, offset, length), then the values and -- beside them, in device memory -- the node's tile, its CPT and
+    // its references: two trips over the bus on the lane's critical path, as in bp_evidence_kernel, with the device reads under the second.
+    const bool frozen = j < a.ne, restore = !frozen && j < a.ne + a.n_restore;
+    int v = -1, off = 0, len = 0;
+    if (frozen) {
+        v = a.ev_node[j];
+        off = a.ev_off[j];
+        len = a.ev_off[j + 1] - off;
+    } else if (restore) {
+        v = a.restore[j - a.ne];
+    }
+    double x[4] = {0.0, 0.0, 0.0, 0.0};
+    if (frozen) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < len) x[i] = a.ev_val[off + i];
+    }
+    unsigned long long bits = a.seed;
+    const int t = v >= 0 ? b.node_tile[v] : -1;
+    if (t >= 0) {  // (else: no node for this lane, or one owned by another rank)
+        if (frozen) {
+            const TileDesc td = b.tiles[t];
+            const int nl = b.node_nl[v];
+            const int half = ((td.kv + 1) & ~1) >> 1;
+            for (int i = 0; i < td.kv; ++i) {
+                const double y = i < 4 ? x[i & 3] : a.ev_val[off + i];
+                b.node0[td.node_base + vidx(0, i, td.npt, nl)] = y;
+                b.node0[td.node_base + vidx(half, i, td.npt, nl)] = y;
+                b.node1[td.node_base + vidx(0, i, td.npt, nl)] = y;
+                b.node1[td.node_base + vidx(half, i, td.npt, nl)] = y;
+            }
+            b.frozen[td.slot_base + nl] = b.frozen_mark;
+        }
+        const unsigned long long p = (unsigned long long)__double_as_longlong(memo0_node(b, v, frozen, x, a.rec, a.node));
+        if (frozen) bits = p > bits ? p : bits;
+    }
+    bits = wave_umax(bits);
+    if ((threadIdx.x & (kWave - 1)) == 0) __hip_atomic_fetch_max(a.word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (j == 0) *a.word_next = 0ull;
+}
+
 // This rank's residual slots in both buffers.  A finished run leaves them zero itself
 // (bp_finish_kernel); this kernel runs only after a run that did not end normally.
 __global__ __launch_bounds__(kBlockThreads) void bp_reset_kernel(BpBuffers b) {
@@ -150,6 +349,20 @@ int launch_bp_evidence(const EvidenceArgs& a, void* stream) {
     const int blocks = (a.ne + kBlockThreads - 1) / kBlockThreads;
     (void)hipGetLastError();  // drop any stale error of this thread
     hipLaunchKernelGGL(bp_evidence_kernel, dim3(blocks), dim3(kBlockThreads), 0, (hipStream_t)stream, a);
+    return hip_rc(hipGetLastError());
+}
+int launch_bp_memo0_build(const Memo0Args& a, void* stream) {
+    if (a.n <= 0) return 0;
+    const int blocks = (a.n + kBlockThreads - 1) / kBlockThreads;
+    (void)hipGetLastError();  // drop any stale error of this thread
+    hipLaunchKernelGGL(bp_memo0_build_kernel, dim3(blocks), dim3(kBlockThreads), 0, (hipStream_t)stream, a);
+    return hip_rc(hipGetLastError());
+}
+int launch_bp_memo0_patch(const Memo0Args& a, void* stream) {
+    const int64_t work = int64_t(a.ne + a.n_restore) << a.spread;   // (0: one block still seeds the word)
+    const int blocks = work > 0 ? int((work + kWave - 1) / kWave) : 1;
+    (void)hipGetLastError();  // drop any stale error of this thread
+    hipLaunchKernelGGL(bp_memo0_patch_kernel, dim3(blocks), dim3(kWave), 0, (hipStream_t)stream, a);
     return hip_rc(hipGetLastError());
 }
 int launch_bp_reset(const BpBuffers& b, void* stream) {

@@ -835,7 +835,13 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
         // evidence nodes hold their vector as pi and lambda (:68-73); from the second sweep on (and in a
         // continued run) the vectors are what the previous sweep left
         if (frozen || s > 0) {
-            const double2_t* nin = reinterpret_cast<const double2_t*>(((s & 1) ? b.node1 : b.node0) + (BATCH ? int64_t(set) * a.node_stride : 0) +
+            const double* nodd = b.node1;
+            if constexpr (!BATCH && !FLOW) {  // the launch begins behind the memoised first sweep: its vectors are in the image (Memo0Image)
+                if (s == 1) {
+                    if (const Memo0Image* mi = a.memo) nodd = mi->node;
+                }
+            }
+            const double2_t* nin = reinterpret_cast<const double2_t*>(((s & 1) ? nodd : b.node0) + (BATCH ? int64_t(set) * a.node_stride : 0) +
                                                                       td.node_base) + lc;
 #pragma unroll
             for (int h = 0; h < H; ++h) {
@@ -864,7 +870,13 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
         if constexpr (BATCH) load_nodes(set, s);
         const bool first = s == 0;
         const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(b.rec0 + (BATCH ? int64_t(set) * a.rec_stride : 0), 0, int(rec_bytes), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc(b.rec1 + (BATCH ? int64_t(set) * a.rec_stride : 0), 0, int(rec_bytes), 0x00020000);
+        double* rodd = b.rec1 + (BATCH ? int64_t(set) * a.rec_stride : 0);
+        if constexpr (!BATCH && !FLOW) {  // the sweep behind the memoised first one reads the image's records (an odd sweep only reads this buffer)
+            if (s == 1) {
+                if (const Memo0Image* mi = a.memo) rodd = mi->rec;
+            }
+        }
+        const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc(rodd, 0, int(rec_bytes), 0x00020000);
         const __amdgpu_buffer_rsrc_t rin = (s & 1) ? rsrc1 : rsrc0;
         const __amdgpu_buffer_rsrc_t rout = (s & 1) ? rsrc0 : rsrc1;
 
@@ -1235,6 +1247,15 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
                 }
             }
 #endif
+        }
+    }
+    if constexpr (MODE == kModeBarrier) {
+        // the launch began behind the memoised first sweep: that sweep's residual is the word the evidence launch left (Memo0Args).
+        // Once per launch, here rather than in the tile code's report: every use of the arguments there is inlined once per tile shape
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (const Memo0Image* mi = a.memo) {
+                if (b.res_cap > 0) b.res_hist[0] = residual_of(*mi->word);
+            }
         }
     }
     if constexpr (!FLOW) {

@@ -304,6 +304,13 @@ int bn_em_fit(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const
  * "direct" 1/0 -- resident path, grid-barrier form, one evidence set (BN_RESIDENT_DIRECT sets the default, 1): 1 = every tile block
  *   reads all blocks' arrival words itself and takes the stop decision (one hand-off per barrier); 0 = a service block collects
  *   them and publishes the decision (two).  Same bits.
+ * "memo0" 1/0 -- resident path, grid-barrier form, one evidence set (BN_MEMO0 sets the default, 1): sweep 0 of a run reads no message,
+ *   so what it leaves behind -- every node's first messages and vectors -- depends on the CPTs and, node by node, on the node's own
+ *   evidence alone.  1 = the engine keeps that state in device memory (one more record and node buffer; built by the first run that
+ *   can use it, rebuilt after bn_reload_cpt), the launch that applies an evidence set recomputes the slots of the set's nodes and of the
+ *   nodes it drops, and a run starts at sweep 1; 0 = every run executes sweep 0.  Same sweep counts, residual histories and bits either
+ *   way; runs with max_sweeps 1 or eps above sweep 0's residual execute sweep 0 regardless.  bn_get_info "memo0_active" (the image
+ *   exists and is in use), "memo0_bytes"; bn_bp_stats.memo_sweeps tells what the last run did.
  * "poll_sleep" n -- dataflow form: pause between two polls of a waiting tile, n x 512 cycles (default 2).
  * "beliefs_direct" 1/0 -- bn_bp_run_view: the kernels write the marginals straight into the engine's mapped host
  *   buffer (default 1, outputs up to 16 MB) instead of a copy command queued behind the run.
@@ -374,6 +381,8 @@ typedef struct bn_bp_stats {
     float sweep_devclock_ms;   /* device clock: first sweep's start -> last executed sweep's end */
     int32_t resident_aborts;   /* resident launches that gave up a bounded wait, over the engine's life: each sends
                                   the following runs down the per-sweep launches for a while (8, 16, ... runs) */
+    int32_t memo_sweeps;       /* sweeps of the last run that were taken from the first-sweep image instead of being executed
+                                  (option "memo0"): 0 or 1.  `sweeps` counts them all the same */
 } bn_bp_stats;
 int bn_bp_last_stats(bn_engine *eng, bn_bp_stats *out);
 
