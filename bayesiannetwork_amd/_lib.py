@@ -34,7 +34,7 @@ class BpStats(ctypes.Structure):
                 ("total_ms", ctypes.c_float), ("algorithmic_bytes_per_sweep", ctypes.c_int64),
                 ("layout_bytes_per_sweep", ctypes.c_int64), ("messages_per_sweep", ctypes.c_int64),
                 ("sweep_devclock_ms", ctypes.c_float), ("resident_aborts", ctypes.c_int32),
-                ("memo_sweeps", ctypes.c_int32)]
+                ("memo_sweeps", ctypes.c_int32), ("memo_depth", ctypes.c_int32)]
 
 
 class AnnealParams(ctypes.Structure):

@@ -112,6 +112,10 @@ struct Memo0Image {
     double* rec;
     const double* node;
     const unsigned long long* word;   // bit pattern of sweep 0's residual for the evidence the image holds (res_hist[0])
+    // A record of the second-sweep image (Memo1Args) is read by a launch whose sweeps are numbered one later than the run's (see
+    // ResidentArgs::memo): `word` is then sweep 1's residual, and word_before -- nullptr in a first-sweep record -- sweep 0's, which
+    // goes into the history entry in front of the launch's first
+    const unsigned long long* word_before;
 };
 struct Memo0Args {
     BpBuffers b;
@@ -128,6 +132,31 @@ struct Memo0Args {
     unsigned long long* word;     // the sweep-0 residual's bit pattern: max(seed, the evidence nodes' contributions); zero before the launch
     unsigned long long* word_next;  // ... the word of the NEXT patch launch, left zero by this one
     unsigned long long seed;      // largest contribution among the nodes WITHOUT evidence (bit pattern; the host knows it)
+    int32_t spread;               // patch: one node per 2^spread lanes (0..6)
+};
+
+// The second-sweep image (bn_kernels.hip memo_step_node): what sweep 1 leaves behind, in the layout of rec0 / node0, the buffers
+// sweep 2 reads.  One Jacobi sweep (first == false) per node from the first-sweep image into this one: what it leaves at node v
+// depends on the CPTs and on the evidence of v's closed neighbourhood N[v] alone.  Built once per CPT image from the first-sweep image
+// of the network WITHOUT evidence (the marks are ignored by the build); per evidence set E the launch behind the first-sweep patch
+// recomputes N[E + R], R = the nodes this image held as evidence nodes and the set drops: one thread per (listed node, slot of its
+// closed neighbourhood).  A node reached from two listed nodes is computed twice and written twice with the same bits.
+struct Memo1Args {
+    BpBuffers b;
+    const double* src_rec;        // the first-sweep image (of the set in force; build: of the network without evidence)
+    const double* src_node;
+    double* rec;                  // this image
+    double* node;
+    double* cv;                   // build only: [n] the node's own residual contribution in sweep 1
+    int32_t n;                    // build only: nodes
+    int32_t n_list;               // patch: listed nodes (E, then R)
+    const int32_t* list;          // ... read in place from page-locked host memory
+    const int32_t* adj_off;       // [n + 1] node-level CSR: parents, then children
+    const int32_t* adj;
+    int32_t width;                // patch: threads per listed node = 1 + the largest degree
+    unsigned long long* word;     // sweep 1's residual (bit pattern): max(seed, what the launch computed); zero before the launch
+    unsigned long long* word_next;  // the word of the NEXT patch launch, left zero by this one
+    unsigned long long seed;      // largest pristine contribution among the nodes outside N[E] (bit pattern)
     int32_t spread;               // patch: one node per 2^spread lanes (0..6)
 };
 
@@ -218,7 +247,10 @@ struct ResidentArgs {
     int32_t direct;                   // grid-barrier form, one evidence set: every tile block reads all blocks' granules itself (no service block)
     int32_t first_poll_delay;         // direct form: margin, in 10 ns ticks, between the predicted arrival of the last block and a block's first poll
     // grid-barrier form, one evidence set: the launch begins at sweep 1, and that sweep reads the first-sweep image instead of rec1 /
-    // node1; nullptr: no image in use.  ONE pointer to a record in device memory: the tile code is inlined once per tile shape, and
+    // node1; nullptr: no image in use.  A run that starts from the SECOND-sweep image is launched in the same form: the host numbers
+    // the launch's sweeps one later than the run's -- sweep_begin 1 for the run's sweep 2, max_sweeps one less, rec0 / rec1 and node0 /
+    // node1 exchanged, res_hist one entry further -- so the tile code is the same code with the same registers, and adds the one back
+    // to the sweep count the launch reports (bn_engine_paths.cpp run_resident).  ONE pointer to a record in device memory: the tile code is inlined once per tile shape, and
     // every use of a kernel argument there counts (the compiler gives up splitting the argument block beyond a number of uses).
     const Memo0Image* memo;
 };
@@ -228,6 +260,8 @@ int launch_bp_resident(const ResidentArgs& a, int grid_blocks, int lean_k, void*
 int launch_bp_evidence(const EvidenceArgs& a, void* stream);  // bn_bp_set_evidence: marks + vectors
 int launch_bp_memo0_build(const Memo0Args& a, void* stream);   // the first-sweep image of the network without evidence + cv
 int launch_bp_memo0_patch(const Memo0Args& a, void* stream);   // marks + vectors + the image's slots of the new set and of the nodes it drops
+int launch_bp_memo1_build(const Memo1Args& a, void* stream);   // the second-sweep image of the network without evidence + cv
+int launch_bp_memo1_patch(const Memo1Args& a, void* stream);   // the second-sweep image's slots of the listed nodes' closed neighbourhoods
 int launch_bp_reset(const BpBuffers& b, void* stream);         // residual slots; after an abnormal end only
 // n_sets > 1: the batched instantiation, one evidence set per blockIdx.y (a.sets valid)
 int launch_bp_sweep(const SweepArgs& a, int grid_blocks, int n_sets, bool nontemporal, bool light, int variants, void* stream);

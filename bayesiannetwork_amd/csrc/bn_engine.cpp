@@ -174,6 +174,7 @@ static int set_evidence_impl(bn_engine* e, int32_t ne, const int32_t* ev_node, c
         return BN_OK;
     }
     e->ev_deferred = true;
+    e->ev_one_shot = !wait;   // (bn_bp_run / bn_bp_run_view pass wait == false: the set is run once, in this call)
     if ((rc = flush_evidence(e))) return rc;
     if (wait) {
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -269,6 +270,7 @@ void bn_eng::note_run_result(bn_engine* e) {
     e->predicted_sweeps = e->last_ctl.n_sweeps;
     e->stats.sweeps = e->last_ctl.n_sweeps;
     e->stats.memo_sweeps = 0;   // (run_resident says otherwise behind this)
+    e->stats.memo_depth = 0;
     // device clock (100 MHz): start of sweep 0 -> start of the launch after the last executed sweep
     const unsigned long long t0 = e->last_ctl.t_first, t1 = e->last_ctl.t_last;
     e->stats.sweep_devclock_ms = t1 > t0 ? float(double(t1 - t0) * 1e-5) : 0.f;
@@ -338,6 +340,12 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
     if (std::strcmp(name, "flow") == 0) { e->flow = value != 0; return BN_OK; }
     if (std::strcmp(name, "direct") == 0) { e->resident_direct = value != 0; return BN_OK; }
     if (std::strcmp(name, "memo0") == 0) { e->memo.enabled = value != 0; return BN_OK; }   // (the image, once built, is kept right either way)
+    if (std::strcmp(name, "memo1") == 0) {
+        // (built together with the first-sweep image: where that one exists without it, both are built again by the next run)
+        if (value != 0 && e->memo.valid && !e->memo1.built) memo0_invalidate(e);
+        e->memo1.enabled = value != 0;
+        return BN_OK;
+    }
     if (std::strcmp(name, "mid") == 0) { e->mid_mode = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
     if (std::strcmp(name, "dagflow") == 0) { e->dag_flow = value != 0; return BN_OK; }
     if (std::strcmp(name, "dag") == 0) { e->dag_mode = value < 0 ? 0 : (value > 2 ? 2 : value); return BN_OK; }
@@ -396,7 +404,11 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strcmp(name, "resident_aborts") == 0) return e->resident_aborts;
     if (std::strcmp(name, "memo0_active") == 0) return e->memo.enabled != 0 && e->memo.valid ? 1 : 0;   // the first-sweep image exists and runs may start from it
     if (std::strcmp(name, "memo0_bytes") == 0)   // device memory the image takes (0: not built)
-        return e->memo.d_rec ? int64_t(8) * (e->plan.rec_total_doubles + e->plan.node_doubles + e->plan.n + 4) : 0;
+        return (e->memo.d_rec ? int64_t(8) * (e->plan.rec_total_doubles + e->plan.node_doubles + e->plan.n + 4) : 0) +
+               (e->memo1.d_rec ? int64_t(8) * (e->plan.rec_total_doubles + e->plan.node_doubles + e->plan.n + 4) +
+                                     int64_t(4) * int64_t(e->memo1.adj_off.size() + e->memo1.adj.size()) : 0);
+    if (std::strcmp(name, "memo1_active") == 0)   // the second-sweep image exists, holds the evidence in force, and runs may start from it
+        return e->memo.enabled != 0 && e->memo.valid && e->memo1.enabled != 0 && e->memo1.built && e->memo1.holds ? 1 : 0;
     if (std::strcmp(name, "mid_eligible") == 0) return e->mid.ok ? 1 : 0;
     if (std::strcmp(name, "mid_parts") == 0) return e->mid.ok ? int64_t(e->mid.parts.size()) : 0;
     if (std::strcmp(name, "mid_aborts") == 0) return e->mid_aborts;

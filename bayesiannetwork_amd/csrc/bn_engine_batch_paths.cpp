@@ -32,6 +32,7 @@ void finish_batch(bn_engine* e, int path, int32_t launches, float kernel_ms, flo
     e->stats.sweep_devclock_ms = devclock_ms;
     e->stats.sweeps = sweeps;
     e->stats.memo_sweeps = 0;   // (batches run every sweep)
+    e->stats.memo_depth = 0;
 }
 
 // The chunks of a batch follow each other on the stream and the host waits ONCE for all of them (a wait per chunk cost a batch of 16

@@ -365,6 +365,9 @@ static int setup_resident(bn_engine* e, DevLap& dev_lap) {
     if (const char* f = std::getenv("BN_RESIDENT_FLOW")) e->flow = std::atoi(f) != 0;
     if (const char* f = std::getenv("BN_RESIDENT_DIRECT")) e->resident_direct = std::atoi(f) != 0;
     if (const char* f = std::getenv("BN_MEMO0")) e->memo.enabled = std::atoi(f) != 0;
+    if (const char* f = std::getenv("BN_MEMO1")) e->memo1.enabled = std::atoi(f) != 0;
+    if (const char* f = std::getenv("BN_MEMO1_ONESHOT")) e->memo1.oneshot = std::atoi(f) != 0;
+    if (const char* f = std::getenv("BN_MEMO1_LIMIT")) e->memo1.limit = std::max<int64_t>(0, std::atoll(f));
     if (const char* f = std::getenv("BN_RESIDENT_DELAY")) e->resident_poll_margin = std::max(-1, std::min(std::atoi(f), 1000));
     if (const char* z = std::getenv("BN_POLL_SLEEP")) e->poll_sleep = std::max(0, std::min(std::atoi(z), 64));
     dev_lap("resident setup");

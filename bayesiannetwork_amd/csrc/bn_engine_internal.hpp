@@ -287,6 +287,31 @@ struct bn_engine {
         uint32_t epoch = 0;
         double const_residual = 0.0;    // largest contribution among the nodes outside `applied`
     } memo;
+    // Second-sweep image (option "memo1" / BN_MEMO1; bn_device.hpp Memo1Args, bn_engine_memo.cpp): what sweep 1 leaves behind, built
+    // together with the first-sweep image, kept right per evidence set by a launch behind the first-sweep patch
+    struct Memo1 {
+        int enabled = 1;
+        bool built = false;             // the buffers hold the image of the CPTs in force, right for the evidence set `applied`
+        bool holds = false;             // ... and `applied` is the set in force: a run may start at sweep 2
+        int oneshot = 0;                // BN_MEMO1_ONESHOT: 1 = a set that arrives with its single run (bn_bp_run, bn_bp_run_view) patches
+                                        // too; measured on the headline, the launch then costs more than the iteration it saves (EXP R20.2)
+        int64_t limit = 1 << 15;        // BN_MEMO1_LIMIT: most (|E| + |R|) x (1 + max degree) a set may cost and still patch (EXP R20.4)
+        DeviceBuf<double> d_rec, d_node, d_cv;   // records and node vectors in the layout of rec0 / node0; [n] contributions
+        DeviceBuf<unsigned long long> d_words;   // as Memo0::d_words, for sweep 1's residual
+        DeviceBuf<Memo0Image> d_img;    // [9] what the resident kernel reads: record 3 * (first-sweep word) + (second-sweep word)
+        DeviceBuf<int32_t> d_adj_off, d_adj;     // node-level CSR: parents, then children
+        int word = 2, next_word = 0;
+        PinnedBuf<int32_t> h_list;      // [n] mapped: E then R, read in place by the patch launch
+        int32_t* h_list_dev = nullptr;
+        std::vector<double> cv;         // [n] host copy of the pristine contributions
+        std::vector<int32_t> order;     // nodes by descending contribution
+        std::vector<int32_t> adj_off, adj;
+        int32_t max_degree = 0;
+        std::vector<int32_t> applied;   // the evidence set the image holds (its own list: a set over the limit leaves it alone)
+        std::vector<int32_t> list;
+        double seed = 0.0;              // largest pristine contribution outside N[E] for the set in force
+    } memo1;
+    bool ev_one_shot = false;       // the evidence in force arrived in the call that runs it once (bn_bp_run, bn_bp_run_view)
     // dataflow form of the resident kernel (no grid barrier; single evidence set, more than one tile block)
     int poll_sleep = 2;             // option "poll_sleep" / BN_POLL_SLEEP: pause between two polls of a waiting tile (x 512 cycles)
     int flow = 0;                   // option "flow" / BN_RESIDENT_FLOW: 1 = dataflow form where eligible, 0 = grid barrier per sweep

@@ -83,7 +83,13 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         if (int rc = memo0_ensure(e)) return rc;
         memo = bn_policy::memo0_applies({true, e->memo.valid, flow, max_sweeps, eps, e->memo.const_residual});
     }
-    if (memo) run.sweep_begin = 1;
+    // ... and from the stored second sweep where the image holds the set in force and sweep 1 is known not to end the run
+    // (bn_policy::memo1_applies): sweep 2 then reads that image instead of rec0 / node0
+    int depth = memo ? 1 : 0;
+    if (memo && e->res_cap >= 2 && bn_policy::memo1_applies({{true, e->memo.valid, flow, max_sweeps, eps, e->memo.const_residual}, e->memo1.enabled != 0,
+                                          e->memo1.built && e->memo1.holds, e->memo1.seed}))
+        depth = 2;
+    run.sweep_begin = depth;
     while (!run.done) {
         // polled words: generations count on from launch to launch, so they are zeroed only at creation, after an
         // aborted launch and before the 30-bit generation would wrap
@@ -105,14 +111,26 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
             e->gen_base = 0;
         }
         *e->h_abort = 0;
-        const bool from_image = memo && run.launches == 0;   // (one iteration less: the launches of a long run end where they always did)
-        ResidentArgs a{buffers_of(e), eps, max_sweeps, run.sweep_begin, from_image ? kResidentBudget - 1 : kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
+        const bool from_image = memo && run.launches == 0;   // (as many iterations less: the launches of a long run end where they always did)
+        // The kernel knows ONE image form: a launch that begins at sweep 1 and reads the image in the place of rec1 / node1.  A run behind
+        // the second-sweep image is that launch with its sweeps numbered one later than the run's: the buffers of the two parities
+        // exchanged, the residual history one entry further, the cap one less -- and one added to the count it reports (below).
+        const bool shifted = from_image && depth == 2;
+        BpBuffers bufs = buffers_of(e);
+        if (shifted) {
+            std::swap(bufs.rec0, bufs.rec1);
+            std::swap(bufs.node0, bufs.node1);
+            bufs.res_hist += 1;
+            bufs.res_cap -= 1;
+        }
+        ResidentArgs a{bufs, eps, shifted && max_sweeps > 0 ? max_sweeps - 1 : max_sweeps, shifted ? 1 : run.sweep_begin,
+                       from_image ? kResidentBudget - depth : kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
                        // one wait: 50 ms of the 100 MHz clock; shards: 2 s (the ranks' launches start up to a host hiccup apart)
                        shard ? 200000000ull : 5000000ull, e->d_rsync, e->h_ctl_dev,
                        rs.blocks, rs.waves, 1, 1u, 0, 0, 0, 0, 0, flow ? e->d_flow.get() : nullptr,
                        shard ? e->d_peers.get() : nullptr, shard ? e->d_pub_mask.get() : nullptr, shard ? e->plan.n_interior_tiles : 0,
                        e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort_dev, (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin,
-                       from_image ? e->memo.d_img + e->memo.word : nullptr};
+                       !from_image ? nullptr : (depth == 2 ? e->memo1.d_img + (3 * e->memo.word + e->memo1.word) : e->memo.d_img + e->memo.word)};
         if (int rc = run.begin()) return rc;
         if (int code = launch_bp_resident(a, rs.blocks + (shard ? 1 : resident_service_blocks(rs.blocks)), rs.lean, s))
             return fail(BN_ERR_HIP, std::string("bp_resident launch failed: ") + hipGetErrorString(hipError_t(code)));
@@ -142,10 +160,12 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
                           (*e->h_abort >> 8) & 0xfffu, (*e->h_abort >> 20) & 0x7ffu, e->shard_run_seq);
             return fail(BN_ERR_STATE, std::string("resident kernel gave up a bounded wait") + where);
         }
+        if (shifted && e->h_ctl->run_id == e->run_id) e->h_ctl->n_sweeps += 1;   // (the launch counted from one later)
         if (int rc = run.after_sync(BN_ERR_STATE, "resident kernel did not report (stale control block)")) return rc;
     }
     run.finish(2);
     e->stats.memo_sweeps = memo ? 1 : 0;
+    e->stats.memo_depth = depth;
     e->last_flow = flow ? 1 : 0;
     return BN_OK;
 }
@@ -371,6 +391,15 @@ static int autotune_paths(bn_engine* e, double eps) {
     const int keep[4] = {e->multisweep, e->small_mode, e->mid_mode, e->dag_mode};
     const bool keep_timing = e->timing;
     e->timing = false;
+    // A trial executes every sweep it is timed for: the resident path's stored sweeps (options "memo0", "memo1") are one or two
+    // sweeps of any run, but a third of a 6-sweep trial -- with them the resident tiles won trials they lose as whole queries
+    // (128 x 128 grid: 132 us per query against the DAG path's 118).  The images stay as they are and are used again afterwards.
+    struct ImagesOff {
+        bn_engine* e;
+        int keep0, keep1;
+        explicit ImagesOff(bn_engine* e_) : e(e_), keep0(e_->memo.enabled), keep1(e_->memo1.enabled) { e->memo.enabled = 0; e->memo1.enabled = 0; }
+        ~ImagesOff() { e->memo.enabled = keep0; e->memo1.enabled = keep1; }
+    } images_off(e);
     double best = 1e300;
     int best_i = -1;
     for (int i = 0; i < 5; ++i) {

@@ -70,6 +70,82 @@ double memo0_const_residual(const std::vector<int32_t>& order, const std::vector
     return 0.0;
 }
 
+bool memo1_applies(const Memo1Run& r) {
+    if (!memo0_applies(r.level0) || !r.enabled || !r.image_valid) return false;
+    if (r.level0.max_sweeps != 0 && r.level0.max_sweeps < 3) return false;   // the run ends behind sweep 0 or 1: they have to be executed
+    // (written so that a NaN on either side says no)
+    return r.seed > 0.0 && r.seed <= 1.7976931348623157e308 && r.level0.eps <= r.seed;
+}
+
+int32_t memo1_adjacency(int32_t n, const std::vector<int32_t>& in_ptr, const std::vector<int32_t>& in_idx, std::vector<int32_t>& adj_off,
+                        std::vector<int32_t>& adj) {
+    const size_t nn = size_t(n > 0 ? n : 0);
+    adj_off.assign(nn + 1, 0);
+    adj.clear();
+    if (in_ptr.size() < nn + 1) return 0;
+    std::vector<int32_t> deg(nn, 0);
+    for (size_t v = 0; v < nn; ++v) {
+        deg[v] += in_ptr[v + 1] - in_ptr[v];
+        for (int32_t q = in_ptr[v]; q < in_ptr[v + 1]; ++q)
+            if (in_idx[size_t(q)] >= 0 && size_t(in_idx[size_t(q)]) < nn) ++deg[size_t(in_idx[size_t(q)])];
+    }
+    int32_t dmax = 0;
+    for (size_t v = 0; v < nn; ++v) {
+        adj_off[v + 1] = adj_off[v] + deg[v];
+        dmax = deg[v] > dmax ? deg[v] : dmax;
+    }
+    adj.assign(size_t(adj_off[nn]), -1);
+    std::vector<int32_t> at(nn);
+    for (size_t v = 0; v < nn; ++v) {   // parents first ...
+        at[v] = adj_off[v];
+        for (int32_t q = in_ptr[v]; q < in_ptr[v + 1]; ++q) adj[size_t(at[v]++)] = in_idx[size_t(q)];
+    }
+    for (size_t v = 0; v < nn; ++v)     // ... then children, ascending
+        for (int32_t q = in_ptr[v]; q < in_ptr[v + 1]; ++q) {
+            const int32_t u = in_idx[size_t(q)];
+            if (u >= 0 && size_t(u) < nn) adj[size_t(at[size_t(u)]++)] = int32_t(v);
+        }
+    return dmax;
+}
+
+double memo1_seed(const std::vector<int32_t>& order, const std::vector<double>& cv1, const std::vector<int32_t>& adj_off,
+                  const std::vector<int32_t>& adj, const std::vector<uint32_t>& stamp, uint32_t epoch) {
+    auto stamped = [&](int32_t v) { return v >= 0 && size_t(v) < stamp.size() && stamp[size_t(v)] == epoch; };
+    for (int32_t v : order) {
+        if (v < 0 || size_t(v) + 1 >= adj_off.size()) continue;
+        bool ring = stamped(v);
+        for (int32_t q = adj_off[size_t(v)]; !ring && q < adj_off[size_t(v) + 1]; ++q) ring = stamped(adj[size_t(q)]);
+        if (!ring) return cv1[size_t(v)];
+    }
+    return 0.0;
+}
+
+bool memo1_patch_fits(int64_t ne, int64_t n_restore, int32_t max_degree, int64_t limit) {
+    return (ne + n_restore) * (1 + int64_t(max_degree)) <= limit;
+}
+
+Memo1Plan memo1_plan_set(const int32_t* ev_node, int32_t ne, const std::vector<uint32_t>& stamp, uint32_t epoch, bool wanted, int32_t max_degree,
+                         int64_t limit, std::vector<int32_t>& applied, std::vector<int32_t>& list) {
+    Memo1Plan r;
+    list.clear();
+    if (!wanted && (ne > 0 || !applied.empty())) return r;   // (something to apply or to restore, and no launch: nothing to work out)
+    std::vector<int32_t> restore;
+    memo0_restore_list(applied, stamp, epoch, restore);
+    if (ne <= 0 && restore.empty()) {
+        applied.clear();
+        r.holds = true;
+        return r;
+    }
+    if (!wanted || !memo1_patch_fits(ne, int64_t(restore.size()), max_degree, limit)) return r;
+    if (ne > 0) list.assign(ev_node, ev_node + ne);
+    list.insert(list.end(), restore.begin(), restore.end());
+    if (ne > 0) applied.assign(ev_node, ev_node + ne);
+    else applied.clear();
+    r.patch = true;
+    r.holds = true;
+    return r;
+}
+
 bool mid_fits(const PathFacts& f, int n_cus) {
     // the workgroups of a run wait for each other: one per CU, with room to spare
     return !(n_cus > 0 && int64_t(f.mid.parts) > int64_t(n_cus) * 9 / 10);

@@ -87,6 +87,40 @@ void memo0_restore_list(const std::vector<int32_t>& applied, const std::vector<u
 // set decides (usually the very first).  0.0 when every node carries evidence.
 double memo0_const_residual(const std::vector<int32_t>& order, const std::vector<double>& cv, const std::vector<uint32_t>& stamp, uint32_t epoch);
 
+// ---- the second-sweep image (option "memo1"; bn_device.hpp Memo1Args): what sweep 1 leaves at node v depends on the CPTs and on the
+// evidence of v's closed neighbourhood N[v] alone, so it is stored once per CPT image, recomputed on N[E + R] per evidence set, and a
+// run starts at sweep 2 ----
+struct Memo1Run {
+    Memo0Run level0;            // everything memo0_applies asks
+    bool enabled = false;       // option "memo1"
+    bool image_valid = false;   // the second-sweep image exists and holds the evidence in force
+    double seed = 0.0;          // largest pristine sweep-1 contribution among the nodes outside N[E] (memo1_seed)
+};
+// memo0_applies, and sweep 1 must be known not to end the run without looking at the ring: max_sweeps is 0 or >= 3, and eps is at
+// most the seed (the true sweep-1 residual is at least the seed), which must be finite and positive
+bool memo1_applies(const Memo1Run& r);
+// Node-level adjacency: adj[adj_off[v] .. adj_off[v + 1]) = v's parents, then its children.  From the parents' CSR of the model.
+// Returns the largest degree.
+int32_t memo1_adjacency(int32_t n, const std::vector<int32_t>& in_ptr, const std::vector<int32_t>& in_idx, std::vector<int32_t>& adj_off,
+                        std::vector<int32_t>& adj);
+// The seed: `order` lists the nodes by descending pristine contribution cv1[]; the first one with no stamped node in its closed
+// neighbourhood decides (O(degree) per candidate, usually the very first).  0.0 when every node is inside the ring.
+double memo1_seed(const std::vector<int32_t>& order, const std::vector<double>& cv1, const std::vector<int32_t>& adj_off,
+                  const std::vector<int32_t>& adj, const std::vector<uint32_t>& stamp, uint32_t epoch);
+// Whether a set patches the second-sweep image: (|E| + |R|) x (1 + max degree) threads' worth of work within the limit
+bool memo1_patch_fits(int64_t ne, int64_t n_restore, int32_t max_degree, int64_t limit);
+// What one evidence set does to the second-sweep image.  `applied` is the set that image holds (its OWN list: a set that does not
+// patch leaves the list alone, and the next set that does restores what is still non-pristine).  patch == true: `list` = E then
+// R (R = applied minus the stamped set), `applied` becomes E, the image holds the set in force.  Nothing to apply and nothing to
+// restore: no launch, the image is the pristine one and holds the (empty) set.  Over the limit, or `wanted` off (a one-shot call that
+// does not pay for the launch): no launch, `applied` and the image stay as they are, the image does not hold the set in force.
+struct Memo1Plan {
+    bool patch = false;   // launch the step kernel over `list`
+    bool holds = false;   // after this set (and the launch, if any) the image holds the set in force
+};
+Memo1Plan memo1_plan_set(const int32_t* ev_node, int32_t ne, const std::vector<uint32_t>& stamp, uint32_t epoch, bool wanted, int32_t max_degree,
+                         int64_t limit, std::vector<int32_t>& applied, std::vector<int32_t>& list);
+
 // ---- a batch of evidence sets (bn_bp_run_batch_device): the same questions for the batch forms of the paths ----
 // what only the device side knows of a batch: the per-set state of the one-workgroup path is allocated (Batch::d_s_state), a staging
 // block holds the sets' evidence (Batch::ev_base)

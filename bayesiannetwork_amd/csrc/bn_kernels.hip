@@ -276,7 +276,236 @@ __global__ __launch_bounds__(kWave) void bp_memo0_patch_kernel(Memo0Args a) {
     if (j == 0) *a.word_next = 0ull;
 }
 
-// This rank's residual slots in both buffers.  A finished run leaves them zero itself
+// ---- the second-sweep image of the resident path (bn_device.hpp Memo1Args) ---------------------------------------------------
+// One Jacobi sweep with first == false for ONE node, from a source image (records + node vectors) into a destination image of the
+// same layout: it reads the node's CPT, its vectors, its children's lambda-messages, its parents' pi-messages and its own previous
+// outgoing messages from the source and writes exactly the slots this node's lane writes in a sweep of bn_resident.hip's
+// resident_tile -- its pi-messages into the children's in-edge slots (out_refs), its lambda-messages into its own in-edge slots, its
+// new pi(v) / lambda(v) -- into the destination.  `frozen`: the node carries evidence, its vectors in the source are that evidence
+// and stay.  Level-agnostic: the source may be any sweep's state, so a later change can chain it.  Every sum and product keeps
+// resident_tile's association and order of terms (bn_tiles.hpp tile_uniform is the statement-for-statement source): lambda(v) is
+// the product of the children's lambda-messages in ascending child order from 1.0, the pi-message to child c is pi(v) times the OTHER
+// children's lambda-messages in ascending order, a missing child contributes an exact 1.0; pi(v)[i] sums (cpt pi0) pi1 over the
+// assignments in ascending order, the lambda-message to parent j sums (lambda(v)[i] cpt) pi_other with the own state outer;
+// normalisation is unguarded and res_acc drops NaN terms.  Covers what memo0_node covers.  Returns the node's residual contribution.
+// One instantiation per shape (K, M), as memo0_node_t and for its reasons: everything is requested at once and waited for once.
+template <int K, int M>
+__device__ __forceinline__ double memo_step_node_t(const BpBuffers& b, const TileDesc& td, int nl, bool frozen, const double* src_rec,
+                                                   const double* src_node, double* rec, double* node) {
+    constexpr int KP = (K + 1) & ~1, H = KP / 2, C = ipow(K, M), S = K * C, SP = (S + 1) & ~1;
+    const double2_t* cp = reinterpret_cast<const double2_t*>(b.cpt + td.cpt_base) + nl;
+    double cpt[SP];
+#pragma unroll
+    for (int q = 0; q < SP / 2; ++q) {
+        const double2_t x = cp[q * kWave];
+        cpt[2 * q] = x.x;
+        cpt[2 * q + 1] = x.y;
+    }
+    const MsgRef* orf = b.out_refs + td.out_base + nl;
+    Loc ol[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        MsgRef r{-1, 0};
+        if (c < td.cmax) r = orf[c * kWave];
+        ol[c] = decode_ref(r, H);
+    }
+    const double2_t* sr = reinterpret_cast<const double2_t*>(src_rec);
+    const int64_t rbase = td.rec_base / 2 + nl;  // this node's slot in its tile's record block (double2 units)
+    auto in_idx = [&](int j, int part, int h) -> int64_t { return rbase + int64_t((j * 2 + part) * H + h) * kWave; };
+    auto put = [&](double* base, int64_t at2, const double (&x)[K], int h) {  // chunk h of a vector as one double2, padding zero
+        double2_t y;
+        y.x = x[2 * h];
+        y.y = (2 * h + 1 < K) ? x[(2 * h + 1 < K) ? 2 * h + 1 : 0] : 0.0;
+        reinterpret_cast<double2_t*>(base)[at2] = y;
+    };
+    // the node's vectors, the parents' pi-messages, this node's previous lambda-messages
+    const double2_t* nin = reinterpret_cast<const double2_t*>(src_node) + td.node_base / 2 + nl;
+    double piv[KP], lav[KP];
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const double2_t x = nin[h * kWave], y = nin[(H + h) * kWave];
+        piv[2 * h] = x.x; piv[2 * h + 1] = x.y;
+        lav[2 * h] = y.x; lav[2 * h + 1] = y.y;
+    }
+    double pim[M > 0 ? M : 1][KP], oldl[M > 0 ? M : 1][KP];
+#pragma unroll
+    for (int j = 0; j < M; ++j)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            const double2_t x = sr[in_idx(j, 0, h)], y = sr[in_idx(j, 1, h)];
+            pim[j][2 * h] = x.x; pim[j][2 * h + 1] = x.y;
+            oldl[j][2 * h] = y.x; oldl[j][2 * h + 1] = y.y;
+        }
+    // the children's lambda-messages and this node's previous pi-messages (a missing child reads record 0 and counts as 1.0)
+    double lkc[8][KP], oldp[8][KP];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+#pragma unroll
+        for (int i = 0; i < KP; ++i) { lkc[c][i] = 1.0; oldp[c][i] = 1.0; }
+        if (c < td.cmax) {
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                const double2_t y = sr[ol[c].lam + h * ol[c].stride], x = sr[ol[c].pi + h * ol[c].stride];
+                lkc[c][2 * h] = ol[c].has ? y.x : 1.0;
+                lkc[c][2 * h + 1] = ol[c].has ? y.y : 1.0;
+                oldp[c][2 * h] = x.x; oldp[c][2 * h + 1] = x.y;
+            }
+        }
+    }
+    double res = 0.0;
+    // ---- parent role: lambda(v), the pi-message to every child
+    double lan[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        double acc = 1.0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc *= lkc[c][i];
+        lan[i] = acc;
+    }
+    normalize_k<K>(lan);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        if (c < td.cmax) {
+            double u[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                double acc = piv[i];
+#pragma unroll
+                for (int x = 0; x < 8; ++x)
+                    if (x != c) acc *= lkc[x][i];
+                u[i] = acc;
+            }
+            normalize_k<K>(u);
+            if (ol[c].has) {
+#pragma unroll
+                for (int i = 0; i < K; ++i) res = res_acc(res, fabs(u[i] - oldp[c][i]));
+#pragma unroll
+                for (int h = 0; h < H; ++h) put(rec, ol[c].pi + int64_t(h) * ol[c].stride, u, h);
+            }
+        }
+    }
+    // ---- child role: pi(v) and the lambda-message to every parent
+    double pin[K], out[M > 0 ? M : 1][K];
+#pragma unroll
+    for (int j = 0; j < (M > 0 ? M : 1); ++j)
+#pragma unroll
+        for (int i = 0; i < K; ++i) out[j][i] = 0.0;
+#pragma unroll
+    for (int ib = 0; ib < K; ++ib) {
+        if constexpr (M == 0) {
+            pin[ib] = 0.0 + cpt[ib];
+        } else {
+            double acc = 0.0;
+            if constexpr (M == 2) {
+#pragma unroll
+                for (int rr = 0; rr < K; ++rr)
+#pragma unroll
+                    for (int x = 0; x < K; ++x) {
+                        const double r = cpt[ib * C + rr * K + x];
+                        double value = r * pim[0][rr];
+                        value *= pim[1][x];
+                        acc += value;
+                        const double t = lav[ib] * r;
+                        out[0][rr] += t * pim[1][x];
+                        out[1][x] += t * pim[0][rr];
+                    }
+            } else {
+#pragma unroll
+                for (int x = 0; x < K; ++x) {
+                    double value = cpt[ib * C + x];
+                    value *= pim[0][x];
+                    acc += value;
+                }
+#pragma unroll
+                for (int x = 0; x < K; ++x) out[0][x] += lav[ib] * cpt[ib * C + x];
+            }
+            pin[ib] = acc;
+        }
+    }
+    normalize_k<K>(pin);
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        normalize_k<K>(out[j]);
+#pragma unroll
+        for (int i = 0; i < K; ++i) res = res_acc(res, fabs(out[j][i] - oldl[j][i]));
+#pragma unroll
+        for (int h = 0; h < H; ++h) put(rec, in_idx(j, 1, h), out[j], h);
+    }
+    // the node's new vectors; an evidence node keeps its evidence
+    double po[K], lo[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        po[i] = frozen ? piv[i] : pin[i];
+        lo[i] = frozen ? lav[i] : lan[i];
+    }
+    const int64_t nbase = td.node_base / 2 + nl;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        put(node, nbase + int64_t(h) * kWave, po, h);
+        put(node, nbase + int64_t(H + h) * kWave, lo, h);
+    }
+    return res;
+}
+
+__device__ __forceinline__ double memo_step_node(const BpBuffers& b, int v, bool ignore_marks, const double* src_rec, const double* src_node,
+                                                 double* rec, double* node) {
+    const int t = b.node_tile[v];
+    if (t < 0) return 0.0;
+    const TileDesc td = b.tiles[t];
+    if (td.variant != kVariantUniform || td.npt != kWave || td.cmax > 8) return 0.0;  // (the host builds no image for such a plan)
+    const int nl = b.node_nl[v];
+    const bool frozen = !ignore_marks && b.frozen[td.slot_base + nl] == b.frozen_mark;
+    switch (td.kv * 4 + td.m) {
+        case 2 * 4 + 0: return memo_step_node_t<2, 0>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 2 * 4 + 1: return memo_step_node_t<2, 1>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 2 * 4 + 2: return memo_step_node_t<2, 2>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 3 * 4 + 0: return memo_step_node_t<3, 0>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 3 * 4 + 1: return memo_step_node_t<3, 1>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 3 * 4 + 2: return memo_step_node_t<3, 2>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 4 * 4 + 0: return memo_step_node_t<4, 0>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 4 * 4 + 1: return memo_step_node_t<4, 1>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        case 4 * 4 + 2: return memo_step_node_t<4, 2>(b, td, nl, frozen, src_rec, src_node, rec, node);
+        default: return 0.0;
+    }
+}
+
+// the second-sweep image of the network without evidence (the source is the pristine first-sweep image; the marks of whatever set
+// is in force are ignored), and every node's own residual contribution in sweep 1
+__global__ __launch_bounds__(kWave) void bp_memo1_build_kernel(Memo1Args a) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= a.n) return;
+    a.cv[v] = memo_step_node(a.b, v, true, a.src_rec, a.src_node, a.rec, a.node);
+}
+
+// One launch per evidence set, behind the first-sweep patch on the same stream: thread (j, q) recomputes slot q of the closed
+// neighbourhood of listed node j -- q = 0 the node itself, then its parents and children (node-level CSR in device memory).  The marks
+// and the first-sweep image are those of the new set.  *word receives max(seed, every contribution computed): a recomputed node
+// outside N[E] gives its pristine contribution again, which the seed bounds.
+__global__ __launch_bounds__(kWave) void bp_memo1_patch_kernel(Memo1Args a) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int item = (g & ((1 << a.spread) - 1)) == 0 ? (g >> a.spread) : 0x7fffffff;
+    const int j = item / a.width, q = item - j * a.width;
+    int v = -1;
+    if (j < a.n_list) {
+        const int v0 = a.list[j];  // (page-locked host memory: one trip over the bus; the rest is device memory)
+        if (q == 0) {
+            v = v0;
+        } else {
+            const int o = a.adj_off[v0] + q - 1;
+            if (o < a.adj_off[v0 + 1]) v = a.adj[o];
+        }
+    }
+    unsigned long long bits = a.seed;
+    if (v >= 0) {
+        const unsigned long long p = (unsigned long long)__double_as_longlong(memo_step_node(a.b, v, false, a.src_rec, a.src_node, a.rec, a.node));
+        bits = p > bits ? p : bits;
+    }
+    bits = wave_umax(bits);
+    if ((threadIdx.x & (kWave - 1)) == 0) __hip_atomic_fetch_max(a.word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (g == 0) *a.word_next = 0ull;
+}
+
+// This rank's residual slots in both buffers. A finished run leaves them zero itself
 // (bp_finish_kernel); this kernel runs only after a run that did not end normally.
 __global__ __launch_bounds__(kBlockThreads) void bp_reset_kernel(BpBuffers b) {
     unsigned long long* r0 = res_row(b, b.rec0, b.rank);
@@ -363,6 +592,21 @@ int launch_bp_memo0_patch(const Memo0Args& a, void* stream) {
     const int blocks = work > 0 ? int((work + kWave - 1) / kWave) : 1;
     (void)hipGetLastError();  // drop any stale error of this thread
     hipLaunchKernelGGL(bp_memo0_patch_kernel, dim3(blocks), dim3(kWave), 0, (hipStream_t)stream, a);
+    return hip_rc(hipGetLastError());
+}
+int launch_bp_memo1_build(const Memo1Args& a, void* stream) {
+    if (a.n <= 0) return 0;
+    const int blocks = (a.n + kWave - 1) / kWave;
+    (void)hipGetLastError();  // drop any stale error of this thread
+    hipLaunchKernelGGL(bp_memo1_build_kernel, dim3(blocks), dim3(kWave), 0, (hipStream_t)stream, a);
+    return hip_rc(hipGetLastError());
+}
+int launch_bp_memo1_patch(const Memo1Args& a, void* stream) {
+    const int64_t work = (int64_t(a.n_list) * a.width) << a.spread;   // (0: one block still seeds the word)
+    if (a.width <= 0 || work > 0x7fffffff) return int(hipErrorInvalidValue);  // (the host's work limit keeps a launch far below)
+    const int blocks = work > 0 ? int((work + kWave - 1) / kWave) : 1;
+    (void)hipGetLastError();  // drop any stale error of this thread
+    hipLaunchKernelGGL(bp_memo1_patch_kernel, dim3(blocks), dim3(kWave), 0, (hipStream_t)stream, a);
     return hip_rc(hipGetLastError());
 }
 int launch_bp_reset(const BpBuffers& b, void* stream) {

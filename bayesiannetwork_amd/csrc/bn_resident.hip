@@ -1203,12 +1203,29 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
         if (blockIdx.x == 0 && threadIdx.x == 0) {  // written now rather than kept in registers for the whole run
             const unsigned long long t_first = wall_clock64();
             for (int set = 0; set < a.n_sets; ++set) a.host_ctl[set].t_first = t_first;
+            if constexpr (MODE == kModeBarrier) {
+                // a launch behind the second-sweep image counts its sweeps from one later (ResidentArgs::memo): its history begins one
+                // entry into the host's, and the entry in front of it is the first sweep's word.  Two dependent reads: left to the
+                // service block where the launch has one (below); a one-block grid does it here, where nothing is live yet
+                if (a.n_tile_blocks == 1) {
+                    if (const Memo0Image* mi = a.memo) {
+                        if (mi->word_before != nullptr) b.res_hist[-1] = residual_of(*mi->word_before);
+                    }
+                }
+            }
         }
     }
     if (int(blockIdx.x) < a.n_tile_blocks) RUNSTAMP(0, lane, wave);
     // blocks past the tile blocks serve the barrier / collect the residuals
     const int nb = a.n_tile_blocks;
     if (int(blockIdx.x) >= nb) {
+        if constexpr (MODE == kModeBarrier) {  // (off the tiles' path: in the direct form this block has nothing else to do)
+            if (threadIdx.x == 0) {
+                if (const Memo0Image* mi = a.memo) {
+                    if (mi->word_before != nullptr) b.res_hist[-1] = residual_of(*mi->word_before);
+                }
+            }
+        }
         if constexpr (FLOW) flow_service<SHARD>(a, sh, lane, wave);
         else if (wave == 0) resident_service(a, lane);
         return;
@@ -1251,7 +1268,8 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
     }
     if constexpr (MODE == kModeBarrier) {
         // the launch began behind the memoised first sweep: that sweep's residual is the word the evidence launch left (Memo0Args).
-        // Once per launch, here rather than in the tile code's report: every use of the arguments there is inlined once per tile shape
+        // Once per launch, here rather than in the tile code's report: every use of the arguments there is inlined once per tile shape.
+        // (Behind the second-sweep image this entry is the host's res_hist[1]; the one in front of it is the service block's, above.)
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             if (const Memo0Image* mi = a.memo) {
                 if (b.res_cap > 0) b.res_hist[0] = residual_of(*mi->word);

@@ -265,7 +265,7 @@ class Engine:
 
     def info(self, name: str) -> int:
         """bn_get_info: "flow_eligible", "last_flow", "nbr_max", "resident_eligible", "resident_blocks", "resident_aborts",
-        "small_eligible", "small_waves", "small_lds_bytes", "memo0_active", "memo0_bytes" ..."""
+        "small_eligible", "small_waves", "small_lds_bytes", "memo0_active", "memo0_bytes", "memo1_active" ..."""
         return _lib.check(_lib.lib().bn_get_info(self._h, name.encode()))
 
     def last_path(self) -> int:

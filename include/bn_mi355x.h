@@ -311,6 +311,13 @@ int bn_em_fit(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const
  *   nodes it drops, and a run starts at sweep 1; 0 = every run executes sweep 0.  Same sweep counts, residual histories and bits either
  *   way; runs with max_sweeps 1 or eps above sweep 0's residual execute sweep 0 regardless.  bn_get_info "memo0_active" (the image
  *   exists and is in use), "memo0_bytes"; bn_bp_stats.memo_sweeps tells what the last run did.
+ * "memo1" 1/0 -- the same one sweep further (BN_MEMO1 sets the default, 1): what sweep 1 leaves at a node depends on the CPTs and on the
+ *   evidence of the node's closed neighbourhood (itself, its parents, its children) alone.  1 = the engine also keeps the state behind
+ *   sweep 1 (one more record and node buffer, a node-level adjacency), a launch behind the one that applies an evidence set recomputes
+ *   the closed neighbourhoods of the set's nodes and of the nodes it drops, and a run starts at sweep 2; 0 = runs start at sweep 1.
+ *   Same sweep counts, residual histories and bits either way.  Runs with max_sweeps 1 or 2, or eps above what sweep 1's residual
+ *   is known to reach, start earlier; a set whose patch would cost more than a sweep (BN_MEMO1_LIMIT, in threads) does not patch, and
+ *   runs start at sweep 1 until a smaller set arrives.  bn_get_info "memo1_active"; bn_bp_stats.memo_depth tells what the last run did.
  * "poll_sleep" n -- dataflow form: pause between two polls of a waiting tile, n x 512 cycles (default 2).
  * "beliefs_direct" 1/0 -- bn_bp_run_view: the kernels write the marginals straight into the engine's mapped host
  *   buffer (default 1, outputs up to 16 MB) instead of a copy command queued behind the run.
@@ -383,6 +390,7 @@ typedef struct bn_bp_stats {
                                   the following runs down the per-sweep launches for a while (8, 16, ... runs) */
     int32_t memo_sweeps;       /* sweeps of the last run that were taken from the first-sweep image instead of being executed
                                   (option "memo0"): 0 or 1.  `sweeps` counts them all the same */
+    int32_t memo_depth;        /* sweeps of the last run taken from stored images (options "memo0", "memo1"): 0, 1 or 2 */
 } bn_bp_stats;
 int bn_bp_last_stats(bn_engine *eng, bn_bp_stats *out);
 
