@@ -92,6 +92,42 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 // K * C products of the unrolled loops and needs far more than 256 registers for their temporaries.
 __device__ __forceinline__ void pin_here(double& x) { asm volatile("" : "+v"(x)); }
 
+// Issue priority of the two waves that share a SIMD (grid-barrier form, one evidence set, 8 waves per block: waves w and w + 4 are
+// partners and leave every barrier together, so they run the same role at the same time and vector issue goes to the older one).
+// -DBN_RES_PRIO=n selects the schedule (EXPERIMENTS R21): 0 none; 1 waves 4-7 at priority 1 for the whole run; 2 in segment g of a
+// sweep (parent role, child role up to own state K / 2, the rest of the contraction, normalise + stores) the half with
+// (g + (wave >> 2)) odd holds priority 1 and the other 0, so it changes hands at every fence; 3 the same with two segments
+// (parent role, child role).  Under 2 and 3 the partner that gets ahead by one segment holds the same priority as the one behind, and
+// age decides again (R21.3); so 4: every wave runs segment g at priority 3 - g, whichever half it is in -- the wave that is BEHIND
+// holds the higher priority until it has caught up, no test of the wave number; 5 the same with three segments (parent role 2,
+// contraction 1, normalise + stores 0); 6, shipped: three segments at 3, 2 and -- waves 4-7 -- 1 or -- waves 0-3 -- 0: the wave behind
+// wins, and where the older half still led into the last segment the younger one wins that: the halves issue their sweeps together
+// (stamps, 316 x 316 grid: 5.6 / 7.1 us -> 6.6 / 6.6).  Timing only: no arithmetic, load, store or barrier moves.
+#ifndef BN_RES_PRIO
+#define BN_RES_PRIO 6
+#endif
+// Entry into segment G of a sweep under schedule SCHED; true if the schedule has a flip there.  `wave` must be the readfirstlane'd
+// scalar: the instruction ignores EXEC, so a per-lane test would set the priority of every wave
+template <int SCHED, int G>
+__device__ __forceinline__ bool prio_segment(int wave) {
+    if constexpr (SCHED == 2 || (SCHED == 3 && G < 2)) {
+        if (((wave >> 2) & 1) != (G & 1)) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+        return true;
+    } else if constexpr (SCHED == 4) {
+        __builtin_amdgcn_s_setprio(3 - G);
+        return true;
+    } else if constexpr (SCHED == 5 && G != 2) {
+        __builtin_amdgcn_s_setprio(G == 0 ? 2 : G == 1 ? 1 : 0);
+        return true;
+    } else if constexpr (SCHED == 6 && G != 2) {
+        if (G == 3 && (wave & 4) == 0) __builtin_amdgcn_s_setprio(0);
+        else __builtin_amdgcn_s_setprio(G == 0 ? 3 : G == 1 ? 2 : 1);
+        return true;
+    }
+    return false;
+}
+
 struct BlockShared {
     unsigned long long slot[kResidentMaxSets][kResidentWaves];  // per-set, per-wave residual bit patterns
     int verdict[kResidentMaxSets];                              // of a set's last barrier: kGoOn / kConverged / kCapped / kAbort
@@ -731,6 +767,8 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
     constexpr int SR = (S > 32 && !BIG) ? 28 : SP;
     static_assert(SR % 2 == 0 && (SR == SP || (S - SR) / 2 <= kResidentLdsSlots), "CPT split");
     auto PIN = [](double& x) { if constexpr (!BIG) pin_here(x); };
+    // the other forms' waves are not in phase, and a BIG block's wave has its SIMD to itself
+    constexpr int kPrio = (!BATCH && !FLOW && !BIG) ? BN_RES_PRIO : 0;
     const BpBuffers& b = a.b;
     const bool active = lane < td.n_nodes;
     const int lc = active ? lane : 0;  // idle lanes shadow lane 0 and store nothing
@@ -868,6 +906,7 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
     const size_t rec_bytes = size_t(b.rec_total_doubles) * 8;
     auto phase = [&](int set, int s) -> double {
         if constexpr (BATCH) load_nodes(set, s);
+        if constexpr (kPrio >= 2) prio_segment<kPrio, 0>(wave);
         const bool first = s == 0;
         const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(b.rec0 + (BATCH ? int64_t(set) * a.rec_stride : 0), 0, int(rec_bytes), 0x00020000);
         double* rodd = b.rec1 + (BATCH ? int64_t(set) * a.rec_stride : 0);
@@ -970,6 +1009,9 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
 
         RSTAMP(7, s - a.sweep_begin, lane, wave);  // parent role
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (kPrio >= 2) {
+            if (prio_segment<kPrio, 1>(wave)) __builtin_amdgcn_sched_barrier(0);
+        }
         // ---- child role, calculate_pi (:174-200) and calculate_lambda_k (:240-266): each accumulator
         // sees its terms in the reference's order (see tile_uniform); lambda(v)[i] * cpt is formed at each
         // use instead of being kept (same operation, same bits, 2 C fewer live registers)
@@ -999,6 +1041,9 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
                 pin[ib] = 0.0 + cpt[ib];
             } else {
                 // one own state at a time: everything this step consumes is pinned here
+                if constexpr (kPrio >= 2) {
+                    if (ib == K / 2) prio_segment<kPrio, 2>(wave);
+                }
                 PIN(lav[ib]);
 #pragma unroll
                 for (int j = 0; j < M; ++j)
@@ -1076,6 +1121,9 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
         }
         RSTAMP(8, s - a.sweep_begin, lane, wave);  // contraction
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (kPrio >= 2) {
+            if (prio_segment<kPrio, 3>(wave)) __builtin_amdgcn_sched_barrier(0);
+        }
         normalize_k<K>(pin);
 #pragma unroll
         for (int jt = 0; jt < M; ++jt) normalize_k<K>(out[jt]);
@@ -1124,6 +1172,7 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
         // several sets: a set's vectors go through memory between its turns; dataflow form: the state the run stops in
         // may be one iteration older than the registers (the stop decision lags)
         if constexpr (BATCH || FLOW) store_nodes(set, s + 1);
+        if constexpr (kPrio >= 2) __builtin_amdgcn_s_setprio(0);  // the barrier and finalize run as without a schedule
         return wres;
     };
     // the set stopped after n sweeps (or the budget ran out, done == 0): node vectors to the buffer the next
@@ -1157,6 +1206,9 @@ __device__ __forceinline__ bool resident_tile(const ResidentArgs& a, BlockShared
             }
         }
     };
+    if constexpr (kPrio == 1) {
+        if (wave & 4) __builtin_amdgcn_s_setprio(1);
+    }
     if constexpr (FLOW) return flow_drive<SHARD>(a, tile, lane, wave, phase, finalize);
     else return resident_drive<BATCH>(a, sh, lane, wave, phase, finalize);
 }

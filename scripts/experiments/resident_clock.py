@@ -1,6 +1,8 @@
 # Phase stamps of one iteration (the sixth) of the resident kernel and of the run's fixed cost (kernel entry, CPT image,
 # first sweep, last verdict, finalize), every wave: needs the diagnostic library
 #   (cd build/dbg_csrc && make EXTRA=-DBN_TILE_CLOCK OUT=../libbn_dbg.so)   and   BN_MI355X_LIB=build/libbn_dbg.so
+# Grid-barrier form (second argument 0): every phase again by half of the block -- waves 0-3 and their SIMD partners 4-7 -- with the
+# gap between the halves at "sweep issued" (EXPERIMENTS R21; EXTRA="-DBN_TILE_CLOCK -DBN_RES_PRIO=n" stamps another priority schedule)
 import ctypes
 import os
 import sys
@@ -28,7 +30,10 @@ with Engine(g) as e:
     buf = np.zeros((n, 12), dtype=np.uint64)
     rc = L.bn_debug_tile_clock_resident(buf.ctypes.data_as(ctypes.c_void_p), n)
     assert rc == 0
-    st = buf[buf[:, 1] != 0].astype(np.int64)
+    slot = np.flatnonzero(buf[:, 1] != 0)   # slot = block * 8 + wave: waves w and w + 4 of a block share a SIMD
+    st = buf[slot].astype(np.int64)
+    if not flow:   # a wave without a tile takes part in the barriers but never stamps the roles
+        slot, st = slot[st[:, 7] != 0], st[st[:, 7] != 0]
     if flow:
         st[:, 5] = st[:, 4]  # no block-level arrival in the dataflow form
     t0 = st[:, 0].min()
@@ -43,6 +48,45 @@ with Engine(g) as e:
     print(f"  {'iteration (start->published)':26s} {np.median(tot):8.0f} {np.percentile(tot, 90):8.0f} {tot.max():8.0f}")
     print("  spread of iteration starts over waves (ns):", (st[:, 0].max() - st[:, 0].min()) * 10, " of verdict arrival:", (st[:, 1].max() - st[:, 1].min()) * 10)
     print("  first start -> last publish (ns):", (st[:, 6].max() - t0) * 10)
+    if not flow:
+        # ---- the two halves of a block: waves 0-3 (dispatched first) and their SIMD partners 4-7; waves with a tile only (an idle
+        # wave never stamps the roles).  Which half is the slow one, and in which phase?
+        wave, blk = slot % 8, slot // 8
+        tiled = st[:, 7] != 0
+        release = np.full(blk.max() + 1, np.iinfo(np.int64).max)
+        np.minimum.at(release, blk, st[:, 1])   # a block's release: the first of its waves to know the verdict
+        halves = [("waves 0-3", tiled & (wave < 4)), ("waves 4-7", tiled & (wave >= 4))]
+        phases = [("verdict known", 0, 1), ("parent role", 1, 7), ("contraction", 7, 8), ("normalise + stores", 8, 3), ("drain", 3, 4),
+                  ("block sync", 4, 5), ("publish", 5, 6), ("compute: verdict -> sweep issued", 1, 3),
+                  ("verdict -> stores drained", 1, 4)]
+        print(f"  by half of the block, ns: median / p90 / max   {halves[0][0]} ({halves[0][1].sum()} waves) | {halves[1][0]} ({halves[1][1].sum()} waves)")
+        for nm, i, j in phases:
+            cells = []
+            for _, m in halves:
+                v = (st[m, j] - st[m, i]) * 10
+                cells.append(f"{np.median(v):7.0f} {np.percentile(v, 90):7.0f} {v.max():7.0f}")
+            print(f"    {nm:34s} {cells[0]}  | {cells[1]}")
+        since = (st[:, 3] - release[blk]) * 10   # "sweep issued" since the block's release
+        med = [np.median(since[m]) for _, m in halves]
+        print(f"    {'sweep issued since block release':34s} " + "  | ".join(
+            f"{np.median(since[m]):7.0f} {np.percentile(since[m], 90):7.0f} {since[m].max():7.0f}" for _, m in halves))
+        print(f"  gap between the halves' medians at 'sweep issued' (waves 4-7 minus waves 0-3): {med[1] - med[0]:.0f} ns")
+        comp = (st[:, 3] - st[:, 1]) * 10
+        print("  compute (verdict -> sweep issued) by wave number, median ns:", " ".join(f"{np.median(comp[tiled & (wave == w)]):.0f}" for w in range(8)))
+        slowest = np.argmax(np.where(tiled, comp, -1))
+        print(f"  slowest wave's compute: {comp[slowest]} ns (block {blk[slowest]}, wave {wave[slowest]})")
+        # per block: which half holds the wave that issues its sweep last, and how long the block's first four wait for it
+        last_half = np.zeros(2, dtype=np.int64)
+        wait = []
+        for bk in np.unique(blk[tiled]):
+            m = tiled & (blk == bk)
+            if (m & (wave >= 4)).sum() == 0:
+                continue
+            w_last = wave[m][np.argmax(st[m, 3])]
+            last_half[int(w_last >= 4)] += 1
+            wait.append((st[m, 3].max() - np.median(st[m, 3])) * 10)
+        print(f"  blocks whose last wave to issue is in waves 0-3 / waves 4-7: {last_half[0]} / {last_half[1]};"
+              f" last wave behind the block's median wave, median over blocks: {np.median(wait):.0f} ns")
     # ---- the run's fixed cost: what is not sweeps (stamps of the LAST run above)
     run = np.zeros((n, 8), dtype=np.uint64)
     assert L.bn_debug_run_clock_resident(run.ctypes.data_as(ctypes.c_void_p), n) == 0
