@@ -114,6 +114,11 @@ SYMBOLS = [
                                              f64p, i32p]),
     ("bn_em_fit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(EmOptions), f64p, f64p, i32p,
                                  f64p, ctypes.c_int32]),
+    ("bn_jt_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, f64p, f64p, f64p]),
+    ("bn_jt_run_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, f64p, f64p, f64p]),
+    ("bn_jt_scales", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
+    ("bn_jt_plan_dims", ctypes.c_int, [ctypes.c_void_p, i64p]),
+    ("bn_jt_plan_dump", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]),
     ("bn_set_option", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),
     ("bn_bp_last_path", ctypes.c_int, [ctypes.c_void_p]),
     ("bn_get_info", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),

@@ -7,7 +7,9 @@
 // (dense) engine, the entry points and their dispatch; bn_engine_batch_paths.cpp: the five runs of a batch and what they share;
 // bn_batch_stage.hpp / .cpp: the layout of a batch's evidence staging block (no HIP either); bn_engine_shard.cpp: RCCL communicator
 // and the in-kernel exchange of sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and
-// the fit's entry points.  No CPU compute path exists in any of them: every result comes from the kernels.
+// the fit's entry points; bn_engine_mpe.cpp, bn_engine_em.cpp, bn_engine_jt.cpp: max-product, expectation-maximisation and
+// junction-tree propagation, each over a state of its own.  No CPU compute path exists in any of them: every result comes from the
+// kernels.
 #ifndef BN_ENGINE_INTERNAL_HPP
 #define BN_ENGINE_INTERNAL_HPP
 #include <hip/hip_runtime_api.h>
@@ -38,6 +40,7 @@
 #include "bn_batch_stage.hpp"
 #include "bn_maxprod.hpp"
 #include "bn_em.hpp"
+#include "bn_jt.hpp"
 
 using namespace bnmi;
 
@@ -196,6 +199,40 @@ struct EmState {
     // the last call
     int32_t last_iters = 0;
     int64_t capped = 0, skipped = 0, estep_ns = 0, mstep_ns = 0;
+};
+
+// Junction-tree propagation (bn_engine_jt.cpp, bn_jt.hip): the plan (built at the first call that asks for it), its tables on the
+// device, the base potentials, scratch and outputs -- allocated at the first run.  Nothing here is read or written by a bn_bp_* /
+// bn_mpe_* / bn_em_* call, and a bn_jt_* call touches nothing else of the engine.
+struct JtState {
+    int form_option = 0;                // option "jt_form": 0 the rule (jt_form), 1 state in LDS, 2 state in device scratch
+    int64_t scratch_cells = kJtScratchCells;   // option "jt_scratch_cells"
+    JtPlan plan;
+    bool tried = false;                 // the planner has run (bn_get_info "jt_eligible", the plan calls, the first run)
+    bool uploaded = false;              // the item tables are on the device
+    bool psi_ready = false;             // ... and the base potentials of the CPTs in force
+    DeviceBuf<JtClique> d_cliques;
+    DeviceBuf<JtLevel> d_levels;
+    DeviceBuf<JtNode> d_nodes;
+    DeviceBuf<int32_t> d_ent_clique, d_dn_map, d_sep_clique, d_c_base, d_p_base, d_c_res, d_p_res, d_up_map, d_home_nodes, d_elem_node, d_asg_ptr;
+    DeviceBuf<JtAsg> d_asg;
+    DeviceBuf<JtFam> d_fam;
+    DeviceBuf<double> d_cpt, d_psi0;
+    DeviceBuf<double> d_scratch;        // form 2: [scratch_slots][state_cells]
+    int64_t scratch_slots = 0;
+    DeviceBuf<int32_t> d_ev_slot;       // [ev_slots][n]
+    int64_t ev_slots = 0;
+    DeviceBuf<double> d_beliefs, d_scales;   // [cap_sets][N], [cap_sets][nc]
+    int32_t cap_sets = 0;
+    PinnedBuf<char> h_ev;               // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
+    char* h_ev_dev = nullptr;
+    size_t h_ev_cap = 0;
+    // the last call
+    bool have_run = false;
+    int last_form = 0;
+    int32_t n_sets = 0, last_launches = 0;
+    int64_t last_kernel_ns = 0;         // option "timing": HIP events around the run's launches
+    std::vector<double> scales;         // [n_sets][nc]
 };
 
 struct bn_engine {
@@ -465,6 +502,7 @@ struct bn_engine {
     ScoreState score;
     MpeState mpe;
     EmState em;
+    JtState jt;
 };
 
 
@@ -566,6 +604,10 @@ void mpe_cpt_reloaded(bn_engine* e);   // bn_reload_cpt: what max-product built 
 // the "em_*" names (bn_engine_em.cpp)
 int em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t em_get_info(bn_engine* e, const char* name, bool* known);
+// the "jt_*" names (bn_engine_jt.cpp)
+int jt_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
+int64_t jt_get_info(bn_engine* e, const char* name, bool* known);
+void jt_cpt_reloaded(bn_engine* e);    // bn_reload_cpt: the base potentials are computed again at the next run
 }  // namespace bn_eng
 
 #endif  // BN_ENGINE_INTERNAL_HPP

@@ -1,0 +1,77 @@
+// bn_jt.hpp -- exact inference by junction-tree propagation: the kernels' interface (bn_jt.hip) and the rules of the arithmetic.
+// The plan and its item tables: bn_jt_plan.hpp.  The entry points: bn_engine_jt.cpp.
+//
+// Hugin-style two-pass propagation in fp64, one workgroup per evidence set, __syncthreads() between phases, no communication
+// between workgroups.  Every sum and product has a stated order that depends on the plan only -- not on the form, the workgroup
+// size or a set's position in a batch -- so the device equals the host restatement (tests/jtree_refs.py) bit for bit.
+//   Two-level sum of terms t_0, t_1, ...: runs of kJtRun (64) consecutive terms, each run added left to right from +0.0, then the
+//     run sums added left to right from +0.0.  (One lane adds one sum today; the order lets a later kernel spread a long sum.)
+//   Base potentials (once per engine and after bn_reload_cpt): psi0_c[e] = 1.0 x the entries of the CPTs assigned to c, in
+//     ascending node id.
+//   Per query: psi_c[e] = psi0_c[e] x the evidence vectors of the nodes whose home is c, in ascending node id.  Evidence is a
+//     LIKELIHOOD, hard or soft: the answer is normalise(P(x_v, e)) for every node, evidence nodes included.
+//   Collect, deepest level first: raw separator entry = two-level sum of the clique's matching entries in ascending entry index;
+//     s = the separator's entries added left to right from +0.0 (kept: the scale of the clique); the message is raw / s where s > 0,
+//     else raw; the parent's entries multiply their children's messages in, in ascending child-clique id.  A root's "separator" has
+//     one entry, the two-level sum of all its entries: the root's scale.
+//   Distribute, top level first: new = two-level sum of the parent's matching entries; ratio = new / message, and exactly 0 where
+//     the message is 0; the child's entries are multiplied by their ratio.
+//   Read-out: u[x] = two-level sum of the home clique's entries with x_v = x, ascending entry index; belief = u[x] / (u[0] + u[1] +
+//     ... left to right from +0.0), no zero guard: P(e) = 0 gives NaN.
+//   Scales: [n_cliques] in clique id order; P(e) is their product (the host adds their std::log in that order).
+#ifndef BN_JT_HPP
+#define BN_JT_HPP
+#include <cstddef>
+#include <cstdint>
+
+#include "bn_jt_plan.hpp"
+
+namespace bnmi {
+
+struct JtArgs {
+    int32_t n, N, nc, nlev;
+    int32_t pot_cells, sep_cells, state_cells;
+    int32_t set_base;               // the launch's first set: workgroup b runs set set_base + b in state slot b
+    const JtClique* cliques;
+    const JtLevel* levels;
+    const JtNode* nodes;
+    const int32_t* ent_clique;
+    const int32_t* dn_map;
+    const int32_t* sep_clique;
+    const int32_t* c_base;
+    const int32_t* p_base;
+    const int32_t* c_res;
+    const int32_t* p_res;
+    const int32_t* up_map;
+    const int32_t* home_nodes;
+    const int32_t* elem_node;
+    const double* psi0;             // [pot_cells]
+    // evidence: the caller's arrays in a staging block (bn_batch_stage.hpp), set q's header at ev_meta + 8 q
+    const int32_t* ev_node;
+    const int32_t* ev_off;
+    const double* ev_val;
+    const int32_t* ev_meta;
+    int32_t* ev_slot;               // [slots][n] scratch: where a node's evidence vector starts, -1: none
+    double* scratch;                // form 2: [slots][state_cells]
+    double* beliefs;                // [sets][N]
+    double* scales;                 // [sets][nc]
+};
+
+struct JtBaseArgs {
+    int32_t pot_cells;
+    const JtClique* cliques;
+    const int32_t* ent_clique;
+    const int32_t* asg_ptr;
+    const JtAsg* asg;
+    const JtFam* fam;
+    const double* cpt;              // the flat CPT array
+    double* psi0;
+};
+
+int launch_jt_base(const JtBaseArgs& a, void* stream);
+// form 1: state in LDS; form 2: in a.scratch.  One workgroup per set.
+int launch_jt(const JtArgs& a, int form, int n_sets, void* stream);
+
+}  // namespace bnmi
+
+#endif  // BN_JT_HPP

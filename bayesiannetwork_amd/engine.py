@@ -209,6 +209,55 @@ class Engine:
         _lib.check(_lib.lib().bn_mpe_messages(self._h, _p(pi, ctypes.c_double), _p(lam, ctypes.c_double)))
         return pi[:nm], lam[:nm]
 
+    # ---- exact inference: junction-tree propagation (bn_jt_*) -----------------------------------
+    def jt_run(self, evidence: Evidence | None = None):
+        """bn_jt_run: evidence in (a likelihood, hard or soft); "beliefs" (node-major [sum k], normalise(P(x_v, e)) for every node,
+        evidence nodes included), "log_evidence" (log P(e)) and "scales" (the scale array, [cliques]) out.  Exact on any network
+        the plan takes (info("jt_eligible"))."""
+        ev = evidence if evidence is not None else Evidence.none()
+        bel = np.empty(self._nbel, dtype=np.float64)
+        lg = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().bn_jt_run(self._h, ev.ne, _p(ev.node, ctypes.c_int32), _p(ev.off, ctypes.c_int32), _p(ev.val, ctypes.c_double),
+                                        _p(bel, ctypes.c_double), ctypes.byref(lg)))
+        return {"beliefs": bel, "log_evidence": lg.value, "scales": self.jt_scales(0)}
+
+    def jt_run_batch(self, evidences):
+        """bn_jt_run_batch: several evidence sets in one call; set q gets exactly what jt_run(evidences[q]) returns.
+        "beliefs" [n_sets, sum k], "log_evidence" [n_sets], "scales" [n_sets, cliques]."""
+        ne, node, off, val = self._pack_sets(evidences)
+        B = int(ne.size)
+        bel = np.empty((B, self._nbel), dtype=np.float64)
+        lg = np.zeros(B, dtype=np.float64)
+        _lib.check(_lib.lib().bn_jt_run_batch(self._h, B, _p(ne, ctypes.c_int32), _p(node, ctypes.c_int32), _p(off, ctypes.c_int32),
+                                              _p(val, ctypes.c_double), _p(bel, ctypes.c_double), _p(lg, ctypes.c_double)))
+        scales = np.zeros((B, max(self.info("jt_cliques"), 1)), dtype=np.float64)
+        _lib.check(_lib.lib().bn_jt_scales(self._h, -1, _p(scales, ctypes.c_double), scales.size))
+        return {"beliefs": bel, "log_evidence": lg, "scales": scales}
+
+    def jt_scales(self, set: int = 0) -> np.ndarray:
+        """The scale array of evidence set `set` of the last jt_run / jt_run_batch: their product is P(e)."""
+        nc = self.info("jt_cliques")
+        out = np.zeros(max(nc, 1), dtype=np.float64)
+        cnt = _lib.check(_lib.lib().bn_jt_scales(self._h, int(set), _p(out, ctypes.c_double), nc))
+        return out[:cnt].copy()
+
+    def jt_plan(self) -> dict:
+        """bn_jt_plan_dims + bn_jt_plan_dump: the junction tree as the kernels run it (also on host-only engines).  Raises BnError
+        (BN_ERR_STATE, with the planner's reason) where the planner stopped at a clique above its limit."""
+        L = _lib.lib()
+        d = np.zeros(12, dtype=np.int64)
+        _lib.check(L.bn_jt_plan_dims(self._h, _p(d, ctypes.c_int64)))
+        names = ("eligible", "cliques", "levels", "pot_cells", "sep_cells", "state_cells", "max_clique", "max_clique_vars", "n_vars",
+                 "n_sep_vars", "run", "form")
+        plan = {k: int(v) for k, v in zip(names, d)}
+        n, nc = self.model.n, plan["cliques"]
+        a = {"order": n, "parent": nc, "level": nc, "var_ptr": nc + 1, "vars": plan["n_vars"], "sep_ptr": nc + 1,
+             "sep_vars": plan["n_sep_vars"], "cpt_clique": n, "home": n}
+        arrs = {k: np.zeros(max(sz, 1), dtype=np.int32) for k, sz in a.items()}
+        _lib.check(L.bn_jt_plan_dump(self._h, *[_p(arrs[k], ctypes.c_int32) for k in a]))
+        plan.update({k: arrs[k][:sz] for k, sz in a.items()})
+        return plan
+
     # ---- expectation-maximisation: CPTs from a table with unobserved cells (bn_em_*) ------------
     def _em_table(self, patterns, counts):
         patterns = np.ascontiguousarray(patterns, dtype=np.uint8).reshape(-1, max(self.model.n, 1))
@@ -687,6 +736,38 @@ class MaxProduct:
             self.last = self.engine.mpe_run_batch(evs[b:b + _lib.BN_MAX_BATCH_SETS], epsilon, max_sweeps)
             out += [(st, self.log_probability(st)) for st in self.last["states"]]
         return out
+
+
+class JunctionTree:
+    """Exact marginals by junction-tree propagation -- not in the reference; the surface of ``BeliefPropagation``:
+    ``jt = JunctionTree(model); marg = jt({node: state})``, then ``jt.log_evidence`` is log P(e).
+
+    Evidence is a likelihood, hard or soft: entry v of the result is normalise(P(x_v, e)), for evidence nodes too (not the
+    reference BP's e^2 treatment of soft evidence).  Raises BnError (BN_ERR_STATE, with the planner's reason) on a network whose
+    clique tree is beyond the plan's limits."""
+
+    def __init__(self, model: FlatModel, device: int = _lib.BN_DEVICE_CURRENT):
+        self.engine = Engine(model, device)
+        self.model = model
+        self.last = None
+
+    def _evidence(self, precondition):
+        return Evidence.from_dict(self.model, precondition) if isinstance(precondition, dict) else precondition
+
+    def __call__(self, precondition=None):
+        self.last = self.engine.jt_run(self._evidence(precondition))
+        return _split(self.model, self.last["beliefs"])
+
+    @property
+    def log_evidence(self) -> float:
+        """log P(e) of the last call."""
+        return self.last["log_evidence"]
+
+    def run_batch(self, preconditions):
+        """Several evidence sets in one call: a list of (marginals, log P(e)), entry q exactly what ``self(preconditions[q])``
+        and ``self.log_evidence`` give."""
+        self.last = self.engine.jt_run_batch([self._evidence(p) for p in preconditions])
+        return [(_split(self.model, bel), float(lg)) for bel, lg in zip(self.last["beliefs"], self.last["log_evidence"])]
 
 
 class LikelihoodWeighting:

@@ -270,6 +270,62 @@ int bn_em_expected_counts(bn_engine *eng, int64_t n_patterns, const uint8_t *pat
 int bn_em_fit(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const uint64_t *counts, const bn_em_options *opt,
               const double *cpt_init, double *cpt_out, int32_t *iters_out, double *delta_hist_out, int32_t hist_cap);
 
+/*
+ * Exact inference: junction-tree (clique-tree) propagation -- an extension beside the drop-in.  bn_bp_run is exact on polytrees
+ * and an approximation on networks with loops; this path is exact on every network whose clique tree fits: Hugin-style two-pass
+ * propagation in fp64, one workgroup per evidence set, the whole query in one launch.
+ * Evidence arguments and their checks are those of bn_bp_run / bn_bp_run_batch (layout of the batch arrays: see there), but
+ * evidence is a LIKELIHOOD here, hard or soft: the answer is normalise(P(x_v, e)) for EVERY node, evidence nodes included -- not
+ * the reference BP's treatment, where an evidence node's belief is e^2 / sum(e^2) and soft evidence enters pi and lambda both.
+ * For one-hot evidence on a polytree the two agree.
+ *   beliefs_out      : [sum k] (batch: [n_sets][sum k]) node-major; P(e) = 0 gives NaN (0 / 0: no zero guard)
+ *   log_evidence_out : one value (batch: [n_sets]), may be NULL: log P(e) = the std::log of the scales added in array order;
+ *                      -inf when a factor is 0
+ *   bn_jt_scales     : the scale array of set `set` of the last run, [jt_cliques] in clique id order (returns the count written):
+ *                      per clique the sum its message to the parent was divided by, per root the total; their product is P(e).
+ *                      set = -1: every set's, [n_sets][jt_cliques] (cap must hold them all)
+ * The plan (built at the first call that asks for it; pure host work, also on BN_DEVICE_HOST_ONLY engines): moral graph, min-fill
+ * elimination (ties: smaller table of node + neighbours, then lower node id), the MAXIMAL cliques, a clique forest with every tree
+ * rooted at its centre, cliques numbered level by level.  Variables of a clique or separator: ascending node id, first most
+ * significant.  Each CPT goes to one clique that holds its family; each node has one home clique, which receives its evidence
+ * vector and is where its marginal is read.
+ *   bn_jt_plan_dims: dims_out[12] = eligible, cliques, levels, potential entries, separator entries (a root counts one), state
+ *     cells (potentials + separators + sum k + cliques), largest clique table, its variable count, sum of the cliques' variable
+ *     counts, sum of the separators', terms per run of a two-level sum (64), the form of the next run.
+ *   bn_jt_plan_dump (any pointer may be NULL): order [n] the elimination order; parent, level [cliques] (-1 / 0: a root);
+ *     var_ptr [cliques + 1] into vars; sep_ptr [cliques + 1] into sep_vars (a root has none); cpt_clique, home [n].
+ * The arithmetic (every order depends on the plan only; tests/jtree_refs.py restates it bit for bit):
+ *   two-level sum: runs of 64 consecutive terms, each added left to right from +0.0, then the run sums left to right from +0.0;
+ *   base potential of a clique = 1.0 x its CPTs' entries, ascending node id (computed on the device once, and after bn_reload_cpt);
+ *   per query: x the evidence vectors of the clique's home nodes, ascending node id;
+ *   collect, deepest level first: raw separator entry = two-level sum of the clique's matching entries, ascending entry index;
+ *     s = the separator's entries added left to right from +0.0 (the clique's scale); message = raw / s where s > 0, else raw; the
+ *     parent's entries multiply their children's messages in, ascending child id; a root's scale = two-level sum of all its entries;
+ *   distribute, top level first: new = two-level sum of the parent's matching entries; ratio = new / message, exactly 0 where the
+ *     message is 0; the child's entries are multiplied by it;
+ *   read-out: u[x] = two-level sum of the home clique's entries with x_v = x; belief = u[x] / (u[0] + u[1] + ... left to right).
+ * Limits are facts of the plan, not failures of bn_create: an elimination clique of more than 2^20 entries, or a per-set state
+ * above option "jt_scratch_cells" (doubles; 0 = the default, 2^22), make the network ineligible: BN_ERR_STATE at the run, with the
+ * planner's reason (it names the clique, its variable count and its size).  Sharded engines: BN_ERR_STATE.  BN_DEVICE_HOST_ONLY
+ * engines: BN_ERR_NO_DEVICE, after the argument checks (BN_ERR_ARG) and the plan's.
+ * Two forms from one plan, the same bits: 1 = the set's state in LDS (states of at most 8192 doubles), 2 = in a slice of device
+ * scratch; a batch in form 2 launches as many sets as the scratch holds and queues the launches behind each other.  Option
+ * "jt_form" 0 (default: 1 where it fits) / 1 / 2; forcing form 1 on a plan that does not fit gives BN_ERR_STATE at the run.
+ * bn_get_info: "jt_eligible" (builds the plan), "jt_form" (of the next run, 0 none), "jt_last_form", "jt_last_launches",
+ * "jt_cliques", "jt_max_clique", "jt_state_cells", "jt_levels"; with option "timing" 1, "jt_last_kernel_ns": HIP events around the
+ * last run's launches.
+ * A bn_jt_* call leaves everything the bn_bp_* / bn_mpe_* / bn_em_* calls use as it was; bn_reload_cpt reaches its potentials.
+ */
+#define BN_JT_MAX_BATCH_SETS 65536
+int bn_jt_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int32_t *ev_off, const double *ev_val, double *beliefs_out,
+              double *log_evidence_out);
+int bn_jt_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const int32_t *ev_node, const int32_t *ev_off,
+                    const double *ev_val, double *beliefs_out, double *log_evidence_out);
+int bn_jt_scales(bn_engine *eng, int32_t set, double *out, int32_t cap);
+int bn_jt_plan_dims(bn_engine *eng, int64_t *dims_out);
+int bn_jt_plan_dump(bn_engine *eng, int32_t *order, int32_t *parent, int32_t *level, int32_t *var_ptr, int32_t *vars, int32_t *sep_ptr,
+                    int32_t *sep_vars, int32_t *cpt_clique, int32_t *home);
+
 /* Options: "timing" 1/0 -- HIP events on the engine's stream around every batch of sweep launches
  * (bn_bp_stats.sweep_kernel_ms).  Default 0 (BN_TIMING=1 in the environment turns it on): an event
  * record between two launches opens a bubble of several microseconds in the queue, so a timed run is
