@@ -66,6 +66,12 @@ BpBuffers bn_eng::buffers_of(bn_engine* e) {
     return b;
 }
 
+int bn_eng::refuse_unusable(const bn_engine* e, int host_only_code) {
+    if (e->host_only) return fail(host_only_code, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
+    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    return BN_OK;
+}
+
 // `seen` / `epoch`: one stamp per node, kept by the engine so that a query costs O(ne), not O(n)
 int bn_eng::check_evidence(const Plan& p, int32_t ne, const int32_t* ev_node, const int32_t* ev_off,
                           std::vector<uint32_t>& seen, uint32_t& epoch) {
@@ -82,6 +88,24 @@ int bn_eng::check_evidence(const Plan& p, int32_t ne, const int32_t* ev_node, co
         seen[v] = epoch;
         if (ev_off[j + 1] - ev_off[j] != p.k[v])
             return fail(BN_ERR_ARG, "evidence vector of node " + std::to_string(v) + " must have selectable_num entries");
+    }
+    return BN_OK;
+}
+
+int bn_eng::check_evidence_sets(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t*& ev_off, const double* ev_val,
+                                bn_stage::BatchLayout& out) {
+    int64_t total = 0;
+    for (int32_t q = 0; q < n_sets; ++q) {
+        if (ne[q] < 0) return fail(BN_ERR_ARG, "negative evidence count");
+        total += ne[q];
+    }
+    if (total == 0) ev_off = nullptr;   // (nothing of it is read)
+    out = bn_stage::layout_of(n_sets, ne, ev_off);
+    for (int32_t q = 0; q < n_sets; ++q) {
+        if (ne[q] > 0 && (!ev_node || !ev_off)) return fail(BN_ERR_ARG, "null evidence array");
+        if (int rc = check_evidence(e->plan, ne[q], ev_node ? ev_node + out.node_at[q] : nullptr, ev_off ? ev_off + out.off_at[q] : nullptr, e->ev_seen, e->ev_epoch))
+            return rc;
+        if (ne[q] > 0 && !ev_val) return fail(BN_ERR_ARG, "null ev_val");
     }
     return BN_OK;
 }
@@ -132,8 +156,7 @@ int bn_eng::flush_evidence(bn_engine* e) {
 static int set_evidence_impl(bn_engine* e, int32_t ne, const int32_t* ev_node, const int32_t* ev_off,
                              const double* ev_val, bool wait) {
     if (!e) return fail(BN_ERR_ARG, "null engine");
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     const Plan& p = e->plan;
     int rc = check_evidence(p, ne, ev_node, ev_off, e->ev_seen, e->ev_epoch);
     if (rc) return rc;
@@ -150,11 +173,9 @@ static int set_evidence_impl(bn_engine* e, int32_t ne, const int32_t* ev_node, c
         // the staging block is sized ONCE, for the largest evidence set the model admits (every node observed): growing it
         // later would mean freeing page-locked memory, which waits for the whole device -- and where several shard engines share a process,
         // a rank whose kernel is already waiting for this rank's would never let that return
-        e->ev_bytes_cap = ((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64;
-        HIPCHK(host_malloc(e->h_ev, e->ev_bytes_cap, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ev_dev), e->h_ev, 0));
+        HIPCHK(e->h_ev.alloc(((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64));
     }
-    if (bytes > e->ev_bytes_cap) return fail(BN_ERR_ARG, "evidence larger than the model");
+    if (bytes > e->h_ev.capacity()) return fail(BN_ERR_ARG, "evidence larger than the model");
     // ONE kernel applies a set: it reads the arrays in place from the page-locked staging block (no copy command in the
     // queue in front of the run) and marks the nodes with this set's mark value (no memset of the previous set's marks)
     if (ne > 0) {
@@ -162,9 +183,9 @@ static int set_evidence_impl(bn_engine* e, int32_t ne, const int32_t* ev_node, c
         std::memcpy(e->h_ev + off_off, ev_off, size_t(ne + 1) * 4);
         std::memcpy(e->h_ev + off_val, ev_val, size_t(nval) * 8);
     }
-    e->d_ev_node = reinterpret_cast<int32_t*>(e->h_ev_dev + off_node);
-    e->d_ev_off = reinterpret_cast<int32_t*>(e->h_ev_dev + off_off);
-    e->d_ev_val = reinterpret_cast<double*>(e->h_ev_dev + off_val);
+    e->d_ev_node = reinterpret_cast<int32_t*>(e->h_ev.dev() + off_node);
+    e->d_ev_off = reinterpret_cast<int32_t*>(e->h_ev.dev() + off_off);
+    e->d_ev_val = reinterpret_cast<double*>(e->h_ev.dev() + off_val);
     e->ev_ne = ne;
     e->ev_nval = int32_t(nval);
     e->dag_ev_applied = false;
@@ -258,7 +279,7 @@ static int step_sweep_overlapped(bn_engine* e, int32_t sweep, double eps, bool g
 static int step_finish(bn_engine* e, int32_t launched, bool final_batch, double eps) {
     // wave 0 writes the outcome straight into the pinned host Ctl: visible after the stream
     // synchronises, no copy command in between
-    FinishArgs fa{buffers_of(e), eps, launched, final_batch ? 1 : 0, e->run_id, e->h_ctl_dev, SetStrides{}};
+    FinishArgs fa{buffers_of(e), eps, launched, final_batch ? 1 : 0, e->run_id, e->h_ctl.dev(), SetStrides{}};
     if (launch_bp_finish(fa, e->grid_tiles, 1, e->stream)) return fail(BN_ERR_HIP, "bp_finish launch failed");
     return BN_OK;
 }
@@ -543,12 +564,10 @@ extern "C" int bn_bp_run_view(bn_engine* e, int32_t ne, const int32_t* ev_node, 
     if (rc) return rc;
     if (!e->h_beliefs) {
         ON_DEVICE(e);
-        HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(e->plan.node_off[e->plan.n], 1) * sizeof(double),
-                             hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
+        HIPCHK(e->h_beliefs.alloc(size_t(e->plan.node_off[e->plan.n])));
     }
     if (e->beliefs_direct && e->plan.nranks == 1 && e->plan.node_off[e->plan.n] * 8 <= (int64_t(16) << 20)) {
-        e->beliefs_override = e->h_beliefs_dev;
+        e->beliefs_override = e->h_beliefs.dev();
         rc = run_device_impl(e, eps, max_sweeps, sweeps_out, residual_out, nullptr);
         e->beliefs_override = nullptr;
         e->beliefs_on_host_only = rc == BN_OK;

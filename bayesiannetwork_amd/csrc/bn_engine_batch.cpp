@@ -29,9 +29,8 @@ static int batch_reserve(bn_engine* e, int32_t n_sets) {
     HIPCHK(hipMemsetAsync(bt.d_ctl, 0, sizeof(Ctl) * B, e->stream));  // done_run = 0: no run is marked done
     HIPCHK(hipMemsetAsync(bt.d_frozen, 0, B * size_t(std::max(p.n_slots, 1)), e->stream));
     HIPCHK(hipMemsetAsync(bt.d_beliefs, 0, std::max<size_t>(B * p.node_off[p.n], 1) * 8, e->stream));
-    HIPCHK(host_malloc(bt.h_ctl, sizeof(Ctl) * B, hipHostMallocMapped));
+    HIPCHK(bt.h_ctl.alloc(B));
     std::memset(bt.h_ctl, 0, sizeof(Ctl) * B);
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.h_ctl_dev), bt.h_ctl, 0));
     HIPCHK(hipStreamSynchronize(e->stream));
     bt.cap_sets = n_sets;
     return BN_OK;
@@ -127,8 +126,7 @@ static int flush_batch_evidence(bn_engine* e) {
 extern "C" int bn_bp_set_evidence_batch(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node,
                                         const int32_t* ev_off, const double* ev_val) {
     if (!e) return fail(BN_ERR_ARG, "null engine");
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     e->batch_on_dense = false;
     if (n_sets >= 1 && n_sets <= BN_MAX_BATCH_SETS) {
         int rc;
@@ -172,20 +170,18 @@ extern "C" int bn_bp_set_evidence_batch(bn_engine* e, int32_t n_sets, const int3
         // workgroup per set) each set's arrays, no copy command, no evidence launch per set, no synchronisation here; the tile
         // buffers get the marks and vectors only if another path runs the batch (flush_batch_evidence).  (No kernel is in
         // flight when the block is rewritten: every run entry point synchronises before it returns.)
-        if (bytes > bt.h_ev_cap) {
-            bt.h_ev_cap = std::max<size_t>(bytes * 2, 4096);
-            HIPCHK(host_malloc(bt.h_ev, bt.h_ev_cap, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.h_ev_dev), bt.h_ev, 0));
-        }
-        bt.ev_base = bt.h_ev_dev;   // (every time: the batch before may have been staged in d_ev -- the options decide, and they may change)
+        HIPCHK(bt.h_ev.reserve(bytes));
+        bt.ev_base = bt.h_ev.dev();   // (every time: the batch before may have been staged in d_ev -- the options decide, and they may change)
         bt.ev_layout.fill(bt.h_ev, ev_node, ev_off, ev_val);
         bt.d_ev_meta = bt.ev_layout.meta(bt.ev_base);
         return BN_OK;
     }
     // every other network: one H2D copy, then one evidence kernel per set
     if (bytes > bt.ev_cap) {
-        bt.ev_cap = std::max<size_t>(bytes * 2, 4096);
-        HIPCHK(dev_malloc(bt.d_ev, bt.ev_cap));
+        const size_t cap = std::max<size_t>(bytes * 2, 4096);
+        bt.ev_cap = 0;   // (a failed allocation leaves d_ev empty)
+        HIPCHK(dev_malloc(bt.d_ev, cap));
+        bt.ev_cap = cap;
     }
     bt.ev_base = bt.d_ev;
     std::vector<char> host(std::max<size_t>(bytes, 1));
@@ -219,8 +215,7 @@ extern "C" int bn_bp_run_batch_device(bn_engine* e, double eps, int32_t max_swee
         if (rc == BN_OK) adopt_batch_outcome(e);
         return rc;
     }
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if (max_sweeps < 0) return fail(BN_ERR_ARG, "max_sweeps < 0");
     bn_engine::Batch& bt = e->batch;
     if (bt.n_sets < 1) return fail(BN_ERR_STATE, "call bn_bp_set_evidence_batch first");

@@ -95,8 +95,8 @@ static int enqueue_batch_resident_chunk(bn_engine* e, double eps, int32_t max_sw
         if ((mask >> q) & 1u) bt.h_ctl[first + q].run_id = 0;
     const SetStrides st = strides_of(e);
     ResidentArgs a{batch_buffers_of(e, first), eps, max_sweeps, begin, kResidentBudget, e->run_id, bt.gen_base, 5000000ull, bt.d_sync,
-                   bt.h_ctl_dev + first, e->shape.blocks, e->shape.waves, count, mask, st.rec, st.node, st.slot, st.belief, st.res_hist,
-                   nullptr, nullptr, nullptr, 0, nullptr, 1, 0, e->h_abort_dev};
+                   bt.h_ctl.dev() + first, e->shape.blocks, e->shape.waves, count, mask, st.rec, st.node, st.slot, st.belief, st.res_hist,
+                   nullptr, nullptr, nullptr, 0, nullptr, 1, 0, e->h_abort.dev()};
     if (int code = launch_bp_resident(a, e->shape.blocks + resident_service_blocks(e->shape.blocks), e->shape.lean, s))
         return fail(BN_ERR_HIP, std::string("bp_resident launch failed: ") + hipGetErrorString(hipError_t(code)));
     bt.gen_base += kResidentBudget + 1;
@@ -185,7 +185,7 @@ int bn_eng::run_batch_launches(bn_engine* e, double eps, int32_t max_sweeps) {
             if (launch_bp_sweep(sa, grid, B, false, p.light && !no_light, p.variants, s)) return fail(BN_ERR_HIP, "bp_sweep launch failed");
         }
         launched += batch;
-        FinishArgs fa{b0, eps, launched, (max_sweeps > 0 && launched >= max_sweeps) ? 1 : 0, e->run_id, bt.h_ctl_dev, st};
+        FinishArgs fa{b0, eps, launched, (max_sweeps > 0 && launched >= max_sweeps) ? 1 : 0, e->run_id, bt.h_ctl.dev(), st};
         if (launch_bp_finish(fa, e->grid_tiles, B, s)) return fail(BN_ERR_HIP, "bp_finish launch failed");
         HIPCHK(hipStreamSynchronize(s));
         bool all_done = true;
@@ -212,16 +212,12 @@ int bn_eng::run_batch_small(bn_engine* e, double eps, int32_t max_sweeps, double
     next_run_id(e);
     const int32_t B = bt.n_sets;
     const int64_t state_stride = 2 * int64_t(e->small.M) + 2 * int64_t(e->small.N);
-    SmallArgs a = small_args_of(e, batch_buffers_of(e, 0), eps, max_sweeps, 0, bt.h_ctl_dev);
+    SmallArgs a = small_args_of(e, batch_buffers_of(e, 0), eps, max_sweeps, 0, bt.h_ctl.dev());
     a.state = bt.d_s_state; a.sets = strides_of(e); a.state_stride = state_stride;
     const size_t per_set = size_t(p.node_off[p.n]);
     if (bt.direct_out) {  // bn_bp_run_batch: the marginals go straight into page-locked host memory (no copy command, no second sync)
-        if (size_t(B) * per_set > bt.h_beliefs_cap) {
-            bt.h_beliefs_cap = size_t(bt.cap_sets) * per_set;
-            HIPCHK(host_malloc(bt.h_beliefs, std::max<size_t>(bt.h_beliefs_cap, 1) * sizeof(double), hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&bt.h_beliefs_dev), bt.h_beliefs, 0));
-        }
-        a.b.beliefs = bt.h_beliefs_dev;
+        if (size_t(B) * per_set > bt.h_beliefs.capacity()) HIPCHK(bt.h_beliefs.alloc(size_t(bt.cap_sets) * per_set));   // (for every set the batch's buffers hold)
+        a.b.beliefs = bt.h_beliefs.dev();
     }
     bt.beliefs_on_host = bt.direct_out;
     stage_evidence_of(bt, a, 0);
@@ -232,9 +228,9 @@ int bn_eng::run_batch_small(bn_engine* e, double eps, int32_t max_sweeps, double
     for (int32_t q = 0; q < B; ++q) {
         if (bt.h_ctl[q].run_id != e->run_id) return fail(BN_ERR_HIP, "bp_small kernel did not report (stale control block)");
         while (bt.h_ctl[q].done == 0) {  // a set that used up the launch's budget of iterations goes on by itself
-            SmallArgs c = small_args_of(e, batch_buffers_of(e, q), eps, max_sweeps, bt.h_ctl[q].n_sweeps, bt.h_ctl_dev + q);
+            SmallArgs c = small_args_of(e, batch_buffers_of(e, q), eps, max_sweeps, bt.h_ctl[q].n_sweeps, bt.h_ctl.dev() + q);
             c.state = bt.d_s_state + size_t(q) * state_stride;
-            if (bt.direct_out) c.b.beliefs = bt.h_beliefs_dev + size_t(q) * per_set;
+            if (bt.direct_out) c.b.beliefs = bt.h_beliefs.dev() + size_t(q) * per_set;
             stage_evidence_of(bt, c, q);
             if (int code = launch_bp_small(c, e->small.waves, e->small.lds_bytes, 1, s))
                 return fail(BN_ERR_HIP, std::string("bp_small launch failed: ") + hipGetErrorString(hipError_t(code)));
@@ -264,7 +260,7 @@ int bn_eng::run_batch_mid(bn_engine* e, double eps, int32_t max_sweeps, double*)
     // (a chunk's sets use the state slots the previous chunk's kernel has left)
     int rc = run_chunks(e, (B + per_launch - 1) / per_launch, gave_up, launches, nullptr,
         [&](int32_t c) {
-            MidArgs a = mid_args_of(e, b0, st, bt.h_ctl_dev, eps, max_sweeps, 0, c * per_launch, 0);
+            MidArgs a = mid_args_of(e, b0, st, bt.h_ctl.dev(), eps, max_sweeps, 0, c * per_launch, 0);
             stage_evidence_of(bt, a, 0);
             return mid_launch(e, a, std::min(per_launch, B - c * per_launch), nullptr, nullptr, false);
         },
@@ -280,7 +276,7 @@ int bn_eng::run_batch_mid(bn_engine* e, double eps, int32_t max_sweeps, double*)
     if (rc != BN_OK) return rc;
     for (int32_t q = 0; q < B; ++q) {
         while (bt.h_ctl[q].done == 0) {  // a set that used up the launch's budget of iterations goes on by itself, in its slot
-            MidArgs c = mid_args_of(e, b0, st, bt.h_ctl_dev, eps, max_sweeps, bt.h_ctl[q].n_sweeps, q, q % per_launch);
+            MidArgs c = mid_args_of(e, b0, st, bt.h_ctl.dev(), eps, max_sweeps, bt.h_ctl[q].n_sweeps, q, q % per_launch);
             stage_evidence_of(bt, c, 0);
             if ((rc = mid_launch(e, c, 1, nullptr, nullptr))) return rc;
             ++launches;
@@ -357,7 +353,7 @@ static int enqueue_batch_dag_chunk(bn_engine* e, double eps, int32_t max_sweeps,
     a.eps = eps; a.max_sweeps = max_sweeps; a.sweep_begin = 0; a.budget = kDagBudget; a.run_id = e->run_id;
     a.gen_base = bt.dag_gen_base;
     a.timeout_ticks = 5000000ull;
-    a.sync = bt.d_g_sync; a.host_ctl = bt.h_ctl_dev + first; a.host_abort = e->h_abort_dev;
+    a.sync = bt.d_g_sync; a.host_ctl = bt.h_ctl.dev() + first; a.host_abort = e->h_abort.dev();
     a.n = dp.n; a.E = dp.E; a.n_blocks = dp.blocks;
     a.tiles = e->dag_img.tiles; a.slot_ptr = e->dag_img.slotptr; a.cnode = e->dag_img.cnode; a.pitem = e->dag_img.pitem; a.oedge = e->dag_img.oedge;
     a.cpt_img = e->dag_img.cpt; a.npi_init = e->dag_img.init; a.state = bt.d_g_state; a.frz = bt.d_g_frz; a.frz_mark = bt.dag_mark;

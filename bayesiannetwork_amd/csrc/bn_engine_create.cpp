@@ -319,9 +319,8 @@ static int setup_tile_images(bn_engine* e, DevLap& dev_lap) {
     if ((r = dalloc(e->d_beliefs, size_t(p.node_off[p.n])))) return r;
     HIPCHK(hipMemsetAsync(e->d_beliefs, 0, std::max<size_t>(p.node_off[p.n], 1) * 8, e->stream));
     dev_lap("state buffers");
-    HIPCHK(host_malloc(e->h_ctl, sizeof(Ctl), hipHostMallocMapped));
+    HIPCHK(e->h_ctl.alloc(1));
     std::memset(e->h_ctl, 0, sizeof(Ctl));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ctl_dev), e->h_ctl, 0));
     dev_lap("h_ctl (mapped host)");
     return BN_OK;
 }
@@ -337,9 +336,8 @@ static int setup_resident(bn_engine* e, DevLap& dev_lap) {
     const char* w = std::getenv("BN_RESIDENT_WAVES");
     e->shape = bn_policy::plan_resident(e->facts, e->n_cus, w ? std::atoi(w) : 0);
     if (e->shape.resident_ok) HIPCHK(dev_malloc(e->d_rsync, sizeof(ResidentSync)));
-    HIPCHK(host_malloc(e->h_abort, 64, hipHostMallocMapped));
+    HIPCHK(e->h_abort.alloc(64 / sizeof(unsigned)));
     std::memset(e->h_abort, 0, 64);
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_abort_dev), e->h_abort, 0));
     if (e->shape.flow_ok) {
         HIPCHK(dev_malloc(e->d_flow, flow_sync_bytes(1)));
         int r2;
@@ -348,12 +346,8 @@ static int setup_resident(bn_engine* e, DevLap& dev_lap) {
     if (p.nranks > 1) {
         // shards allocate their page-locked staging now: no allocation call may fall between two ranks' launches of a run
         // (several shard engines in one process: such calls can wait for the whole device)
-        const size_t evb = ((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64;
-        e->ev_bytes_cap = evb;
-        HIPCHK(host_malloc(e->h_ev, evb, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_ev_dev), e->h_ev, 0));
-        HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(p.node_off[p.n], 1) * sizeof(double), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
+        HIPCHK(e->h_ev.alloc(((size_t(p.n) * 4 + size_t(p.n + 1) * 4 + 7) & ~size_t(7)) + size_t(p.node_off[p.n]) * 8 + 64));
+        HIPCHK(e->h_beliefs.alloc(size_t(p.node_off[p.n])));
     }
     if (e->shape.shard_shapes_ok) {  // zeroed HERE, once: peers write into it from their kernels whenever they run
         if (e->fine_grained)
@@ -378,17 +372,8 @@ static int setup_small(bn_engine* e, DevLap& dev_lap) {
     if (e->small.ok) {
         const SmallPlan& sp = e->small;
         int r2;
-        if ((r2 = upload(e->d_s_ent, sp.ent, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_cpt, sp.ent_cpt, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_term, sp.term, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_clist, sp.clist, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_bslot, sp.bslot, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_cslot, sp.cslot, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_nvidx, sp.nv_idx, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_nvslot, sp.nv_slot, e->stream))) return r2;
-        if ((r2 = upload(e->d_s_init, sp.npi_init, e->stream))) return r2;
+        if ((r2 = upload_items(e->small_img, sp, e->stream))) return r2;
         if ((r2 = dalloc(e->d_s_state, size_t(2 * sp.M + 2 * sp.N)))) return r2;
-        if ((r2 = upload(e->d_s_nodeoff, sp.node_off, e->stream))) return r2;
         if (int code = prepare_bp_small())
             return fail(BN_ERR_HIP, std::string("bp_small attribute: ") + hipGetErrorString(hipError_t(code)));
         e->small_ok = true;
@@ -406,20 +391,8 @@ static int setup_mid(bn_engine* e, DevLap& dev_lap) {
     if (e->mid.ok) {
         MidTables t;   // (a local: mid_reserve_slots waits for the stream before it goes)
         build_mid_tables(e->mid, e->plan, t);
-        const SmallPlan& g0 = e->mid.parts[0];  // (carries the tables over all nodes)
         int r2;
-        if ((r2 = upload(e->d_m_parts, t.parts, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_ent, t.ent, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_cpt, t.ent_cpt, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_term, t.term, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_clist, t.clist, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_bslot, t.bslot, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_cslot, t.cslot, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_nvidx, g0.nv_idx, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_nvslot, g0.nv_slot, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_init, g0.npi_init, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_nodeoff, g0.node_off, e->stream))) return r2;
-        if ((r2 = upload(e->d_m_msgfirst, t.msg_first, e->stream))) return r2;
+        if ((r2 = upload_items(e->mid_img, t, e->mid.parts[0], e->stream))) return r2;   // (the first part carries the tables over all nodes)
         if ((r2 = mid_reserve_slots(e, 1))) return r2;
         if (int code = prepare_bp_mid())
             return fail(BN_ERR_HIP, std::string("bp_mid attribute: ") + hipGetErrorString(hipError_t(code)));

@@ -10,9 +10,6 @@ namespace {
 
 static_assert(bn_policy::kEmBlock == bnmi::kEmBlock && BN_EM_MISSING == kEmMissing, "bn_engine_policy.hpp / bn_mi355x.h: a constant differs from bn_em.hpp");
 
-const char kHostOnly[] = "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute";
-const char kPoisoned[] = "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)";
-
 // why the network has no one-workgroup plan, in the planner's own words
 std::string not_eligible_text(const bn_engine* e) {
     if (e->plan.nranks > 1) return "expectation-maximisation is not available on sharded engines";
@@ -114,8 +111,7 @@ int check_call(bn_engine* e, int64_t n_patterns, const uint8_t* patterns, const 
 }
 int check_engine(bn_engine* e) {
     if (e->plan.nranks > 1 || !e->small.ok) return fail(BN_ERR_STATE, not_eligible_text(e));
-    if (e->host_only) return fail(BN_ERR_NO_DEVICE, kHostOnly);
-    if (e->poisoned) return fail(BN_ERR_STATE, kPoisoned);
+    if (int rc = refuse_unusable(e, BN_ERR_NO_DEVICE)) return rc;
     if (!e->small_ok) return fail(BN_ERR_STATE, "the item tables of the one-workgroup path were not set up on the device");
     return BN_OK;
 }
@@ -164,8 +160,9 @@ int run(bn_engine* e, const EmCall& c) {
     EmSmallArgs a{};
     a.eps = c.bp_eps; a.max_sweeps = c.cap;
     a.n = sp.n; a.N = sp.N; a.M = sp.M; a.S = S; a.T = sp.T; a.TT = sp.TT; a.CL = sp.CL; a.re = sp.re; a.rb = sp.rb; a.rc = sp.rc;
-    a.ent = e->d_s_ent; a.ent_cpt = m.d_cpt; a.term = e->d_s_term; a.clist = e->d_s_clist; a.bslot = e->d_s_bslot; a.cslot = e->d_s_cslot;
-    a.npi_init = m.d_init; a.node_off = e->d_s_nodeoff; a.ent_flat = m.d_ent_flat;
+    put_items(a, e->small_img);
+    a.ent_cpt = m.d_cpt; a.npi_init = m.d_init;   // (the images the M-step rewrites, not the engine's)
+    a.ent_flat = m.d_ent_flat;
     a.b = m.d_b; a.counters = m.d_words;
     EmAccArgs acc{};
     acc.S = S; acc.n_patterns = c.n_patterns; acc.b = m.d_b; acc.counts = m.d_counts; acc.partial = m.d_partial; acc.E = m.d_E;

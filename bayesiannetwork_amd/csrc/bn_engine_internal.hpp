@@ -1,5 +1,7 @@
 // bn_engine_internal.hpp -- what the translation units of the C ABI (include/bn_mi355x.h) share: the engine object and the helpers
-// that more than one of them uses.  bn_engine.cpp: evidence, the steps of a run with one launch per sweep, options, info, read-out,
+// that more than one of them uses -- among them the one guard of the compute entry points (refuse_unusable), the one validation of
+// a call's evidence sets (check_evidence_sets) and the one device image of the item tables (ItemImage, upload_items, put_items);
+// mapped page-locked buffers are MappedBuf (bn_buffer.hpp): block, device alias and capacity in one owner.  bn_engine.cpp: evidence, the steps of a run with one launch per sweep, options, info, read-out,
 // messages; bn_engine_create.cpp: bn_create / bn_destroy, the device set-up one step per path, the stream pool, ensure_dag;
 // bn_engine_paths.cpp: the one-launch paths of a single query, their dispatch (run_device_impl) and "autotune";
 // bn_engine_policy.hpp / .cpp: which path runs a query, as pure host functions of a few facts (no HIP: checked stand-alone on a
@@ -116,6 +118,21 @@ struct DagImage {
     DeviceBuf<DagFlowSync> flow;
 };
 
+// The item tables of the one-workgroup and the several-workgroup kernels (bn_small.hpp) on the device: one image per plan -- the
+// engine's two, and the one max-product builds for itself.  upload_items fills one, put_items hands it to a kernel's arguments.
+struct ItemImage {
+    DeviceBuf<SmallEntry> ent;
+    DeviceBuf<double> ent_cpt;
+    DeviceBuf<uint32_t> term;
+    DeviceBuf<uint16_t> clist;
+    DeviceBuf<SmallSlot> bslot, cslot;
+    DeviceBuf<int32_t> nv_idx, nv_slot;
+    DeviceBuf<double> npi_init;
+    DeviceBuf<int32_t> node_off;
+    DeviceBuf<MidPart> parts;           // several workgroups only: each one's share, and the first message element of a node's in-edges
+    DeviceBuf<int32_t> msg_first;
+};
+
 // Scoring (bn_score.cpp): the log of the flat CPT and the model's structure as the scoring kernels read them, made at the
 // first bn_score_* call; bn_reload_cpt clears `ready`, so the next call takes the logarithms of the new tables.
 struct ScoreState {
@@ -137,16 +154,12 @@ struct MpeState {
     bool small_ready = false, mid_ready = false;   // the form's kernels are prepared, its state allocated
     DeviceBuf<int32_t> d_elem_node; // [N] node of a node-vector element (the lanes that decode a node's state)
     int32_t cap_sets = 0, res_cap = 0;   // what the per-set buffers below were sized for
-    PinnedBuf<double> h_mm;         // [cap_sets][N] max-marginals: mapped, the kernels write them here themselves (no copy command
-    double* h_mm_dev = nullptr;     //   behind the run: the results are there when the run's one synchronisation returns)
-    PinnedBuf<int32_t> h_states;    // [cap_sets][n], the same
-    int32_t* h_states_dev = nullptr;
+    MappedBuf<double> h_mm;         // [cap_sets][N] max-marginals: mapped, the kernels write them here themselves (no copy command
+                                    //   behind the run: the results are there when the run's one synchronisation returns)
+    MappedBuf<int32_t> h_states;    // [cap_sets][n], the same
     DeviceBuf<double> d_res_hist;   // [cap_sets][res_cap]
-    PinnedBuf<MpeCtl> h_ctl;        // [cap_sets], mapped: the kernels write it themselves
-    MpeCtl* h_ctl_dev = nullptr;
-    PinnedBuf<char> h_ev;           // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
-    char* h_ev_dev = nullptr;
-    size_t h_ev_cap = 0;
+    MappedBuf<MpeCtl> h_ctl;        // [cap_sets], mapped: the kernels write it themselves
+    MappedBuf<char> h_ev;           // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
     DeviceBuf<double> d_s_state;    // one workgroup: [small_state_sets][2 M + 2 N] the state each set's run stopped in
     int32_t small_state_sets = 0;
     DeviceBuf<double> d_m_state;    // several workgroups: pi[2][M], lam[2][M], npi[2][N], nlam[2][N]
@@ -157,14 +170,7 @@ struct MpeState {
     // run's own at its first use; bn_reload_cpt drops them.
     MidPlan own_mid;
     bool own_tried = false, own_uploaded = false;
-    DeviceBuf<MidPart> d_o_parts;
-    DeviceBuf<SmallEntry> d_o_ent;
-    DeviceBuf<double> d_o_cpt;
-    DeviceBuf<uint32_t> d_o_term;
-    DeviceBuf<uint16_t> d_o_clist;
-    DeviceBuf<SmallSlot> d_o_bslot, d_o_cslot;
-    DeviceBuf<double> d_o_init;
-    DeviceBuf<int32_t> d_o_nodeoff;
+    ItemImage own_img;
     uint32_t run_id = 0;
     // the last call
     bool have_run = false, last_single = false;
@@ -224,9 +230,7 @@ struct JtState {
     int64_t ev_slots = 0;
     DeviceBuf<double> d_beliefs, d_scales;   // [cap_sets][N], [cap_sets][nc]
     int32_t cap_sets = 0;
-    PinnedBuf<char> h_ev;               // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
-    char* h_ev_dev = nullptr;
-    size_t h_ev_cap = 0;
+    MappedBuf<char> h_ev;               // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
     // the last call
     bool have_run = false;
     int last_form = 0;
@@ -258,7 +262,6 @@ struct bn_engine {
     bool overlap = true;                 // BN_OVERLAP=0 / bn_set_option("overlap", 0): kernel and collective back to back
     DeviceBuf<uint8_t> d_frozen;
     uint8_t frozen_mark = 1;        // mark value of the evidence set in force (1..255; wrapping clears the array)
-    char* h_ev_dev = nullptr;       // h_ev as the device sees it (mapped page-locked memory: the evidence kernel reads it in place)
     DeviceBuf<int32_t> d_slot_node;
     DeviceBuf<int64_t> d_slot_boff;
     DeviceBuf<int32_t> d_node_tile;
@@ -266,9 +269,8 @@ struct bn_engine {
     DeviceBuf<double> d_res_hist;
     DeviceBuf<Ctl> d_ctl;
     DeviceBuf<double> d_beliefs;
-    // evidence staging: one pinned host block the device reads mapped, sub-pointers into h_ev_dev
-    PinnedBuf<char> h_ev;
-    size_t ev_bytes_cap = 0;
+    // evidence staging: one pinned host block the device reads mapped (the evidence kernel reads it in place), sub-pointers into h_ev.dev()
+    MappedBuf<char> h_ev;
     int32_t ev_ne = 0;
     int32_t ev_nval = 0;            // values of the evidence in force (sum of the observed nodes' arities)
     int32_t* d_ev_node = nullptr;
@@ -288,8 +290,7 @@ struct bn_engine {
     int32_t resident_aborts = 0;    // launches that gave up, over the engine's life (bn_bp_stats.resident_aborts)
     int32_t resident_cooldown = 0;  // runs left before the resident path is tried again
     int32_t resident_backoff = 8;   // length of the next pause
-    PinnedBuf<double> h_beliefs;    // pinned: bn_bp_run_view hands this out, bn_bp_run stages nothing through it
-    double* h_beliefs_dev = nullptr;  // ... as the device sees it
+    MappedBuf<double> h_beliefs;    // pinned: bn_bp_run_view hands this out, bn_bp_run stages nothing through it
     double* beliefs_override = nullptr;  // where the kernels write the beliefs of the run in hand instead of d_beliefs
     bool beliefs_on_host_only = false;   // the last run wrote its marginals into h_beliefs, not d_beliefs (synced back on demand)
     int beliefs_direct = 1;         // option "beliefs_direct": bn_bp_run_view lets the kernels write the marginals straight into
@@ -314,8 +315,7 @@ struct bn_engine {
         DeviceBuf<Memo0Image> d_img;    // [3] what the resident kernel reads: the two buffers and word q
         int word = 2;                   // the word that holds sweep 0's residual for the evidence the image holds
         int next_word = 0;              // the (zero) word of the next patch launch
-        PinnedBuf<int32_t> h_restore;   // [n] mapped: the nodes that lose their evidence, read in place by the patch launch
-        int32_t* h_restore_dev = nullptr;
+        MappedBuf<int32_t> h_restore;   // [n] mapped: the nodes that lose their evidence, read in place by the patch launch
         std::vector<double> cv;         // [n] host copy of the contributions
         std::vector<int32_t> order;     // nodes by descending contribution
         std::vector<int32_t> applied;   // the evidence set the image holds
@@ -338,8 +338,7 @@ struct bn_engine {
         DeviceBuf<Memo0Image> d_img;    // [9] what the resident kernel reads: record 3 * (first-sweep word) + (second-sweep word)
         DeviceBuf<int32_t> d_adj_off, d_adj;     // node-level CSR: parents, then children
         int word = 2, next_word = 0;
-        PinnedBuf<int32_t> h_list;      // [n] mapped: E then R, read in place by the patch launch
-        int32_t* h_list_dev = nullptr;
+        MappedBuf<int32_t> h_list;      // [n] mapped: E then R, read in place by the patch launch
         std::vector<double> cv;         // [n] host copy of the pristine contributions
         std::vector<int32_t> order;     // nodes by descending contribution
         std::vector<int32_t> adj_off, adj;
@@ -366,8 +365,7 @@ struct bn_engine {
     DeviceBuf<uint32_t> d_pub_mask;
     std::vector<uint32_t> pub_mask; // host copy (introspection)
     std::vector<void*> ipc_opened;  // hipIpcOpenMemHandle results to close
-    PinnedBuf<unsigned> h_abort;    // pinned + mapped: set by a kernel that gives up a bounded wait
-    unsigned* h_abort_dev = nullptr;
+    MappedBuf<unsigned> h_abort;    // pinned + mapped: set by a kernel that gives up a bounded wait
     uint32_t gen_base = 0;          // barrier generations used so far on d_rsync
     // several evidence sets per launch (bn_bp_*_batch): per-set records, node vectors, marks, beliefs, histories
     struct Batch {
@@ -393,21 +391,16 @@ struct bn_engine {
         uint32_t dag_gen_base = 0;
         bool ev_deferred = false;     // the sets' evidence sits in d_ev only (read there by that kernel); d_ev_meta: per set {count, first node / offset / value}
         int32_t* d_ev_meta = nullptr;   // (inside the staging block)
-        PinnedBuf<char> h_ev;           // small networks: the staging block is page-locked host memory the kernels read in place
-        char* h_ev_dev = nullptr;       // ... as the device sees it
-        char* ev_base = nullptr;        // the staging block of the batch in force as the device sees it: d_ev, or h_ev_dev
-        size_t h_ev_cap = 0;
-        PinnedBuf<double> h_beliefs;    // small networks, bn_bp_run_batch: the kernel writes every set's marginals here (mapped) ...
-        double* h_beliefs_dev = nullptr;
-        size_t h_beliefs_cap = 0;
+        MappedBuf<char> h_ev;           // small networks: the staging block is page-locked host memory the kernels read in place
+        char* ev_base = nullptr;        // the staging block of the batch in force as the device sees it: d_ev, or h_ev.dev()
+        MappedBuf<double> h_beliefs;    // small networks, bn_bp_run_batch: the kernel writes every set's marginals here (mapped) ...
         bool direct_out = false;        // ... when this is set for the run at hand
         bool beliefs_on_host = false;   // the last run's marginals are in h_beliefs, not d_beliefs
         bn_stage::BatchLayout ev_layout;   // where the arrays and each set's entries start inside the staging block
         DeviceBuf<Ctl> d_ctl;       // per-sweep launches: one control block per set
         bool rows_clean = true;     // ... and every set's residual slots are zero
         int32_t predicted_sweeps = 0;
-        PinnedBuf<Ctl> h_ctl;       // pinned, [cap_sets]
-        Ctl* h_ctl_dev = nullptr;
+        MappedBuf<Ctl> h_ctl;       // pinned + mapped, [cap_sets]
         DeviceBuf<char> d_ev;       // staging of every set's evidence
         size_t ev_cap = 0;
         // host copy of the evidence (sets run one after another when the network is not resident-eligible)
@@ -425,35 +418,15 @@ struct bn_engine {
     SmallPlan small;
     bool small_ok = false;
     int small_mode = 1;             // option "small": 0 never, 1 where it was measured faster than the other paths, 2 wherever eligible
-    DeviceBuf<SmallEntry> d_s_ent;
-    DeviceBuf<double> d_s_cpt;
-    DeviceBuf<uint32_t> d_s_term;
-    DeviceBuf<uint16_t> d_s_clist;
-    DeviceBuf<SmallSlot> d_s_bslot;
-    DeviceBuf<SmallSlot> d_s_cslot;
-    DeviceBuf<int32_t> d_s_nvidx;
-    DeviceBuf<int32_t> d_s_nvslot;
-    DeviceBuf<double> d_s_init;
+    ItemImage small_img;
     DeviceBuf<double> d_s_state;    // [2 M + 2 N] the state the last launch stopped in
-    DeviceBuf<int32_t> d_s_nodeoff;
     // networks beyond one workgroup's LDS, spread over up to 32 (bn_mid.hip): the same items, state in device memory
     MidPlan mid;
     bool mid_ok = false;
     int mid_mode = 1;               // option "mid": 0 never, 1 where eligible and the resident tiles do not cover the network, 2 wherever eligible
     int32_t small_cooldown = 0;     // (never set: the one-workgroup path waits for nobody; the path table wants a member)
     int32_t mid_cooldown = 0, mid_aborts = 0;   // runs left on the tile kernels after a grid wait gave up; how often that happened
-    DeviceBuf<MidPart> d_m_parts;
-    DeviceBuf<SmallEntry> d_m_ent;
-    DeviceBuf<double> d_m_cpt;
-    DeviceBuf<uint32_t> d_m_term;
-    DeviceBuf<uint16_t> d_m_clist;
-    DeviceBuf<SmallSlot> d_m_bslot;
-    DeviceBuf<SmallSlot> d_m_cslot;
-    DeviceBuf<int32_t> d_m_nvidx;
-    DeviceBuf<int32_t> d_m_nvslot;
-    DeviceBuf<double> d_m_init;
-    DeviceBuf<int32_t> d_m_nodeoff;
-    DeviceBuf<int32_t> d_m_msgfirst;
+    ItemImage mid_img;
     DeviceBuf<double> d_m_state;    // [4 M + 4 N]: pi[2][M], lam[2][M], npi[2][N], nlam[2][N]
     DeviceBuf<uint8_t> d_m_frz;
     DeviceBuf<char> d_m_sync;       // per state slot kMidSyncBytes: the barrier counter, the three residual words, the group counters
@@ -488,8 +461,7 @@ struct bn_engine {
                                     // >= kResidentMinTiles tiles), 2 wherever eligible (tests, experiments)
     int32_t last_path = 0;          // 0 per-sweep launches, 2 one launch for the whole run (resident tiles), 3 one workgroup, state in LDS (bn_small.hip)
     int32_t last_flow = 0;          // ... in its dataflow form
-    PinnedBuf<Ctl> h_ctl;  // pinned
-    Ctl* h_ctl_dev = nullptr;  // the same memory as the device sees it
+    MappedBuf<Ctl> h_ctl;           // pinned + mapped: the finishing kernels write it themselves
     // run state
     int32_t res_cap = 1 << 16;
     int32_t predicted_sweeps = 0;
@@ -540,6 +512,35 @@ inline int dalloc(DeviceBuf<T>& dst, size_t count) {
 }
 
 
+// the item tables of a one-workgroup plan / of a several-workgroup plan (g0: its first part, which carries the tables over all nodes)
+inline int upload_items(ItemImage& img, const SmallPlan& sp, hipStream_t s) {
+    int r;
+    if ((r = upload(img.ent, sp.ent, s)) || (r = upload(img.ent_cpt, sp.ent_cpt, s)) || (r = upload(img.term, sp.term, s)) ||
+        (r = upload(img.clist, sp.clist, s)) || (r = upload(img.bslot, sp.bslot, s)) || (r = upload(img.cslot, sp.cslot, s)) ||
+        (r = upload(img.nv_idx, sp.nv_idx, s)) || (r = upload(img.nv_slot, sp.nv_slot, s)) || (r = upload(img.npi_init, sp.npi_init, s)) ||
+        (r = upload(img.node_off, sp.node_off, s)))
+        return r;
+    return BN_OK;
+}
+inline int upload_items(ItemImage& img, const MidTables& t, const SmallPlan& g0, hipStream_t s) {
+    int r;
+    if ((r = upload(img.parts, t.parts, s)) || (r = upload(img.ent, t.ent, s)) || (r = upload(img.ent_cpt, t.ent_cpt, s)) ||
+        (r = upload(img.term, t.term, s)) || (r = upload(img.clist, t.clist, s)) || (r = upload(img.bslot, t.bslot, s)) ||
+        (r = upload(img.cslot, t.cslot, s)) || (r = upload(img.nv_idx, g0.nv_idx, s)) || (r = upload(img.nv_slot, g0.nv_slot, s)) ||
+        (r = upload(img.npi_init, g0.npi_init, s)) || (r = upload(img.node_off, g0.node_off, s)) || (r = upload(img.msg_first, t.msg_first, s)))
+        return r;
+    return BN_OK;
+}
+// the pointers every item kernel's argument struct names alike (nv_idx, nv_slot, parts, msg_first: where the struct has them)
+template <class Args>
+inline void put_items(Args& a, const ItemImage& t) {
+    a.ent = t.ent; a.ent_cpt = t.ent_cpt; a.term = t.term; a.clist = t.clist; a.bslot = t.bslot; a.cslot = t.cslot;
+    a.npi_init = t.npi_init; a.node_off = t.node_off;
+}
+
+// What every compute entry point refuses: an engine without a device (host_only_code: the code that entry point returns for it,
+// BN_ERR_STATE or BN_ERR_NO_DEVICE) and one a failed bn_reload_cpt left with device images of mixed age.  BN_OK: go on.
+int refuse_unusable(const bn_engine* e, int host_only_code);
 bn_policy::PathFacts path_facts_of(const Plan& p, const SmallPlan& small, const MidPlan& mid, const DagPlan& dag);
 inline bn_policy::PathOks oks_of(const bn_engine* e) { return {e->small_ok, e->mid_ok, e->dag_ok, e->shard_flow_ok}; }
 inline bn_policy::PathModes modes_of(const bn_engine* e) { return {e->multisweep, e->small_mode, e->mid_mode, e->dag_mode}; }
@@ -570,6 +571,10 @@ int mid_reserve_slots(bn_engine* e, int32_t slots);
 int ensure_events(bn_engine* e, size_t count);
 int check_evidence(const Plan& p, int32_t ne, const int32_t* ev_node, const int32_t* ev_off,
                           std::vector<uint32_t>& seen, uint32_t& epoch);
+// The evidence of a call that brings its sets with it (bn_mpe_*, bn_jt_*): every set validated like bn_bp_set_evidence does, at its
+// slices of the concatenated arrays; `out`: where the sets start.  No findings at all: ev_off is not read and comes back null.
+int check_evidence_sets(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t*& ev_off, const double* ev_val,
+                        bn_stage::BatchLayout& out);
 void free_engine(bn_engine* e);
 int small_gave_up(bn_engine*, const char*);
 int dag_gave_up(bn_engine* e, const char* what);

@@ -9,8 +9,6 @@
 
 namespace {
 
-const char kHostOnly[] = "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute";
-const char kPoisoned[] = "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)";
 const char kSharded[] = "junction-tree propagation is not available on sharded engines";
 
 void ensure_plan(bn_engine* e) {
@@ -75,22 +73,9 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     if (!beliefs_out) return fail(BN_ERR_ARG, "null beliefs_out");
     if (n_sets < 1 || n_sets > BN_JT_MAX_BATCH_SETS) return fail(BN_ERR_ARG, "n_sets must be in 1.." + std::to_string(BN_JT_MAX_BATCH_SETS));
     if (!ne) return fail(BN_ERR_ARG, "null ne");
-    const Plan& p = e->plan;
-    // every set is validated like bn_bp_set_evidence does, at its slices of the concatenated arrays
-    int64_t total = 0;
-    for (int32_t q = 0; q < n_sets; ++q) {
-        if (ne[q] < 0) return fail(BN_ERR_ARG, "negative evidence count");
-        total += ne[q];
-    }
-    if (total == 0) ev_off = nullptr;   // (nothing of it is read)
-    const bn_stage::BatchLayout lay = bn_stage::layout_of(n_sets, ne, ev_off);
-    for (int32_t q = 0; q < n_sets; ++q) {
-        if (ne[q] > 0 && (!ev_node || !ev_off)) return fail(BN_ERR_ARG, "null evidence array");
-        if (int rc = check_evidence(p, ne[q], ev_node ? ev_node + lay.node_at[q] : nullptr, ev_off ? ev_off + lay.off_at[q] : nullptr, e->ev_seen, e->ev_epoch))
-            return rc;
-        if (ne[q] > 0 && !ev_val) return fail(BN_ERR_ARG, "null ev_val");
-    }
-    if (p.nranks > 1) return fail(BN_ERR_STATE, kSharded);
+    bn_stage::BatchLayout lay;
+    if (int rc = check_evidence_sets(e, n_sets, ne, ev_node, ev_off, ev_val, lay)) return rc;
+    if (e->plan.nranks > 1) return fail(BN_ERR_STATE, kSharded);
     JtState& j = e->jt;
     ensure_plan(e);
     const JtPlan& P = j.plan;
@@ -99,8 +84,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     if (form == 0)
         return fail(BN_ERR_STATE, "option jt_form = 1, but the state of one evidence set, " + std::to_string(P.state_cells) + " doubles, does not fit the " +
                                       std::to_string(kJtLdsCells) + " doubles of LDS that form 1 keeps it in");
-    if (e->host_only) return fail(BN_ERR_NO_DEVICE, kHostOnly);
-    if (e->poisoned) return fail(BN_ERR_STATE, kPoisoned);
+    if (int rc = refuse_unusable(e, BN_ERR_NO_DEVICE)) return rc;
     ON_DEVICE(e);
     j.have_run = false;
     if (int rc = ensure_device(e)) return rc;
@@ -123,13 +107,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
         if ((r = dalloc(j.d_scales, size_t(n_sets) * nc))) return r;
         j.cap_sets = n_sets;
     }
-    if (lay.bytes > j.h_ev_cap) {
-        j.h_ev_cap = 0;
-        const size_t cap = std::max<size_t>(lay.bytes * 2, 4096);
-        HIPCHK(host_malloc(j.h_ev, cap, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j.h_ev_dev), j.h_ev, 0));
-        j.h_ev_cap = cap;
-    }
+    HIPCHK(j.h_ev.reserve(lay.bytes));
     // (no kernel is in flight when the staging block is rewritten: every entry point here synchronises before it returns)
     lay.fill(j.h_ev, ev_node, ev_off, ev_val);
     JtArgs a{};
@@ -138,10 +116,10 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     a.cliques = j.d_cliques; a.levels = j.d_levels; a.nodes = j.d_nodes; a.ent_clique = j.d_ent_clique; a.dn_map = j.d_dn_map;
     a.sep_clique = j.d_sep_clique; a.c_base = j.d_c_base; a.p_base = j.d_p_base; a.c_res = j.d_c_res; a.p_res = j.d_p_res;
     a.up_map = j.d_up_map; a.home_nodes = j.d_home_nodes; a.elem_node = j.d_elem_node; a.psi0 = j.d_psi0;
-    a.ev_node = reinterpret_cast<const int32_t*>(j.h_ev_dev + lay.b_node);
-    a.ev_off = reinterpret_cast<const int32_t*>(j.h_ev_dev + lay.b_off);
-    a.ev_val = reinterpret_cast<const double*>(j.h_ev_dev + lay.b_val);
-    a.ev_meta = lay.meta(j.h_ev_dev);
+    a.ev_node = reinterpret_cast<const int32_t*>(j.h_ev.dev() + lay.b_node);
+    a.ev_off = reinterpret_cast<const int32_t*>(j.h_ev.dev() + lay.b_off);
+    a.ev_val = reinterpret_cast<const double*>(j.h_ev.dev() + lay.b_val);
+    a.ev_meta = lay.meta(j.h_ev.dev());
     a.ev_slot = j.d_ev_slot; a.scratch = j.d_scratch; a.beliefs = j.d_beliefs; a.scales = j.d_scales;
     // the launches of a batch follow each other on the stream (they share the scratch slots) and the host waits once for all of them
     hipStream_t s = e->stream;

@@ -66,7 +66,7 @@ static int memo1_patch(bn_engine* e) {
     unsigned long long seed = 0;
     std::memcpy(&seed, &m1.seed, sizeof seed);
     const int32_t width = 1 + m1.max_degree;
-    Memo1Args a{buffers_of(e), m.d_rec, m.d_node, m1.d_rec, m1.d_node, nullptr, 0, int32_t(m1.list.size()), m1.h_list_dev, m1.d_adj_off, m1.d_adj,
+    Memo1Args a{buffers_of(e), m.d_rec, m.d_node, m1.d_rec, m1.d_node, nullptr, 0, int32_t(m1.list.size()), m1.h_list.dev(), m1.d_adj_off, m1.d_adj,
                 width, m1.d_words + m1.next_word, m1.d_words + (m1.next_word ^ 1), seed, memo1_spread(int64_t(m1.list.size()) * width)};
     if (int code = launch_bp_memo1_patch(a, e->stream)) {
         memo0_invalidate(e);
@@ -103,8 +103,7 @@ static int memo1_build(bn_engine* e) {
         HIPCHK(hipMemcpy(m1.d_img, img, sizeof img, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(m1.d_adj_off, m1.adj_off.data(), sizeof(int32_t) * m1.adj_off.size(), hipMemcpyHostToDevice));
         if (!m1.adj.empty()) HIPCHK(hipMemcpy(m1.d_adj, m1.adj.data(), sizeof(int32_t) * m1.adj.size(), hipMemcpyHostToDevice));
-        HIPCHK(host_malloc(m1.h_list, sizeof(int32_t) * size_t(p.n), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m1.h_list_dev), m1.h_list, 0));
+        HIPCHK(m1.h_list.alloc(size_t(p.n)));
     }
     HIPCHK(hipMemsetAsync(m1.d_rec, 0, rec_bytes, s));     // (padding and the slots of lanes without a node: never read for a result)
     HIPCHK(hipMemsetAsync(m1.d_node, 0, node_bytes, s));
@@ -145,7 +144,7 @@ static int memo0_patch_level0(bn_engine* e) {
     if (!m.restore.empty()) std::memcpy(m.h_restore.get(), m.restore.data(), m.restore.size() * sizeof(int32_t));
     unsigned long long seed = 0;
     std::memcpy(&seed, &m.const_residual, sizeof seed);
-    Memo0Args a{buffers_of(e), ne, e->d_ev_node, e->d_ev_off, e->d_ev_val, int32_t(m.restore.size()), m.h_restore_dev,
+    Memo0Args a{buffers_of(e), ne, e->d_ev_node, e->d_ev_off, e->d_ev_val, int32_t(m.restore.size()), m.h_restore.dev(),
                 m.d_rec, m.d_node, nullptr, 0, m.d_words + m.next_word, m.d_words + (m.next_word ^ 1), seed, memo0_spread(ne + int32_t(m.restore.size()))};
     if (int code = launch_bp_memo0_patch(a, e->stream)) {
         memo0_invalidate(e);
@@ -182,8 +181,7 @@ int bn_eng::memo0_ensure(bn_engine* e) {
         Memo0Image img[3];
         for (int w = 0; w < 3; ++w) img[w] = Memo0Image{m.d_rec, m.d_node, m.d_words + w, nullptr};
         HIPCHK(hipMemcpy(m.d_img, img, sizeof img, hipMemcpyHostToDevice));
-        HIPCHK(host_malloc(m.h_restore, sizeof(int32_t) * size_t(p.n), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m.h_restore_dev), m.h_restore, 0));
+        HIPCHK(m.h_restore.alloc(size_t(p.n)));
     }
     HIPCHK(hipMemsetAsync(m.d_rec, 0, rec_bytes, s));     // (padding and the slots of lanes without a node: never read for a result)
     HIPCHK(hipMemsetAsync(m.d_node, 0, node_bytes, s));

@@ -7,9 +7,6 @@
 
 namespace {
 
-const char kHostOnly[] = "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute";
-const char kPoisoned[] = "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)";
-
 // The several-workgroup plan a max-product run uses: the engine's, or -- on a network ONE workgroup holds, for which bn_create builds none --
 // a plan of its own, built when option "mpe_form" 2 first asks for it (pure host work: also on engines without a device).
 const MidPlan& mid_of(const bn_engine* e) { return e->mid.ok ? e->mid : e->mpe.own_mid; }
@@ -70,16 +67,7 @@ int reserve(bn_engine* e, int form, int32_t n_sets, int32_t res_cap, size_t ev_b
     if (form == 2 && !e->mid.ok && !m.own_uploaded) {   // the tables of the own plan (bn_engine_create.cpp setup_mid has the engine's)
         MidTables t;
         build_mid_tables(m.own_mid, p, t);
-        const SmallPlan& g0 = m.own_mid.parts[0];
-        if ((r = upload(m.d_o_parts, t.parts, e->stream))) return r;
-        if ((r = upload(m.d_o_ent, t.ent, e->stream))) return r;
-        if ((r = upload(m.d_o_cpt, t.ent_cpt, e->stream))) return r;
-        if ((r = upload(m.d_o_term, t.term, e->stream))) return r;
-        if ((r = upload(m.d_o_clist, t.clist, e->stream))) return r;
-        if ((r = upload(m.d_o_bslot, t.bslot, e->stream))) return r;
-        if ((r = upload(m.d_o_cslot, t.cslot, e->stream))) return r;
-        if ((r = upload(m.d_o_init, g0.npi_init, e->stream))) return r;
-        if ((r = upload(m.d_o_nodeoff, g0.node_off, e->stream))) return r;
+        if ((r = upload_items(m.own_img, t, m.own_mid.parts[0], e->stream))) return r;
         HIPCHK(hipStreamSynchronize(e->stream));   // (`t` is a local)
         m.own_uploaded = true;
     }
@@ -95,13 +83,10 @@ int reserve(bn_engine* e, int form, int32_t n_sets, int32_t res_cap, size_t ev_b
         const size_t B = size_t(std::max(n_sets, m.cap_sets));
         const int32_t rc = std::max(res_cap, m.res_cap);
         m.cap_sets = 0;
-        HIPCHK(host_malloc(m.h_mm, std::max<size_t>(B * N, 1) * sizeof(double), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m.h_mm_dev), m.h_mm, 0));
-        HIPCHK(host_malloc(m.h_states, std::max<size_t>(B * n, 1) * sizeof(int32_t), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m.h_states_dev), m.h_states, 0));
+        HIPCHK(m.h_mm.alloc(B * N));
+        HIPCHK(m.h_states.alloc(B * n));
         if ((r = dalloc(m.d_res_hist, B * size_t(rc)))) return r;
-        HIPCHK(host_malloc(m.h_ctl, B * sizeof(MpeCtl), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m.h_ctl_dev), m.h_ctl, 0));
+        HIPCHK(m.h_ctl.alloc(B));
         m.small_state_sets = 0;
         m.cap_sets = int32_t(B);
         m.res_cap = rc;
@@ -110,11 +95,7 @@ int reserve(bn_engine* e, int form, int32_t n_sets, int32_t res_cap, size_t ev_b
         if ((r = dalloc(m.d_s_state, size_t(m.cap_sets) * (2 * size_t(e->small.M) + 2 * size_t(e->small.N))))) return r;
         m.small_state_sets = m.cap_sets;
     }
-    if (ev_bytes > m.h_ev_cap) {
-        m.h_ev_cap = std::max<size_t>(ev_bytes * 2, 4096);
-        HIPCHK(host_malloc(m.h_ev, m.h_ev_cap, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&m.h_ev_dev), m.h_ev, 0));
-    }
+    HIPCHK(m.h_ev.reserve(ev_bytes));
     return BN_OK;
 }
 
@@ -124,15 +105,15 @@ int run_small(bn_engine* e, const bn_stage::BatchLayout& lay, int32_t n_sets, do
     const SmallPlan& sp = e->small;
     MpeSmallArgs a{};
     a.eps = eps; a.max_sweeps = cap; a.sweep_begin = 0; a.budget = kSmallBudget; a.run_id = m.run_id;
-    a.host_ctl = m.h_ctl_dev;
+    a.host_ctl = m.h_ctl.dev();
     a.n = sp.n; a.N = sp.N; a.M = sp.M; a.T = sp.T; a.TT = sp.TT; a.CL = sp.CL; a.re = sp.re; a.rb = sp.rb; a.rc = sp.rc;
-    a.ent = e->d_s_ent; a.ent_cpt = e->d_s_cpt; a.term = e->d_s_term; a.clist = e->d_s_clist; a.bslot = e->d_s_bslot; a.cslot = e->d_s_cslot;
-    a.npi_init = e->d_s_init; a.node_off = e->d_s_nodeoff; a.elem_node = m.d_elem_node;
-    a.ev_node = reinterpret_cast<const int32_t*>(m.h_ev_dev + lay.b_node);
-    a.ev_off = reinterpret_cast<const int32_t*>(m.h_ev_dev + lay.b_off);
-    a.ev_val = reinterpret_cast<const double*>(m.h_ev_dev + lay.b_val);
-    a.ev_meta = lay.meta(m.h_ev_dev);
-    a.max_marginals = m.h_mm_dev; a.states = m.h_states_dev; a.res_hist = m.d_res_hist; a.state = m.d_s_state; a.res_cap = m.res_cap;
+    put_items(a, e->small_img);
+    a.elem_node = m.d_elem_node;
+    a.ev_node = reinterpret_cast<const int32_t*>(m.h_ev.dev() + lay.b_node);
+    a.ev_off = reinterpret_cast<const int32_t*>(m.h_ev.dev() + lay.b_off);
+    a.ev_val = reinterpret_cast<const double*>(m.h_ev.dev() + lay.b_val);
+    a.ev_meta = lay.meta(m.h_ev.dev());
+    a.max_marginals = m.h_mm.dev(); a.states = m.h_states.dev(); a.res_hist = m.d_res_hist; a.state = m.d_s_state; a.res_cap = m.res_cap;
     // a set that stops leaves done != 0; a launch that ends on its budget continues every set from the smallest sweep count reached --
     // only a cap above kSmallBudget sweeps gets there, and then with a single set (a batch's sets would not stay in step)
     for (;;) {
@@ -155,24 +136,22 @@ int run_small(bn_engine* e, const bn_stage::BatchLayout& lay, int32_t n_sets, do
 int run_mid(bn_engine* e, const bn_stage::BatchLayout& lay, int32_t n_sets, double eps, int32_t cap) {
     MpeState& m = e->mpe;
     const MidPlan& mp = mid_of(e);
-    const bool own = !e->mid.ok;
+    const ItemImage& t = e->mid.ok ? e->mid_img : m.own_img;
     const SmallPlan& g0 = mp.parts[0];
     const size_t M = size_t(g0.M), N = size_t(g0.N);
     MpeMidArgs a{};
     a.eps = eps; a.max_sweeps = cap; a.run_id = m.run_id;
     a.n = g0.n; a.N = g0.N; a.M = g0.M; a.nparts = int32_t(mp.parts.size());
-    a.parts = own ? m.d_o_parts : e->d_m_parts; a.ent = own ? m.d_o_ent : e->d_m_ent; a.ent_cpt = own ? m.d_o_cpt : e->d_m_cpt;
-    a.term = own ? m.d_o_term : e->d_m_term; a.clist = own ? m.d_o_clist : e->d_m_clist;
-    a.bslot = own ? m.d_o_bslot : e->d_m_bslot; a.cslot = own ? m.d_o_cslot : e->d_m_cslot;
-    a.npi_init = own ? m.d_o_init : e->d_m_init; a.node_off = own ? m.d_o_nodeoff : e->d_m_nodeoff; a.elem_node = m.d_elem_node;
+    put_items(a, t);
+    a.parts = t.parts; a.elem_node = m.d_elem_node;
     a.pi = m.d_m_state; a.lam = a.pi + 2 * M; a.npi = a.lam + 2 * M; a.nlam = a.npi + 2 * N;
     a.frz = m.d_m_frz; a.sync = m.d_m_sync; a.res_cap = m.res_cap;
     const int32_t group = std::max(1, std::min(m.group, kMpeMaxGroup));
     for (int32_t q = 0; q < n_sets; ++q) {
-        const bn_stage::SetView v = lay.set_view(m.h_ev_dev, q);
-        a.host_ctl = m.h_ctl_dev + q;
+        const bn_stage::SetView v = lay.set_view(m.h_ev.dev(), q);
+        a.host_ctl = m.h_ctl.dev() + q;
         a.ev_ne = v.ne; a.ev_node = v.node; a.ev_off = v.off; a.ev_val = v.val;
-        a.max_marginals = m.h_mm_dev + size_t(q) * N; a.states = m.h_states_dev + size_t(q) * size_t(g0.n); a.res_hist = m.d_res_hist + size_t(q) * size_t(m.res_cap);
+        a.max_marginals = m.h_mm.dev() + size_t(q) * N; a.states = m.h_states.dev() + size_t(q) * size_t(g0.n); a.res_hist = m.d_res_hist + size_t(q) * size_t(m.res_cap);
         int code = launch_mpe_mid_init(a, e->stream);
         if (!code) code = launch_mpe_mid_evidence(a, e->stream);
         if (code) return fail(BN_ERR_HIP, std::string("mpe_mid set-up launch failed: ") + hipGetErrorString(hipError_t(code)));
@@ -202,27 +181,14 @@ int mpe_run_impl(bn_engine* e, bool single, int32_t n_sets, const int32_t* ne, c
     if (n_sets < 1 || n_sets > BN_MAX_BATCH_SETS) return fail(BN_ERR_ARG, "n_sets must be in 1.." + std::to_string(BN_MAX_BATCH_SETS));
     if (!ne) return fail(BN_ERR_ARG, "null ne");
     const Plan& p = e->plan;
-    // every set is validated like bn_bp_set_evidence does, at its slices of the concatenated arrays
-    int64_t total = 0;
-    for (int32_t q = 0; q < n_sets; ++q) {
-        if (ne[q] < 0) return fail(BN_ERR_ARG, "negative evidence count");
-        total += ne[q];
-    }
-    if (total == 0) ev_off = nullptr;   // (nothing of it is read)
-    const bn_stage::BatchLayout lay = bn_stage::layout_of(n_sets, ne, ev_off);
-    for (int32_t q = 0; q < n_sets; ++q) {
-        if (ne[q] > 0 && (!ev_node || !ev_off)) return fail(BN_ERR_ARG, "null evidence array");
-        if (int rc = check_evidence(p, ne[q], ev_node ? ev_node + lay.node_at[q] : nullptr, ev_off ? ev_off + lay.off_at[q] : nullptr, e->ev_seen, e->ev_epoch))
-            return rc;
-        if (ne[q] > 0 && !ev_val) return fail(BN_ERR_ARG, "null ev_val");
-    }
+    bn_stage::BatchLayout lay;
+    if (int rc = check_evidence_sets(e, n_sets, ne, ev_node, ev_off, ev_val, lay)) return rc;
     if (max_sweeps < 0) return fail(BN_ERR_ARG, "max_sweeps < 0");
     if (p.nranks > 1) return fail(BN_ERR_STATE, "max-product is not available on sharded engines");
     MpeState& m = e->mpe;
     const int form = form_of(e);
     if (form == 0) return fail(BN_ERR_STATE, no_form_text(e, m.form_option));
-    if (e->host_only) return fail(BN_ERR_STATE, kHostOnly);
-    if (e->poisoned) return fail(BN_ERR_STATE, kPoisoned);
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if ((form == 1 && !e->small_ok) || (form == 2 && e->mid.ok && !e->mid_ok)) return fail(BN_ERR_STATE, "the item tables of this form were not set up on the device");
     const int32_t cap = max_sweeps == 0 ? kMpeDefaultCap : max_sweeps;   // never unbounded (bn_maxprod.hpp)
     ON_DEVICE(e);
@@ -328,5 +294,8 @@ void bn_eng::mpe_cpt_reloaded(bn_engine* e) {
     MpeState& m = e->mpe;
     m.own_mid = MidPlan();
     m.own_tried = false;
-    m.own_uploaded = false;   // (the device tables are replaced at the next upload; no kernel is in flight: every entry point synchronises)
+    m.own_uploaded = false;
+    DeviceGuard guard;        // (device memory is released on the engine's device; no kernel is in flight: every entry point synchronises)
+    if (!e->host_only) (void)guard.enter(e->device);
+    m.own_img = ItemImage();
 }

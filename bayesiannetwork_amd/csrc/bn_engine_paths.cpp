@@ -126,10 +126,10 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         ResidentArgs a{bufs, eps, shifted && max_sweeps > 0 ? max_sweeps - 1 : max_sweeps, shifted ? 1 : run.sweep_begin,
                        from_image ? kResidentBudget - depth : kResidentBudget, e->run_id, flow ? e->flow_gen_base : e->gen_base,
                        // one wait: 50 ms of the 100 MHz clock; shards: 2 s (the ranks' launches start up to a host hiccup apart)
-                       shard ? 200000000ull : 5000000ull, e->d_rsync, e->h_ctl_dev,
+                       shard ? 200000000ull : 5000000ull, e->d_rsync, e->h_ctl.dev(),
                        rs.blocks, rs.waves, 1, 1u, 0, 0, 0, 0, 0, flow ? e->d_flow.get() : nullptr,
                        shard ? e->d_peers.get() : nullptr, shard ? e->d_pub_mask.get() : nullptr, shard ? e->plan.n_interior_tiles : 0,
-                       e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort_dev, (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin,
+                       e->d_nbr, e->plan.nbr_chunks, e->poll_sleep, e->h_abort.dev(), (!flow && !shard) ? e->resident_direct : 0, e->resident_poll_margin,
                        !from_image ? nullptr : (depth == 2 ? e->memo1.d_img + (3 * e->memo.word + e->memo1.word) : e->memo.d_img + e->memo.word)};
         if (int rc = run.begin()) return rc;
         if (int code = launch_bp_resident(a, rs.blocks + (shard ? 1 : resident_service_blocks(rs.blocks)), rs.lean, s))
@@ -144,8 +144,7 @@ static int run_resident(bn_engine* e, double eps, int32_t max_sweeps, double* co
         if (copy_to && shard) {  // through the engine's page-locked buffer: a plain DMA, nothing that blocks inside the runtime
             const size_t bytes = sizeof(double) * e->plan.node_off[e->plan.n];
             if (copy_to != e->h_beliefs && !e->h_beliefs) {
-                HIPCHK(host_malloc(e->h_beliefs, std::max<size_t>(bytes, 8), hipHostMallocMapped));
-                HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_beliefs_dev), e->h_beliefs, 0));
+                HIPCHK(e->h_beliefs.alloc(size_t(e->plan.node_off[e->plan.n])));
             }
             HIPCHK(hipMemcpyAsync(e->h_beliefs, e->d_beliefs, bytes, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
@@ -177,11 +176,10 @@ SmallArgs bn_eng::small_args_of(bn_engine* e, const BpBuffers& b, double eps, in
     a.host_ctl = host_ctl;
     a.n = sp.n; a.N = sp.N; a.M = sp.M; a.S = sp.S; a.T = sp.T; a.TT = sp.TT; a.CL = sp.CL;
     a.re = sp.re; a.rb = sp.rb; a.rc = sp.rc; a.mmax = sp.mmax;
-    a.ent = e->d_s_ent; a.ent_cpt = e->d_s_cpt; a.term = e->d_s_term; a.clist = e->d_s_clist;
-    a.bslot = e->d_s_bslot; a.cslot = e->d_s_cslot; a.nv_idx = e->d_s_nvidx; a.nv_slot = e->d_s_nvslot; a.npi_init = e->d_s_init;
+    put_items(a, e->small_img);
+    a.nv_idx = e->small_img.nv_idx; a.nv_slot = e->small_img.nv_slot;
     a.state = e->d_s_state; a.sets = SetStrides{}; a.state_stride = 0;
     a.ev_mode = 0; a.ev_ne = 0; a.ev_nval = 0; a.ev_node = nullptr; a.ev_off = nullptr; a.ev_val = nullptr; a.ev_meta = nullptr;
-    a.node_off = e->d_s_nodeoff;
     return a;
 }
 
@@ -190,7 +188,7 @@ static int run_small(bn_engine* e, double eps, int32_t max_sweeps, double* copy_
     hipStream_t s = e->stream;
     OneLaunchRun run(e);
     while (!run.done) {
-        SmallArgs a = small_args_of(e, buffers_of(e), eps, max_sweeps, run.sweep_begin, e->h_ctl_dev);
+        SmallArgs a = small_args_of(e, buffers_of(e), eps, max_sweeps, run.sweep_begin, e->h_ctl.dev());
         if (e->ev_deferred) {  // the evidence in force was never written to the tile buffers: the kernel reads the staging block
             a.ev_mode = 1; a.ev_ne = e->ev_ne; a.ev_nval = e->ev_nval; a.ev_node = e->d_ev_node; a.ev_off = e->d_ev_off; a.ev_val = e->d_ev_val;
         }
@@ -216,16 +214,15 @@ MidArgs bn_eng::mid_args_of(bn_engine* e, const BpBuffers& b0, const SetStrides&
     a.b = b0; a.eps = eps; a.max_sweeps = max_sweeps; a.sweep_begin = begin; a.budget = kSmallBudget; a.run_id = e->run_id;
     a.host_ctl = h_ctl_dev;
     a.n = g0.n; a.N = g0.N; a.M = g0.M; a.nparts = int32_t(e->mid.parts.size());
-    a.parts = e->d_m_parts; a.ent = e->d_m_ent; a.ent_cpt = e->d_m_cpt; a.term = e->d_m_term; a.clist = e->d_m_clist;
-    a.bslot = e->d_m_bslot; a.cslot = e->d_m_cslot; a.nv_idx = e->d_m_nvidx; a.nv_slot = e->d_m_nvslot; a.npi_init = e->d_m_init;
-    a.node_off = e->d_m_nodeoff; a.msg_first = e->d_m_msgfirst;
+    put_items(a, e->mid_img);
+    a.parts = e->mid_img.parts; a.nv_idx = e->mid_img.nv_idx; a.nv_slot = e->mid_img.nv_slot; a.msg_first = e->mid_img.msg_first;
     a.ev_mode = 0; a.ev_ne = 0; a.ev_node = nullptr; a.ev_off = nullptr; a.ev_val = nullptr; a.ev_meta = nullptr;
     a.state_stride = 4 * int64_t(g0.M) + 4 * int64_t(g0.N);
     a.pi = e->d_m_state; a.lam = a.pi + 2 * size_t(g0.M); a.npi = a.lam + 2 * size_t(g0.M); a.nlam = a.npi + 2 * size_t(g0.N);
     a.frz = e->d_m_frz;
     a.bar = reinterpret_cast<unsigned*>(e->d_m_sync.get());
     a.res = reinterpret_cast<unsigned long long*>(e->d_m_sync + 8);
-    a.abort = e->h_abort_dev;
+    a.abort = e->h_abort.dev();
     a.timeout_ticks = 5000000ull;  // one wait: 50 ms of the 100 MHz clock
     // first poll of the grid barrier placed by the previous barrier's lag (arrival times in the granules, as bn_dag.hip / bn_resident.hip do):
     // BN_MID_DELAY = margin in 10 ns ticks, -1 (default) = poll from the own arrival on.  mixed10k, us per sweep: 8.30 off, 8.17 at 0,
@@ -260,7 +257,7 @@ static int run_mid(bn_engine* e, double eps, int32_t max_sweeps, double* copy_to
     OneLaunchRun run(e, false);   // (no events around this path's launches: sweep_kernel_ms reads 0)
     const BpBuffers b = buffers_of(e);
     while (!run.done) {
-        MidArgs a = mid_args_of(e, b, SetStrides{}, e->h_ctl_dev, eps, max_sweeps, run.sweep_begin, 0, 0);
+        MidArgs a = mid_args_of(e, b, SetStrides{}, e->h_ctl.dev(), eps, max_sweeps, run.sweep_begin, 0, 0);
         if (e->ev_deferred) {  // the evidence in force was never written to the tile buffers: the kernel reads the staging block
             a.ev_mode = 1; a.ev_ne = e->ev_ne; a.ev_node = e->d_ev_node; a.ev_off = e->d_ev_off; a.ev_val = e->d_ev_val;
         }
@@ -328,7 +325,7 @@ int bn_eng::run_dag_query(bn_engine* e, double eps, int32_t max_sweeps, double* 
         a.b = b; a.eps = eps; a.max_sweeps = max_sweeps; a.sweep_begin = run.sweep_begin; a.budget = kDagBudget; a.run_id = e->run_id;
         a.gen_base = e->dag_gen_base;
         a.timeout_ticks = 5000000ull;  // one wait: 50 ms of the 100 MHz clock
-        a.sync = e->dag_img.sync; a.host_ctl = e->h_ctl_dev; a.host_abort = e->h_abort_dev;
+        a.sync = e->dag_img.sync; a.host_ctl = e->h_ctl.dev(); a.host_abort = e->h_abort.dev();
         a.n = dp.n; a.E = dp.E; a.n_blocks = dp.blocks;
         a.tiles = e->dag_img.tiles; a.slot_ptr = e->dag_img.slotptr; a.cnode = e->dag_img.cnode; a.pitem = e->dag_img.pitem; a.oedge = e->dag_img.oedge;
         a.cpt_img = e->dag_img.cpt; a.npi_init = e->dag_img.init; a.state = e->dag_img.state; a.frz = e->dag_img.frz; a.frz_mark = e->dag_mark;
@@ -488,8 +485,7 @@ int bn_eng::run_device_impl(bn_engine* e, double eps, int32_t max_sweeps, int32_
         if (rc != BN_OK) return rc;
     }
     e->beliefs_on_host_only = false;  // (bn_bp_run_view sets it again when its kernels wrote to the host buffer)
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if (max_sweeps < 0) return fail(BN_ERR_ARG, "max_sweeps < 0");
     if (e->plan.nranks > 1 && !e->comm && !(e->shard_flow_ok && e->multisweep != 0))
         return fail(BN_ERR_COMM, "sharded engine: call bn_comm_init (RCCL exchange) or bn_peer_import (in-kernel exchange) before running");

@@ -144,15 +144,15 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
         int rc;
         if ((rc = reupload(e->d_cpt, p.cpt_striped, size_t(p.cpt_doubles), s, "tile image"))) return rc;
         if (e->small_ok) {
-            if ((rc = reupload(e->d_s_cpt, e->small.ent_cpt, e->small.ent_cpt.size(), s, "entry table"))) return rc;
-            if ((rc = reupload(e->d_s_init, e->small.npi_init, e->small.npi_init.size(), s, "initial pi"))) return rc;
+            if ((rc = reupload(e->small_img.ent_cpt, e->small.ent_cpt, e->small.ent_cpt.size(), s, "entry table"))) return rc;
+            if ((rc = reupload(e->small_img.npi_init, e->small.npi_init, e->small.npi_init.size(), s, "initial pi"))) return rc;
         }
         if (e->mid_ok) {
             MidTables t;
             build_mid_tables(e->mid, p, t);
-            if ((rc = reupload(e->d_m_cpt, t.ent_cpt, t.ent_cpt.size(), s, "entry tables"))) return rc;
+            if ((rc = reupload(e->mid_img.ent_cpt, t.ent_cpt, t.ent_cpt.size(), s, "entry tables"))) return rc;
             HIPCHK(hipStreamSynchronize(s));   // `t` is a local
-            if ((rc = reupload(e->d_m_init, e->mid.parts[0].npi_init, e->mid.parts[0].npi_init.size(), s, "initial pi"))) return rc;
+            if ((rc = reupload(e->mid_img.npi_init, e->mid.parts[0].npi_init, e->mid.parts[0].npi_init.size(), s, "initial pi"))) return rc;
         }
         if (e->dag_ready) {
             if ((rc = reupload(e->dag_img.cpt, e->dag.cpt_img, e->dag.cpt_img.size(), s, "register image"))) return rc;
@@ -229,8 +229,7 @@ extern "C" int bn_layout_class(bn_engine* e, int32_t cls, int32_t* kv, int32_t* 
 extern "C" int bn_lw_run(bn_engine* e, int32_t ne, const int32_t* ev_node, const int32_t* ev_state,
                          uint64_t sample_begin, uint64_t n_samples, uint64_t seed, double* hist_out) {
     if (!e || !hist_out) return fail(BN_ERR_ARG, "null argument");
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if (ne < 0 || (ne > 0 && (!ev_node || !ev_state))) return fail(BN_ERR_ARG, "bad evidence arguments");
     ON_DEVICE(e);
     std::string err;
@@ -244,8 +243,7 @@ extern "C" int bn_lw_run(bn_engine* e, int32_t ne, const int32_t* ev_node, const
 extern "C" int bn_lw_run_allreduce(bn_engine* e, int32_t ne, const int32_t* ev_node, const int32_t* ev_state,
                                    uint64_t sample_begin, uint64_t n_samples_total, uint64_t seed, double* hist_out) {
     if (!e || !hist_out) return fail(BN_ERR_ARG, "null argument");
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if (ne < 0 || (ne > 0 && (!ev_node || !ev_state))) return fail(BN_ERR_ARG, "bad evidence arguments");
     if (!e->comm) return fail(BN_ERR_COMM, "call bn_comm_init first");
     ON_DEVICE(e);
@@ -267,8 +265,7 @@ extern "C" int bn_rs_run(bn_engine* e, int32_t ne, const int32_t* ev_node, const
                          uint64_t sample_begin, uint64_t n_accept, uint64_t max_draw, uint64_t seed, double* counts_out,
                          uint64_t* drawn_out, uint64_t* accepted_out) {
     if (!e || !counts_out) return fail(BN_ERR_ARG, "null argument");
-    if (e->host_only) return fail(BN_ERR_STATE, "engine was created with BN_DEVICE_HOST_ONLY: no GPU, no compute");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_STATE)) return rc;
     if (ne < 0 || (ne > 0 && (!ev_node || !ev_state))) return fail(BN_ERR_ARG, "bad condition arguments");
     if (max_draw == 0) return fail(BN_ERR_ARG, "max_draw must be > 0 (the reference loops forever on impossible evidence)");
     ON_DEVICE(e);

@@ -48,7 +48,7 @@ int check_pair(const bn_engine* e, const bn_info_table* t) {
     if (!e || !t) return fail(BN_ERR_ARG, "null argument");
     if (e->host_only) return fail(BN_ERR_NO_DEVICE, "host-only engine (BN_DEVICE_HOST_ONLY): scoring runs on the device");
     if (e->plan.nranks > 1) return fail(BN_ERR_STATE, "sharded engine: a shard holds only its own nodes' tables (score on an unsharded engine)");
-    if (e->poisoned) return fail(BN_ERR_STATE, "engine unusable: bn_reload_cpt failed while uploading (destroy it and create a new one)");
+    if (int rc = refuse_unusable(e, BN_ERR_NO_DEVICE)) return rc;   // (an engine without a device was refused above, in this call's own words)
     if (t->n != e->plan.n)
         return fail(BN_ERR_ARG, "the table has " + std::to_string(t->n) + " columns, the network " + std::to_string(e->plan.n) + " nodes");
     for (int32_t v = 0; v < t->n; ++v)

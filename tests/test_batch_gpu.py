@@ -190,3 +190,49 @@ def test_batch_keeps_single_query_bits_where_the_dense_layout_would_not(bnlib, o
                 assert np.array_equal(out["beliefs"][q], r["beliefs"]), (seed, q, float(np.abs(out["beliefs"][q] - r["beliefs"]).max()))
                 assert np.abs(r["beliefs"] - o["beliefs"]).max() < 1e-12
     assert refused >= 1   # (at least one of these networks is of the kind the rule is for)
+
+
+def _every_call(eng, evs):
+    """The three calls that bring their evidence sets with them, and bn_bp_run_batch as the C ABI has it (the marginals written
+    straight into the engine's mapped host buffer): everything each of them returns."""
+    import ctypes
+    from bayesiannetwork_amd import _lib
+    from bayesiannetwork_amd.engine import _p
+    B = len(evs)
+    out = {"bp": eng.bp_run_batch(evs, 1e-6, 200), "mpe": eng.mpe_run_batch(evs, 1e-6, 200), "jt": eng.jt_run_batch(evs)}
+    ne, node, off, val = eng._pack_sets(evs)
+    bel, sweeps, res = np.empty((B, int(eng.model.k.sum()))), np.zeros(B, dtype=np.int32), np.zeros(B)
+    _lib.check(_lib.lib().bn_bp_run_batch(eng._h, B, _p(ne, ctypes.c_int32), _p(node, ctypes.c_int32), _p(off, ctypes.c_int32), _p(val, ctypes.c_double),
+                                          1e-6, 200, _p(bel, ctypes.c_double), _p(sweeps, ctypes.c_int32), _p(res, ctypes.c_double)))
+    out["bp_direct"] = {"beliefs": bel, "sweeps": sweeps, "residual": res}
+    return out
+
+
+def test_staging_blocks_grow_and_shrink_on_one_engine(Engine):
+    """One engine, batches of growing and shrinking size on the ALARM-shaped network: 1 set; 8 sets without evidence (the batch's
+    buffers for 8 sets, a staging block of the 4096-byte floor); 8 sets with a positive likelihood vector on EVERY node (about 9 KB:
+    every mapped staging block -- sum-product's, max-product's, the junction tree's -- is allocated anew, and the device has to read
+    the new block, not an address kept from the old one); 1 set again.  Every result has the bits a fresh engine returns for that
+    batch alone."""
+    import os
+    from bayesiannetwork_amd.dsc import load_dsc
+    from bayesiannetwork_amd import Evidence
+    m, _ = load_dsc(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "alarm_shaped.dsc"))
+    rng = np.random.default_rng(17)
+    soft = [Evidence.from_dict(m, {v: rng.uniform(0.05, 1.0, int(m.k[v])) for v in range(m.n)}) for _ in range(8)]
+    one = [Evidence.from_dict(m, {3: 1, 20: rng.uniform(0.1, 1.0, int(m.k[20]))})]
+    batches = [one, [None] * 8, soft, one]
+    staged = sum(4 * ev.ne + 4 * (ev.ne + 1) + 8 * ev.val.size for ev in soft)
+    assert staged > 2 * 4096, "the case should outgrow a staging block of the floor size"
+
+    def same(a, b):
+        return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+    with Engine(m) as eng:
+        for step, evs in enumerate(batches):
+            got = _every_call(eng, evs)
+            with Engine(m) as fresh:
+                want = _every_call(fresh, evs)
+            for call, res in want.items():
+                for key, w in res.items():
+                    assert same(np.asarray(got[call][key]), np.asarray(w)), (step, call, key)
