@@ -44,7 +44,8 @@ namespace bnmi {
 
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-// Diagnostic builds (-DBN_TILE_CLOCK): lane 0 of every wave stamps the phases of ONE iteration (the sixth) of the run
+// Diagnostic builds (-DBN_TILE_CLOCK): lane 0 of every wave stamps the phases of ONE iteration (the sixth) of the run (a block's
+// collecting wave also 2 "every block's granule seen" and 9 "verdict written": wait_verdict)
 #ifdef BN_TILE_CLOCK
 #define RSTAMP(k, iter, lane_, wave_)                                                              \
     do {                                                                                           \
@@ -52,7 +53,7 @@ namespace bnmi {
     } while (0)
 // ... and the fixed cost of the RUN, per wave (scripts/experiments/resident_clock.py): 0 kernel entry, 1 CPT loads issued,
 // 2 CPT resident (registers waited for, LDS part staged), 3 granules of the launch's first sweep published, 4 verdict of the
-// last sweep known, 5 finalize's last store issued
+// last sweep known, 5 finalize's last store issued; 6 is no time: the recorder's check of its re-read (ResidualRecorder)
 constexpr int kRunClockStamps = 8;
 static __device__ unsigned long long g_run_clock[kTileClockTiles][kRunClockStamps];
 #define RUNSTAMP(k, lane_, wave_)                                                                   \
@@ -132,11 +133,14 @@ struct BlockShared {
     unsigned long long slot[kResidentMaxSets][kResidentWaves];  // per-set, per-wave residual bit patterns
     int verdict[kResidentMaxSets];                              // of a set's last barrier: kGoOn / kConverged / kCapped / kAbort
     unsigned long long t_arrive;                                // direct form: 100 MHz clock when this block published its granules
-    int skew_ticks;                                             // ... and how long after this block the LAST block arrived in the previous iteration
+    int block_reports;                                          // this block's first wave records the residuals and reports the run (set once, at kernel entry)
     // several sets per launch: the block's waves are not held together by block barriers (arrive_batch / wait_verdict_batch)
     int arrived[kResidentMaxSets];                              // waves that have finished the set's sweep in hand (the last one publishes)
     int poll_it[kResidentMaxSets];                              // the last iteration for whose barrier a wave of the block has taken the polling on
     int ver[kResidentMaxSets];                                  // the last iteration whose verdict is out, with the verdict: iteration << 2 | verdict
+    // direct form again (behind the fields every form shares): how long after this block the blocks of the collecting wave's lane l
+    // arrived in the previous iteration -- their maximum, the skew, times the wave's first poll of the next barrier
+    int late[kWave];
 };
 enum : int { kGoOn = 0, kConverged = 1, kCapped = 2, kAbort = 3 };
 
@@ -300,12 +304,18 @@ __device__ __forceinline__ bool sweep_granules(const unsigned long long* tbl, in
     return mine;
 }
 
+// Direct form: whether the launch has a wave that records the residuals and reports the run (ResidualRecorder below): the last block
+// that carries a tile has a wave without one (a.waves is 2, 4 or 8).  On the 316 x 316 grid: 1 561 tiles, seven such waves.
+__device__ __forceinline__ bool has_recorder(const ResidentArgs& a) {
+    return a.direct != 0 && a.n_tile_blocks > 1 && (a.b.n_tiles & (a.waves - 1)) != 0;
+}
+
 // Second half: the verdict of iteration `it` of `set` once every block has arrived.
 __device__ __forceinline__ int wait_verdict(const ResidentArgs& a, BlockShared& sh, int set, int it) {
     if (a.direct != 0 && a.n_tile_blocks > 1) {
         // Direct form (one evidence set): the first wave of EVERY tile block sweeps all blocks' granules itself -- lane l those of
-        // blocks l, l + 64, ... -- reduces the residual and takes the (same) decision: one hand-off (granule store -> the other
-        // blocks' poll) instead of two (granule -> service block -> verdict word -> poll).
+        // blocks l, l + 64, ... -- and takes the (same) decision: one hand-off (granule store -> the other blocks' poll) instead of
+        // two (granule -> service block -> verdict word -> poll).
         if (threadIdx.x < kWave) {
             int lane = int(threadIdx.x);
             // opaque to the optimiser: otherwise the per-lane granule addresses are hoisted out of the sweep loop as loop invariants
@@ -320,21 +330,41 @@ __device__ __forceinline__ int wait_verdict(const ResidentArgs& a, BlockShared& 
             const unsigned long long t_arr = sh.t_arrive;
             const unsigned own16 = unsigned(t_arr) & 0xffffu;
             if (a.first_poll_delay >= 0) {   // (negative: poll from this block's own arrival on)
-                const unsigned long long first_at = t_arr + (unsigned long long)(sh.skew_ticks + a.first_poll_delay);
+                // The skew: the largest of the lanes' values of the previous barrier, capped at 400 ticks.  Reduced HERE, inside the wait
+                // it sizes (the margin alone is 300 ns), not behind the verdict, where the block's other waves and the chip would wait
+                // for it; and from votes on its bits, most significant first: scalar work, no LDS-crossbar stage.
+                const int prev = sh.late[lane];
+                int skew = 0;
+                if (__any(prev >= 400)) skew = 400;
+                else {
+#pragma unroll
+                    for (int bit = 256; bit >= 1; bit >>= 1)
+                        if (__any(prev >= (skew | bit))) skew |= bit;
+                }
+                const unsigned long long first_at = t_arr + (unsigned long long)(skew + a.first_poll_delay);
                 while (wall_clock64() < first_at) __builtin_amdgcn_s_sleep(1);
             }
             int late = 0;
             const bool ok = poll_until(a, [&] { return __all(sweep_granules(tbl, lane, nb, gen, m, own16, &late)) != 0; });
-            m = wave_umax(m);
-            {
-                int mx = late;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(mx, off, kWave); mx = o > mx ? o : mx; }
-                if (lane == 0) sh.skew_ticks = ok ? (mx < 400 ? mx : 400) : 0;
-            }
-            if (lane == 0) {
-                if (blockIdx.x == 0 && ok) __hip_atomic_store(&sy->res[it], m, RLX_AGENT);   // the residual history (read back by this block)
-                sh.verdict[set] = ok ? verdict_of(a, residual_of(m), a.sweep_begin + it + 1) : kAbort;
+            RSTAMP(2, it + 1, lane, 0);  // every block's granule seen (the barrier of iteration `it` is waited for in iteration it + 1)
+            // The verdict needs no reduction: every lane holds the maximum over ITS blocks, and "the maximum over all blocks is below
+            // eps" is "every lane's is" (residual_of is monotone, the patterns order like the doubles) -- one compare and a vote
+            // where a 64-lane maximum is six dependent LDS-crossbar stages, with the block's other waves in the barrier below and the
+            // chip behind its last block.  A lane without a block holds 0 and votes as DBL_MIN does: yes wherever any lane can; lane
+            // 0 always has a block, so eps <= DBL_MIN never converges, as in verdict_of, whose order of tests this is.
+            const bool below = residual_of(m) < a.eps;
+            const int n_done = a.sweep_begin + it + 1;
+            const int v = !ok ? kAbort : __all(below) ? kConverged : (a.max_sweeps > 0 && n_done >= a.max_sweeps) ? kCapped : kGoOn;
+            if (lane == 0) sh.verdict[set] = v;
+            RSTAMP(9, it + 1, lane, 0);  // verdict written
+            sh.late[lane] = ok ? late : 0;   // for this wave's next barrier: the skew times its first poll
+            // The residual's VALUE -- the history, the final residual -- is nobody's input before the run ends: a wave without a tile
+            // records it behind the barrier (ResidualRecorder) where the launch has one; else block 0 does, here, behind its verdict
+            // (block_reports is set in block 0 only; the blockIdx test in front of it spares every other block the LDS read, and
+            // the wait for it, between its verdict and its barrier)
+            if (blockIdx.x == 0 && ok && sh.block_reports != 0) {
+                m = wave_umax(m);
+                if (lane == 0) __hip_atomic_store(&sy->res[it], m, RLX_AGENT);   // (read back by this wave: resident_drive's report)
             }
         }
         __syncthreads();
@@ -419,14 +449,53 @@ __device__ __forceinline__ void resident_service(const ResidentArgs& a, int lane
     }
 }
 
+// What a wave does for the residual history between the barriers (resident_drive's `record`).
+// A wave with a tile records nothing; it reports the run -- block 0's first wave -- where the launch has no recorder (BlockShared::block_reports).
+struct NoRecorder {
+    __device__ __forceinline__ void operator()(const ResidentArgs&, int, int, int) const {}
+    __device__ __forceinline__ bool reports(const BlockShared& sh, int wave) const { return wave == 0 && sh.block_reports != 0; }
+};
+// The recorder (direct form; `on`: this is the first wave without a tile of the last block that carries one): behind the verdict barrier
+// of iteration `it` it reads that iteration's granules once more -- one round trip of sweep_granules, while the block's tiles compute
+// -- reduces them and stores the residual; at the end of the run it writes the history and the outcome from the words it stored
+// itself (as flow_service does).  The table it reads is written again in iteration it + 2 at the earliest, and no block can arrive
+// there before this block has arrived at it + 1 -- which takes this wave, through arrive()'s __syncthreads, behind its read.
+struct ResidualRecorder {
+    bool on;
+    __device__ __forceinline__ void operator()(const ResidentArgs& a, int set, int it, int lane) const {
+        if (!on) return;
+        ResidentSync* sy = a.sync + set;
+        const unsigned long long* tbl = (it & 1) ? &sy->blk_odd[0][0] : &sy->blk[0][0];
+        unsigned long long m = 0;
+        // Every block carries the generation (the verdict is out) and no slot has been written again (below).  The diagnostic build
+        // checks it: run-level stamp 6 of this wave takes the number of the first iteration whose re-read found another generation
+        // (scripts/experiments/resident_clock.py asserts that none did).  Not in the product: raising the launch's abort marks
+        // here, two more uses of the kernel arguments, cost <0, 4, 8> its 256th register.
+        const bool same = __all(sweep_granules(tbl, lane, a.n_tile_blocks, a.gen_base + unsigned(it) + 1u, m)) != 0;
+#ifdef BN_TILE_CLOCK
+        if (!same && lane == 0) {
+            unsigned long long& bad = g_run_clock[blockIdx.x * kResidentWaves + (threadIdx.x >> 6)][6];
+            if (bad == 0) bad = (unsigned long long)it + 1;
+        }
+#else
+        (void)same;
+#endif
+        m = wave_umax(m);
+        if (lane == 0) __hip_atomic_store(&sy->res[it], m, RLX_AGENT);
+        drain_stores();   // off every path: the word is in memory before this wave goes on (it reads it back in the report)
+    }
+    __device__ __forceinline__ bool reports(const BlockShared&, int) const { return on; }
+};
+
 // The launch's loop over iterations and evidence sets, shared by every tile kind.
 //   phase(set, s)          one sweep of this wave's tile for `set`; returns the wave's residual contribution
 //   finalize(set, n, done) the set stopped after n sweeps (done = kConverged / kCapped) or the launch's budget
 //                          ran out (done = 0): node vectors to memory where needed, beliefs when done
+//   record                 what this wave does for the residual history (the waves with a tile: NoRecorder)
 // Returns false when a bounded wait gave up.
-template <bool BATCH, class Phase, class Finalize>
+template <bool BATCH, class Phase, class Finalize, class Record = NoRecorder>
 __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShared& sh, int lane, int wave, Phase&& phase,
-                                               Finalize&& finalize) {
+                                               Finalize&& finalize, Record record = Record()) {
     unsigned active = BATCH ? a.set_mask : 1u;
     const int n_sets = BATCH ? a.n_sets : 1;  // one set: everything about sets folds away at compile time
     for (int it = 0; it <= a.budget; ++it) {  // the pass it == budget only collects verdicts
@@ -439,6 +508,7 @@ __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShare
                 if (BATCH && a.direct == 0) v = wait_verdict_batch(a, sh, set, it - 1, lane);
                 else v = wait_verdict(a, sh, set, it - 1);
                 if (v == kAbort) return false;
+                record(a, set, it - 1, lane);
             }
             RSTAMP(1, it, lane, wave);  // verdict of the previous iteration known
             if (v != kGoOn || it == a.budget) {
@@ -446,7 +516,7 @@ __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShare
                 RUNSTAMP(4, lane, wave);  // verdict of the last sweep known
                 finalize(set, s, done, true);
                 RUNSTAMP(5, lane, wave);  // finalize's last store issued
-                if (blockIdx.x == 0 && wave == 0) {  // report: residual history (final since each barrier), outcome
+                if (record.reports(sh, wave)) {  // report: residual history (final since each barrier), outcome
                     const ResidentSync* sy = a.sync + set;
                     double* hist = a.b.res_hist + int64_t(set) * a.res_hist_stride;
                     int q0 = lane;
@@ -476,10 +546,12 @@ __device__ __forceinline__ bool resident_drive(const ResidentArgs& a, BlockShare
     return true;
 }
 
-// A wave without a tile: takes part in the barriers, contributes nothing.
+// A wave without a tile: takes part in the barriers, contributes nothing to the sweep.  The first of them behind the last tile is the
+// launch's recorder where that tile's block is not full (has_recorder): the recorder's code is in this instantiation only.
 template <bool BATCH>
-__device__ __forceinline__ bool resident_idle(const ResidentArgs& a, BlockShared& sh, int lane, int wave) {
-    return resident_drive<BATCH>(a, sh, lane, wave, [](int, int) { return 0.0; }, [](int, int, int, bool) {});
+__device__ __forceinline__ bool resident_idle(const ResidentArgs& a, BlockShared& sh, int lane, int wave, int tile) {
+    const ResidualRecorder record{!BATCH && has_recorder(a) && tile == a.b.n_tiles};
+    return resident_drive<BATCH>(a, sh, lane, wave, [](int, int) { return 0.0; }, [](int, int, int, bool) {}, record);
 }
 
 // ---- the dataflow form: no grid barrier (single evidence set, more than one tile block) -----------------------
@@ -1246,7 +1318,15 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
     const BpBuffers& b = a.b;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x == 0) { sh.t_arrive = 0; sh.skew_ticks = 0; }
+    if (threadIdx.x == 0) {
+        sh.t_arrive = 0;
+        // who reports the run is decided once, here: the tile code is inlined once per tile shape, and every use of a kernel argument
+        // there counts (has_recorder in resident_drive's report cost <0, 4, 8> its 256th register)
+        sh.block_reports = (!FLOW && blockIdx.x == 0 && !has_recorder(a)) ? 1 : 0;
+    }
+    if constexpr (!FLOW) {
+        if (threadIdx.x < kWave) sh.late[threadIdx.x] = 0;   // (written and read by the block's first wave only)
+    }
     if constexpr (BATCH) {
         if (threadIdx.x < kResidentMaxSets) { sh.arrived[threadIdx.x] = 0; sh.poll_it[threadIdx.x] = -1; sh.ver[threadIdx.x] = -1; }
         __syncthreads();
@@ -1288,7 +1368,7 @@ __global__ __launch_bounds__(WMAX * kWave, WMAX == kResidentWaves ? 2 : 1) void 
     bool ok;
     if (tile >= b.n_tiles) {
         if constexpr (FLOW) return;  // nobody waits for a wave without a tile
-        else ok = resident_idle<BATCH>(a, sh, lane, wave);
+        else ok = resident_idle<BATCH>(a, sh, lane, wave, tile);
     } else {
         const TileDesc td = b.tiles[tile];
         double2_t* lds = cpt_lds_all[wave];

@@ -2,7 +2,8 @@
 # first sweep, last verdict, finalize), every wave: needs the diagnostic library
 #   (cd build/dbg_csrc && make EXTRA=-DBN_TILE_CLOCK OUT=../libbn_dbg.so)   and   BN_MI355X_LIB=build/libbn_dbg.so
 # Grid-barrier form (second argument 0): every phase again by half of the block -- waves 0-3 and their SIMD partners 4-7 -- with the
-# gap between the halves at "sweep issued" (EXPERIMENTS R21; EXTRA="-DBN_TILE_CLOCK -DBN_RES_PRIO=n" stamps another priority schedule)
+# gap between the halves at "sweep issued" (EXPERIMENTS R21; EXTRA="-DBN_TILE_CLOCK -DBN_RES_PRIO=n" stamps another priority schedule),
+# and the collecting wave of every block: poll returned -> verdict written -> block released (EXPERIMENTS R22)
 import ctypes
 import os
 import sys
@@ -71,6 +72,17 @@ with Engine(g) as e:
         print(f"    {'sweep issued since block release':34s} " + "  | ".join(
             f"{np.median(since[m]):7.0f} {np.percentile(since[m], 90):7.0f} {since[m].max():7.0f}" for _, m in halves))
         print(f"  gap between the halves' medians at 'sweep issued' (waves 4-7 minus waves 0-3): {med[1] - med[0]:.0f} ns")
+        # the collecting wave (wave 0 of every tile block, direct form): stamps 2 "every block's granule seen" and 9 "verdict written";
+        # what stands between them is on every block's path, and the block's other waves are released behind the second (EXPERIMENTS R22)
+        col = (wave == 0) & (st[:, 2] != 0) & (st[:, 9] != 0)
+        if col.any():
+            print(f"  collecting waves ({col.sum()}), ns: median / p90 / max")
+            for nm, i, j in (("start -> poll returned", 0, 2), ("poll returned -> verdict written", 2, 9), ("verdict written -> released", 9, 1)):
+                v = (st[col, j] - st[col, i]) * 10
+                print(f"    {nm:34s} {np.median(v):7.0f} {np.percentile(v, 90):7.0f} {v.max():7.0f}")
+            seen_last = st[col, 2].max()
+            rel = (st[tiled, 1] - seen_last) * 10
+            print(f"    last collector's poll returned -> a tile wave knows the verdict: {np.median(rel):.0f} median, {rel.max():.0f} max")
         comp = (st[:, 3] - st[:, 1]) * 10
         print("  compute (verdict -> sweep issued) by wave number, median ns:", " ".join(f"{np.median(comp[tiled & (wave == w)]):.0f}" for w in range(8)))
         slowest = np.argmax(np.where(tiled, comp, -1))
@@ -91,6 +103,7 @@ with Engine(g) as e:
     run = np.zeros((n, 8), dtype=np.uint64)
     assert L.bn_debug_run_clock_resident(run.ctypes.data_as(ctypes.c_void_p), n) == 0
     rs = run[run[:, 0] != 0].astype(np.int64)
+    assert (run[:, 6] == 0).all(), f"the recorder's re-read found a granule of another generation in iteration {int(run[:, 6].max()) - 1}"
     e0 = rs[:, 0].min()
     rows_ = [("entry -> CPT loads issued", rs[:, 1] - rs[:, 0]), ("entry -> CPT resident", rs[:, 2] - rs[:, 0]),
              ("CPT resident -> sweep 0 published", rs[:, 3] - rs[:, 2]), ("entry -> sweep 0 published", rs[:, 3] - rs[:, 0]),
