@@ -116,6 +116,8 @@ SYMBOLS = [
                                  f64p, ctypes.c_int32]),
     ("bn_jt_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, f64p, f64p, f64p]),
     ("bn_jt_run_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, f64p, f64p, f64p]),
+    ("bn_jt_mpe_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, f64p, f64p, i32p, f64p]),
+    ("bn_jt_mpe_run_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, f64p, f64p, i32p, f64p]),
     ("bn_jt_scales", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
     ("bn_jt_plan_dims", ctypes.c_int, [ctypes.c_void_p, i64p]),
     ("bn_jt_plan_dump", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]),

@@ -229,11 +229,13 @@ struct JtState {
     DeviceBuf<int32_t> d_ev_slot;       // [ev_slots][n]
     int64_t ev_slots = 0;
     DeviceBuf<double> d_beliefs, d_scales;   // [cap_sets][N], [cap_sets][nc]
+    DeviceBuf<int32_t> d_states;        // [cap_sets][n]: the assignment a max run decodes (bn_jt_mpe_run)
     int32_t cap_sets = 0;
     MappedBuf<char> h_ev;               // the staging block of the call's evidence (bn_batch_stage.hpp), mapped: read in place
     // the last call
     bool have_run = false;
     int last_form = 0;
+    int last_kind = 0;                  // JtKind: 1 a sum run (bn_jt_run*), 2 a max run (bn_jt_mpe_run*)
     int32_t n_sets = 0, last_launches = 0;
     int64_t last_kernel_ns = 0;         // option "timing": HIP events around the run's launches
     std::vector<double> scales;         // [n_sets][nc]

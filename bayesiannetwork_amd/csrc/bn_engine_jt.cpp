@@ -1,8 +1,8 @@
-// bn_engine_jt.cpp -- exact inference: the bn_jt_* entry points over the junction-tree kernels (bn_jt.hip; the rules of the
-// arithmetic: bn_jt.hpp; the planner: bn_jt_plan.hpp).  The plan is built at the first call that asks for it -- bn_get_info
-// "jt_eligible", bn_jt_plan_dims / _dump, a run -- also on engines without a device; tables, base potentials, scratch and outputs
-// are the JtState's own and allocated at the first run: a junction-tree run reads the engine's model and touches nothing the
-// bn_bp_* / bn_mpe_* / bn_em_* calls use.
+// bn_engine_jt.cpp -- exact inference: the bn_jt_* entry points (marginals: bn_jt_run*; exact MPE: bn_jt_mpe_run*) over the
+// junction-tree kernels (bn_jt.hip; the rules of the arithmetic: bn_jt.hpp; the planner: bn_jt_plan.hpp).  The plan is built at
+// the first call that asks for it -- bn_get_info "jt_eligible", bn_jt_plan_dims / _dump, a run -- also on engines without a
+// device; tables, base potentials, scratch and outputs are the JtState's own and allocated at the first run: a junction-tree run
+// reads the engine's model and touches nothing the bn_bp_* / bn_mpe_* / bn_em_* calls use.
 #include <cmath>
 
 #include "bn_engine_internal.hpp"
@@ -67,10 +67,13 @@ int ensure_device(bn_engine* e) {
     return BN_OK;
 }
 
-int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t* ev_off, const double* ev_val,
-                double* beliefs_out, double* log_evidence_out) {
+// a sum run (kJtSum: beliefs, log P(e)) or a max run (kJtMax: max-marginals, the decoded states, log max_x P(x, e)): the same
+// checks, buffers and launches, the kernel apart
+int jt_run_impl(bn_engine* e, int kind, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t* ev_off, const double* ev_val,
+                double* beliefs_out, int32_t* states_out, double* log_evidence_out) {
     if (!e) return fail(BN_ERR_ARG, "null engine");
-    if (!beliefs_out) return fail(BN_ERR_ARG, "null beliefs_out");
+    if (!beliefs_out) return fail(BN_ERR_ARG, kind == kJtMax ? "null max_marginals_out" : "null beliefs_out");
+    if (kind == kJtMax && !states_out) return fail(BN_ERR_ARG, "null states_out");
     if (n_sets < 1 || n_sets > BN_JT_MAX_BATCH_SETS) return fail(BN_ERR_ARG, "n_sets must be in 1.." + std::to_string(BN_JT_MAX_BATCH_SETS));
     if (!ne) return fail(BN_ERR_ARG, "null ne");
     bn_stage::BatchLayout lay;
@@ -88,7 +91,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     ON_DEVICE(e);
     j.have_run = false;
     if (int rc = ensure_device(e)) return rc;
-    const size_t N = size_t(P.N), nc = size_t(P.nc);
+    const size_t N = size_t(P.N), nc = size_t(P.nc), n = size_t(P.n);
     const int32_t per_launch = form == 1 ? n_sets : int32_t(std::min<int64_t>(n_sets, std::max<int64_t>(1, j.scratch_cells / P.state_cells)));
     int r;
     if (form == 2 && per_launch > j.scratch_slots) {
@@ -105,6 +108,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
         j.cap_sets = 0;
         if ((r = dalloc(j.d_beliefs, size_t(n_sets) * N))) return r;
         if ((r = dalloc(j.d_scales, size_t(n_sets) * nc))) return r;
+        if ((r = dalloc(j.d_states, size_t(n_sets) * n))) return r;
         j.cap_sets = n_sets;
     }
     HIPCHK(j.h_ev.reserve(lay.bytes));
@@ -121,6 +125,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     a.ev_val = reinterpret_cast<const double*>(j.h_ev.dev() + lay.b_val);
     a.ev_meta = lay.meta(j.h_ev.dev());
     a.ev_slot = j.d_ev_slot; a.scratch = j.d_scratch; a.beliefs = j.d_beliefs; a.scales = j.d_scales;
+    a.states = j.d_states;
     // the launches of a batch follow each other on the stream (they share the scratch slots) and the host waits once for all of them
     hipStream_t s = e->stream;
     if (e->timing) {   // option "timing": HIP events around the launches (bn_get_info "jt_last_kernel_ns")
@@ -131,13 +136,16 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
     int32_t launches = 0;
     for (int32_t first = 0; first < n_sets && rc == BN_OK; first += per_launch, ++launches) {
         a.set_base = first;
-        if (int code = launch_jt(a, form, std::min(per_launch, n_sets - first), s))
+        if (int code = launch_jt(a, form, kind, std::min(per_launch, n_sets - first), s))
             rc = fail(BN_ERR_HIP, std::string("jt launch failed: ") + hipGetErrorString(hipError_t(code)));
     }
     if (e->timing && rc == BN_OK && hipEventRecord(e->events[1], s) != hipSuccess) rc = fail(BN_ERR_HIP, "hipEventRecord failed");
     j.scales.resize(size_t(n_sets) * nc);
     if (rc == BN_OK && hipMemcpyAsync(beliefs_out, j.d_beliefs, sizeof(double) * size_t(n_sets) * N, hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(BN_ERR_HIP, "copy of the beliefs failed");
+    if (rc == BN_OK && kind == kJtMax &&
+        hipMemcpyAsync(states_out, j.d_states, sizeof(int32_t) * size_t(n_sets) * n, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = fail(BN_ERR_HIP, "copy of the states failed");
     if (rc == BN_OK && hipMemcpyAsync(j.scales.data(), j.d_scales, sizeof(double) * size_t(n_sets) * nc, hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(BN_ERR_HIP, "copy of the scales failed");
     const hipError_t drained = hipStreamSynchronize(s);   // (also after a failed launch: what is on the stream writes into the buffers)
@@ -149,7 +157,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
         HIPCHK(hipEventElapsedTime(&ms, e->events[0], e->events[1]));
         j.last_kernel_ns = int64_t(double(ms) * 1e6);
     }
-    // log P(e) = the scales' logarithms added in array order: -inf as soon as one factor is 0
+    // log P(e) (a max run: log max_x P(x, e)) = the scales' logarithms added in array order: -inf as soon as one factor is 0
     if (log_evidence_out)
         for (int32_t q = 0; q < n_sets; ++q) {
             double lg = 0.0;
@@ -158,6 +166,7 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
         }
     j.n_sets = n_sets;
     j.last_form = form;
+    j.last_kind = kind;
     j.last_launches = launches;
     j.have_run = true;
     return BN_OK;
@@ -167,12 +176,22 @@ int jt_run_impl(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* 
 
 extern "C" int bn_jt_run(bn_engine* e, int32_t ne, const int32_t* ev_node, const int32_t* ev_off, const double* ev_val, double* beliefs_out,
                          double* log_evidence_out) {
-    return jt_run_impl(e, 1, &ne, ev_node, ev_off, ev_val, beliefs_out, log_evidence_out);
+    return jt_run_impl(e, kJtSum, 1, &ne, ev_node, ev_off, ev_val, beliefs_out, nullptr, log_evidence_out);
 }
 
 extern "C" int bn_jt_run_batch(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t* ev_off, const double* ev_val,
                                double* beliefs_out, double* log_evidence_out) {
-    return jt_run_impl(e, n_sets, ne, ev_node, ev_off, ev_val, beliefs_out, log_evidence_out);
+    return jt_run_impl(e, kJtSum, n_sets, ne, ev_node, ev_off, ev_val, beliefs_out, nullptr, log_evidence_out);
+}
+
+extern "C" int bn_jt_mpe_run(bn_engine* e, int32_t ne, const int32_t* ev_node, const int32_t* ev_off, const double* ev_val,
+                             double* max_marginals_out, int32_t* states_out, double* log_p_out) {
+    return jt_run_impl(e, kJtMax, 1, &ne, ev_node, ev_off, ev_val, max_marginals_out, states_out, log_p_out);
+}
+
+extern "C" int bn_jt_mpe_run_batch(bn_engine* e, int32_t n_sets, const int32_t* ne, const int32_t* ev_node, const int32_t* ev_off,
+                                   const double* ev_val, double* max_marginals_out, int32_t* states_out, double* log_p_out) {
+    return jt_run_impl(e, kJtMax, n_sets, ne, ev_node, ev_off, ev_val, max_marginals_out, states_out, log_p_out);
 }
 
 extern "C" int bn_jt_scales(bn_engine* e, int32_t set, double* out, int32_t cap) {
@@ -241,6 +260,7 @@ int64_t bn_eng::jt_get_info(bn_engine* e, const char* name, bool* known) {
     *known = true;
     JtState& j = e->jt;
     if (std::strcmp(name, "jt_last_form") == 0) return j.have_run ? j.last_form : 0;
+    if (std::strcmp(name, "jt_last_kind") == 0) return j.have_run ? j.last_kind : 0;   // 1: a sum run, 2: a max run
     if (std::strcmp(name, "jt_last_launches") == 0) return j.have_run ? j.last_launches : 0;
     if (std::strcmp(name, "jt_scratch_cells") == 0) return j.scratch_cells;
     if (std::strcmp(name, "jt_last_kernel_ns") == 0) return j.have_run ? j.last_kernel_ns : 0;   // option "timing" 1: events around the launches

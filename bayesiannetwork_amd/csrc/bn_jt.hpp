@@ -19,6 +19,29 @@
 //   Read-out: u[x] = two-level sum of the home clique's entries with x_v = x, ascending entry index; belief = u[x] / (u[0] + u[1] +
 //     ... left to right from +0.0), no zero guard: P(e) = 0 gives NaN.
 //   Scales: [n_cliques] in clique id order; P(e) is their product (the host adds their std::log in that order).
+//
+// Exact MPE (bn_jt_mpe_run, jt_mpe_kernel): the same walk over the same tables with every sum replaced by a maximum, and a
+// top-down backtrack.  Restated by tests/jtmpe_refs.py; states, max-marginals and scales are equal bit for bit.
+//   Max fold of terms (bn_maxprod.hpp): acc = +0.0, then acc = x if acc < x else acc.  A NaN never replaces acc: the result is the
+//     largest term above +0.0, else +0.0, WHATEVER THE ORDER -- this pass has no stated order of its folds, so a long fold may be
+//     spread over lanes and reduced without changing a bit.
+//   Potentials: as above.
+//   Collect, deepest level first: raw separator entry = max fold of the clique's matching entries; s = max fold of the separator's
+//     entries (kept: the scale of the clique); the message is raw / s where s > 0, else raw; the parent's entries multiply their
+//     children's messages in, in ascending child-clique id.  A root's "separator" is the max fold of all its entries.
+//   Distribute, top level first: ratio = (max fold of the parent's matching entries) / message, exactly 0 where the message is 0;
+//     the child's entries are multiplied by their ratio.
+//   Scales: their product is max_x P(x, e); log_p = the sum of their std::log in clique order, -inf when a factor is 0.  (The
+//     divisors are constants of the set, so they factor out of every maximum as they factor out of every sum.)
+//   Max-marginals: u[x] = max fold of the home clique's entries with x_v = x; output u[x] / (u[0] + u[1] + ... left to right from
+//     +0.0), no zero guard -- bn_mpe_run's normalisation.
+//   Decode by backtracking, pick[c] an entry index of clique c: a root picks the lowest entry index of its largest entry
+//     (best = t[0]; t[i] > best takes i).  A child's separator entry is j = up_map[up_off + pick[parent]]; the child picks, among
+//     its entries that match j -- the terms c_base[sep_off + j] + c_res[cres_off + t], ascending -- the lowest entry index of the
+//     largest.  The child's entries are read AS THEY STAND AFTER COLLECT, before the clique's own distribute multiply: ties are not
+//     disturbed by the rounding of the ratio, and the pick of a level rides the phase that computes the level's ratios (it needs
+//     pick[parent] of the phase before only), so decoding adds no barrier.  states[v] = (pick[home[v]] / stride_v) % k_v.
+//     With P(e) = 0 the states are what the rule gives: meaningless, but pinned by the restatement.
 #ifndef BN_JT_HPP
 #define BN_JT_HPP
 #include <cstddef>
@@ -53,9 +76,12 @@ struct JtArgs {
     const int32_t* ev_meta;
     int32_t* ev_slot;               // [slots][n] scratch: where a node's evidence vector starts, -1: none
     double* scratch;                // form 2: [slots][state_cells]
-    double* beliefs;                // [sets][N]
+    double* beliefs;                // [sets][N]  (a max run: the max-marginals)
     double* scales;                 // [sets][nc]
+    int32_t* states;                // [sets][n]  a max run's decoded assignment; a sum run does not touch it
 };
+
+enum JtKind : int { kJtNone = 0, kJtSum = 1, kJtMax = 2 };   // bn_get_info "jt_last_kind"
 
 struct JtBaseArgs {
     int32_t pot_cells;
@@ -69,8 +95,8 @@ struct JtBaseArgs {
 };
 
 int launch_jt_base(const JtBaseArgs& a, void* stream);
-// form 1: state in LDS; form 2: in a.scratch.  One workgroup per set.
-int launch_jt(const JtArgs& a, int form, int n_sets, void* stream);
+// form 1: state in LDS; form 2: in a.scratch.  One workgroup per set.  kind: kJtSum (jt_kernel) or kJtMax (jt_mpe_kernel).
+int launch_jt(const JtArgs& a, int form, int kind, int n_sets, void* stream);
 
 }  // namespace bnmi
 

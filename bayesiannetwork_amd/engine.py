@@ -234,8 +234,37 @@ class Engine:
         _lib.check(_lib.lib().bn_jt_scales(self._h, -1, _p(scales, ctypes.c_double), scales.size))
         return {"beliefs": bel, "log_evidence": lg, "scales": scales}
 
+    def jt_mpe_run(self, evidence: Evidence | None = None):
+        """bn_jt_mpe_run: exact MPE by max-propagation with backtracking on the junction tree.  "states" (int32 [n], the most
+        probable joint assignment, evidence nodes included), "max_marginals" (node-major [sum k], normalised), "log_p"
+        (log max_x P(x, e)) and "scales" ([cliques], their product is max_x P(x, e)) out.  With P(e) = 0: log_p = -inf, NaN
+        max-marginals, and states without meaning."""
+        ev = evidence if evidence is not None else Evidence.none()
+        mm = np.empty(self._nbel, dtype=np.float64)
+        st = np.empty(self.model.n, dtype=np.int32)
+        lg = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().bn_jt_mpe_run(self._h, ev.ne, _p(ev.node, ctypes.c_int32), _p(ev.off, ctypes.c_int32), _p(ev.val, ctypes.c_double),
+                                            _p(mm, ctypes.c_double), _p(st, ctypes.c_int32), ctypes.byref(lg)))
+        return {"states": st, "max_marginals": mm, "log_p": lg.value, "scales": self.jt_scales(0)}
+
+    def jt_mpe_run_batch(self, evidences):
+        """bn_jt_mpe_run_batch: several evidence sets in one call; set q gets exactly what jt_mpe_run(evidences[q]) returns.
+        "states" [n_sets, n], "max_marginals" [n_sets, sum k], "log_p" [n_sets], "scales" [n_sets, cliques]."""
+        ne, node, off, val = self._pack_sets(evidences)
+        B = int(ne.size)
+        mm = np.empty((B, self._nbel), dtype=np.float64)
+        st = np.empty((B, self.model.n), dtype=np.int32)
+        lg = np.zeros(B, dtype=np.float64)
+        _lib.check(_lib.lib().bn_jt_mpe_run_batch(self._h, B, _p(ne, ctypes.c_int32), _p(node, ctypes.c_int32), _p(off, ctypes.c_int32),
+                                                  _p(val, ctypes.c_double), _p(mm, ctypes.c_double), _p(st, ctypes.c_int32),
+                                                  _p(lg, ctypes.c_double)))
+        scales = np.zeros((B, max(self.info("jt_cliques"), 1)), dtype=np.float64)
+        _lib.check(_lib.lib().bn_jt_scales(self._h, -1, _p(scales, ctypes.c_double), scales.size))
+        return {"states": st, "max_marginals": mm, "log_p": lg, "scales": scales}
+
     def jt_scales(self, set: int = 0) -> np.ndarray:
-        """The scale array of evidence set `set` of the last jt_run / jt_run_batch: their product is P(e)."""
+        """The scale array of evidence set `set` of the last junction-tree run of either kind: their product is P(e) after
+        jt_run / jt_run_batch, max_x P(x, e) after jt_mpe_run / jt_mpe_run_batch (info("jt_last_kind"): 1 / 2)."""
         nc = self.info("jt_cliques")
         out = np.zeros(max(nc, 1), dtype=np.float64)
         cnt = _lib.check(_lib.lib().bn_jt_scales(self._h, int(set), _p(out, ctypes.c_double), nc))
@@ -760,14 +789,21 @@ class JunctionTree:
 
     @property
     def log_evidence(self) -> float:
-        """log P(e) of the last call."""
-        return self.last["log_evidence"]
+        """log P(e) of the last call (after ``mpe``: log max_x P(x, e))."""
+        return self.last["log_evidence"] if "log_evidence" in self.last else self.last["log_p"]
 
     def run_batch(self, preconditions):
         """Several evidence sets in one call: a list of (marginals, log P(e)), entry q exactly what ``self(preconditions[q])``
         and ``self.log_evidence`` give."""
         self.last = self.engine.jt_run_batch([self._evidence(p) for p in preconditions])
         return [(_split(self.model, bel), float(lg)) for bel, lg in zip(self.last["beliefs"], self.last["log_evidence"])]
+
+    def mpe(self, precondition=None):
+        """(states, log probability): the most probable joint assignment given the evidence (int32 [n], evidence nodes included)
+        and log max_x P(x, e), by max-propagation with backtracking (Engine.jt_mpe_run) -- exact, also where assignments tie:
+        the decoded assignment attains the maximum.  ``self.last["max_marginals"]`` holds the max-marginals of the call."""
+        self.last = self.engine.jt_mpe_run(self._evidence(precondition))
+        return self.last["states"], self.last["log_p"]
 
 
 class LikelihoodWeighting:

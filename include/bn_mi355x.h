@@ -322,6 +322,48 @@ int bn_jt_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int32_t 
 int bn_jt_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const int32_t *ev_node, const int32_t *ev_off,
                     const double *ev_val, double *beliefs_out, double *log_evidence_out);
 int bn_jt_scales(bn_engine *eng, int32_t set, double *out, int32_t cap);
+
+/*
+ * Exact MPE: max-propagation with backtracking on the junction tree -- the pair of bn_jt_run as bn_mpe_run is the pair of
+ * bn_bp_run.  bn_mpe_run (max-product loopy BP) is exact on polytrees only and decodes node by node: where two joint assignments
+ * tie, the per-node argmaxes may combine into an assignment that is no maximiser (node 0 uniform, node 1 = "not node 0": both
+ * max-marginals are [0.5, 0.5], per-node decoding gives (0, 0), which has probability 0).  This call is exact on every network
+ * the junction tree takes, and decodes by backtracking: its assignment always attains the maximum it reports.
+ * Arguments, evidence (a LIKELIHOOD, hard or soft), their checks, the plan, the two forms, the options, the batch rules and the
+ * errors are those of bn_jt_run / bn_jt_run_batch: BN_ERR_ARG first; BN_ERR_STATE with the planner's reason on ineligible or
+ * sharded engines or a forced form that does not fit; BN_ERR_NO_DEVICE on BN_DEVICE_HOST_ONLY engines after both.
+ *   max_marginals_out : [sum k] (batch: [n_sets][sum k]) node-major, each node's vector normalised; P(e) = 0 gives NaN
+ *   states_out        : [n] (batch: [n_sets][n]): the most probable joint assignment x*, evidence nodes included.  With
+ *                       P(e) = 0 the states are what the rule below gives: defined, and meaningless
+ *   log_p_out         : one value (batch: [n_sets]), may be NULL: log max_x P(x, e) = the std::log of the scales added in
+ *                       clique order; -inf when a factor is 0
+ * The arithmetic, fp64 without contraction (tests/jtmpe_refs.py restates it: states, max-marginals and scales bit for bit):
+ *   max fold of terms: acc = +0.0, then acc = x if acc < x else acc -- a NaN never replaces acc, so the result is the largest term
+ *     above +0.0, else +0.0, whatever the order: this pass states no order of its folds;
+ *   potentials: as bn_jt_run;
+ *   collect, deepest level first: raw separator entry = max fold of the clique's matching entries; s = max fold of the
+ *     separator's entries (the clique's scale); message = raw / s where s > 0, else raw; the parent's entries multiply their
+ *     children's messages in, ascending child id; a root's scale = max fold of all its entries;
+ *   distribute, top level first: ratio = (max fold of the parent's matching entries) / message, exactly 0 where the message is
+ *     0; the child's entries are multiplied by it;
+ *   max-marginals: u[x] = max fold of the home clique's entries with x_v = x; output u[x] / (u[0] + u[1] + ... left to right
+ *     from +0.0), no zero guard (bn_mpe_run's normalisation);
+ *   decode: a root picks the lowest entry index of its largest entry (best = t[0]; t[i] > best takes i); a child picks, among
+ *     its entries that agree with its parent's pick on the separator, the lowest entry index of the largest one -- the child's
+ *     entries AS THEY STAND AFTER COLLECT, before its own distribute multiply, so that ties are not disturbed by the rounding of
+ *     a ratio; state of node v = its digit in the pick of its home clique.
+ * A limit: after distribute a clique's table carries the scales of the cliques on its path to the root, each a maximum below 1;
+ * on a tree more than about a thousand levels deep they underflow and the max-marginals of deep nodes are 0 / 0 = NaN.  The
+ * states and log_p are not affected: the picks read the tables as collect left them.
+ * bn_jt_scales reports the scales of the last bn_jt_* run of either kind (a max run: their product is max_x P(x, e)).
+ * bn_get_info "jt_last_kind": 0 none, 1 a sum run (bn_jt_run*), 2 a max run (bn_jt_mpe_run*); "jt_last_form", "jt_last_launches"
+ * and "jt_last_kernel_ns" are updated as for a sum run.
+ */
+int bn_jt_mpe_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int32_t *ev_off, const double *ev_val,
+                  double *max_marginals_out, int32_t *states_out, double *log_p_out);
+int bn_jt_mpe_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const int32_t *ev_node, const int32_t *ev_off,
+                        const double *ev_val, double *max_marginals_out, int32_t *states_out, double *log_p_out);
+
 int bn_jt_plan_dims(bn_engine *eng, int64_t *dims_out);
 int bn_jt_plan_dump(bn_engine *eng, int32_t *order, int32_t *parent, int32_t *level, int32_t *var_ptr, int32_t *vars, int32_t *sep_ptr,
                     int32_t *sep_vars, int32_t *cpt_clique, int32_t *home);
