@@ -333,7 +333,8 @@ def test_hot_kernels_do_not_spill(bnlib):
 def test_small_plan_emulated_equals_oracle(bnlib, oracle_mod):
     """The plan of the one-workgroup path (bn_small_plan.cpp), executed item by item on the CPU (tests/small_emulator.py),
     reproduces the oracle bit for bit -- beliefs, sweep count, residual history, final messages -- on networks with up to
-    four parents per node, mixed arities, hard and soft evidence.  (On the GPU: tests/test_small_gpu.py.)"""
+    four parents per node, mixed arities, hard and soft evidence.  (On the GPU: tests/test_small_gpu.py.  Five to eight parents per
+    node, this path and the several-workgroup one: tests/test_many_parents_refs.py, on the GPU tests/test_many_parents_gpu.py.)"""
     import os
     import small_emulator
     from bayesiannetwork_amd import Evidence, _lib, engine, synth

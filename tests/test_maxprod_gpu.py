@@ -79,9 +79,10 @@ def same_bits(got, want, eng=None, what=""):
         assert np.array_equal(pi, want["pi_msg"], equal_nan=True) and np.array_equal(lam, want["lambda_msg"], equal_nan=True), what
 
 
-def check_form(model, form, ev_names=("none", "hard10", "hard30", "soft", "zero")):
+def check_form(model, form, ev_names=("none", "hard10", "hard30", "soft", "zero"), evs=None):
+    """evs: {name: evidence} to take `ev_names` from instead of evidences(model)"""
     from bayesiannetwork_amd.engine import Engine
-    evs = evidences(model)
+    evs = evidences(model) if evs is None else evs
     with Engine(model, device=0) as eng:
         eng.set_option("mpe_form", form)
         assert eng.info("mpe_form") == form

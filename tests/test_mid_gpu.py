@@ -1,6 +1,7 @@
 """Mid-size networks (beyond one workgroup's LDS, not covered by the resident tiles): the items of bn_small.hip spread over
 several workgroups by node ranges, state in device memory, a grid barrier per iteration, one launch per run (csrc/bn_mid.hip,
-bn_bp_last_path == 4).  Same arithmetic order as the one-workgroup kernel: the oracle BIT FOR BIT, any parent count."""
+bn_bp_last_path == 4).  Same arithmetic order as the one-workgroup kernel: the oracle BIT FOR BIT, any parent count -- up to four
+per node in this file, five to eight in tests/test_many_parents_gpu.py."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,8 @@
 """Small networks (ALARM-sized: what the reference's users load): the whole run in ONE workgroup with the state in
 LDS (csrc/bn_small.hip, bn_bp_last_path == 3).  Sums and products keep the reference's order for any table size,
 so the bar is the oracle BIT FOR BIT -- marginals, sweep count, per-sweep maximum_difference, final messages -- also
-on networks with three and more parents per node, where the tile kernels only agree to rounding."""
+on networks with three and more parents per node, where the tile kernels only agree to rounding.  The networks here have at most
+four parents per node; five to eight (the entry routine's padded instantiations) are tests/test_many_parents_gpu.py."""
 import os
 
 import numpy as np
