@@ -4,7 +4,7 @@
 //
 //   em_small_kernel        one workgroup per pattern row.  Evidence from the row's bytes; the sum-product loop with the state in LDS,
 //                          bounded by the cap; then the epilogue on the state the run stopped in:
-//                            pass 1  entry items: the terms t' of pi(v) into staging (small_entry_any: the iteration's phase 1);
+//                            pass 1  entry items: the terms t' of pi(v) into staging (item_entry_any: the iteration's phase 1);
 //                            barrier
 //                            pass 2  accumulator items of pi(v): r[i] = the run's sum (small_run_sum), r[i] x lambda(v)[i] into the
 //                                    idle half of the pi(v) buffer, s = the vector's sum front to back (small_vector_sum), s stored
@@ -18,6 +18,7 @@
 //                          non-negative doubles order like the values), theta_new into the flat array and the two device images.
 #include "bn_em.hpp"
 #include "bn_small_dev.hpp"
+#include "bn_item_launch.hpp"
 
 namespace bnmi {
 
@@ -33,6 +34,10 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void em_small_kernel(EmSmal
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+    const SmallEntry* const it_ent = a.ent; const double* const it_cpt = a.ent_cpt; const uint32_t* const it_term = a.term;
+    const SmallSlot* const it_bslot = a.bslot; const SmallSlot* const it_cslot = a.cslot;
+    const int it_nt = nt, it_re = a.re, it_rb = a.rb, it_rc = a.rc;
+    constexpr bool it_mine = true;
 #include "bn_small_items.inc"
     // ---- tables and initial state (:33-73) into LDS; the evidence from the pattern's bytes
     for (int t = tid; t < a.TT; t += nt) L.term[t] = a.term[t];
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void em_small_kernel(EmSmal
     double* sbuf = L.npi + (fin ^ 1) * a.N;   // the idle half: r[i] x lambda(v)[i], then s
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r)   // t' at its place in pi(v)[i]'s run (the lambda-message terms beside it are not read)
-        if (r < a.re) small_entry_any<kTermsInRegs>(e_mm[r], L, L.pi + fin * a.M, nlam_fin, ent[r], ecpt[r], treg[r]);
+        if (r < a.re) item_entry_any<kTermsInRegs, false>(e_mm[r], L.stg, L.term, L.pi + fin * a.M, nlam_fin, ent[r], ecpt[r], treg[r], LdPlain{});
     __syncthreads();
     // (the items of passes 2 and 3 are read from the tables once more, round after round: the registers that held them through the
     // run are free again, and the epilogue runs once)
@@ -143,24 +148,12 @@ __global__ __launch_bounds__(256) void em_mstep_kernel(EmMstepArgs a) {
     if ((threadIdx.x & (kWave - 1)) == 0 && bits) atomicMax(a.delta_bits, bits);
 }
 
-int prepare_em_small() {
-    (void)hipGetLastError();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(em_small_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(em_small_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(em_small_kernel<kSmallMaxRounds>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    return e == hipSuccess ? 0 : int(e);
-}
+constexpr auto em_small_of = [](auto R) { return em_small_kernel<decltype(R)::value>; };
+
+int prepare_em_small() { return prepare_item_kernels(em_small_of); }
 
 int launch_em_small(const EmSmallArgs& a, int waves, size_t lds_bytes, int32_t chunk, void* stream) {
-    (void)hipGetLastError();  // drop any stale error of this thread
-    const dim3 grid(chunk), block(waves * kWave);
-    const int rounds = a.re > a.rb ? (a.re > a.rc ? a.re : a.rc) : (a.rb > a.rc ? a.rb : a.rc);
-    if (rounds <= 1) hipLaunchKernelGGL(em_small_kernel<1>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else if (rounds <= 2) hipLaunchKernelGGL(em_small_kernel<2>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(em_small_kernel<kSmallMaxRounds>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launch_item_kernel(item_rounds(a.re, a.rb, a.rc), em_small_of, dim3(chunk), dim3(waves * kWave), lds_bytes, stream, a);
 }
 
 int launch_em_accumulate(const EmAccArgs& a, void* stream) {

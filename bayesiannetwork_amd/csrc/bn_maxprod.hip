@@ -2,15 +2,22 @@
 // kernels (bn_small.hpp / bn_small_plan.cpp: entry, accumulator and product items).  The algorithm, the fold's NaN rule, the
 // state's tie rule and the cap: bn_maxprod.hpp.  Reference for everything but the fold: belief_propagation.hpp:33-158.
 //
-//   mpe_small_kernel   one workgroup runs the whole run with the state in LDS (the shape of bn_small.hip's kernel): phase 1
-//                      entry items -> staged terms; barrier; phase 2 accumulator items (running MAXIMUM of the run, eight
-//                      independent partial maxima), product items, residual; barrier; stop decision by every wave.
+//   mpe_small_kernel   one workgroup runs the whole run with the state in LDS (the shape of bn_small.hip's kernel, over the same
+//                      pieces of bn_small_dev.hpp and the same evidence prologue, bn_small_evidence.inc): phase 1 entry items ->
+//                      staged terms; barrier; phase 2 accumulator items (running MAXIMUM of the run, eight independent partial
+//                      maxima), product items, residual; barrier; stop decision by every wave.  The items and the iteration are
+//                      written out here, NOT bn_small_items.inc / bn_small_sweep.inc: on those texts the one-round kernel runs
+//                      the same instructions under other register names and its sweep of the ALARM-shaped network takes 11-14 ns
+//                      longer (measured), against a spread of 1-2 ns between processes.
 //   mpe_mid_*          one workgroup per MidPart, state in device memory, ONE LAUNCH PER SWEEP.  Nothing waits inside a kernel:
 //                      a sweep's launch reads buffer s & 1 and writes the other, leaves its workgroup's maximum_difference in a
-//                      word of its own, and the NEXT launch's workgroups reduce those words and decide.
+//                      word of its own, and the NEXT launch's workgroups reduce those words and decide.  Items, entry item, LDS
+//                      layout and normalisation are the ones bp_mid_kernel uses (bn_small_dev.hpp); the sweep's statements are
+//                      its own (plain loads: nothing it reads is written during its launch).
 #include "bn_maxprod.hpp"
 #include "bn_tiles.hpp"
 #include "bn_small_dev.hpp"
+#include "bn_item_launch.hpp"
 
 namespace bnmi {
 
@@ -19,7 +26,7 @@ namespace {
 // The running maximum of bn_maxprod.hpp, acc = (acc < x) ? x : acc, as ONE instruction.  v_max_f64 returns the other operand where one
 // is a quiet NaN and +0.0 for (+0.0, -0.0): with acc never NaN and never -0.0 (it starts at +0.0 and is only ever replaced by a larger
 // term) that is the rule exactly -- for every x that is not a SIGNALLING NaN, which the hardware would quiet and return.  A staged term
-// never is one: it is the result of a multiplication, or canonicalised where it is a bare table entry (mpe_entry).  (The rule spelt
+// never is one: it is the result of a multiplication, or canonicalised where it is a bare table entry (item_entry's CANON).  (The rule spelt
 // out in C++ compiles to a compare and two selects per term: three times the issue slots, and slower than the sum's chain of adds.)
 __device__ __forceinline__ double mpe_max(double acc, double x) {
     double r;
@@ -76,73 +83,6 @@ __device__ __forceinline__ int mpe_decode(const double* vec, int k) {
     return idx;
 }
 
-// One CPT entry: its term of pi(v) and of the lambda-message to every parent into their places of the staging array -- the
-// arithmetic and the product order of the sum-product kernels (bn_small.hip small_entry).  pi_cur / nlam_cur: LDS or memory.
-// REG: the entry's parent terms are in registers (they never change; kept there when they fit: one round of items, <= 4 parents).
-template <int MM, bool REG>
-__device__ __forceinline__ void mpe_entry(double* stg, const uint32_t* term, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
-                                          const uint32_t (&treg)[4]) {
-    if (((h.y >> 24) & 1u) == 0) return;
-    const int m = int((h.y >> 16) & 0xffu), tbase = int(h.y & 0xffffu);
-    const double li = nlam_cur[h.x & 0xffffu];
-    uint32_t tw[MM > 0 ? MM : 1];
-    double pj[MM > 0 ? MM : 1];
-#pragma unroll
-    for (int j = 0; j < MM; ++j) {
-        if (REG && MM <= 4) tw[j] = treg[j < 4 ? j : 0];
-        else tw[j] = j < m ? term[tbase + j] : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < MM; ++j) {
-        const double x = pi_cur[tw[j] & 0xffffu];
-        pj[j] = j < m ? x : 1.0;   // x * 1.0 == x
-    }
-    double v = MM == 0 ? __builtin_canonicalize(c) : c;   // (a bare table entry: quiet, like every product -- mpe_max)
-#pragma unroll
-    for (int j = 0; j < MM; ++j) v *= pj[j];
-    stg[h.x >> 16] = v;
-    const double lc = li * c;
-#pragma unroll
-    for (int jt = 0; jt < MM; ++jt) {
-        double w = lc;
-#pragma unroll
-        for (int j = 0; j < MM; ++j)
-            if (j != jt) w *= pj[j];
-        if (jt < m) stg[tw[jt] >> 16] = w;
-    }
-}
-template <bool REG>
-__device__ __forceinline__ void mpe_entry_any(int mm, double* stg, const uint32_t* term, const double* pi_cur, const double* nlam_cur, SmallEntry h,
-                                              double c, const uint32_t (&treg)[4]) {
-    switch (mm) {
-        case 0: return mpe_entry<0, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        case 1: return mpe_entry<1, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        case 2: return mpe_entry<2, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        case 3: return mpe_entry<3, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        case 4: return mpe_entry<4, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        case 5: case 6: return mpe_entry<6, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-        default: return mpe_entry<8, REG>(stg, term, pi_cur, nlam_cur, h, c, treg);
-    }
-}
-
-// Normalisation (:298-311) of the vector whose elements sit in adjacent lanes of this wave.  The un-normalised element goes to
-// buf[idx] (idx - at = the vector's first element), every lane adds the vector front to back and divides.
-__device__ __forceinline__ double mpe_normalize(double* buf, bool on, int idx, int k, int at, double val, int kmax) {
-    if (on) buf[idx] = val;
-    lds_fence();
-    const int vec = on ? idx - at : 0;
-    double sum = 0.0;
-    for (int r0 = 0; r0 < kmax; r0 += 4) {
-        double x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] = buf[vec + (r0 + q < k ? r0 + q : 0)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sum += r0 + q < k ? x[q] : 0.0;  // + 0.0 past the end: a sum started from +0.0 is never -0.0
-    }
-    lds_fence();
-    return val / sum;
-}
-
 // this thread's items of one round and what the wave needs to know of its lanes' items
 struct MpeItems {
     SmallEntry ent;
@@ -165,36 +105,6 @@ __device__ __forceinline__ void mpe_items_finish(MpeItems& it, const uint32_t* t
     it.c_kmax = wave_imax((it.cs.z & 0xffu) != 0 ? int((it.cs.y >> 16) & 0xffu) : 0);
 }
 
-struct MpeSmallLds {
-    double* pi;     // [2][M]
-    double* lam;    // [2][M]
-    double* npi;    // [2][N]
-    double* nlam;   // [2][N]
-    double* stg;    // [T], T >= N
-    uint32_t* term;
-    uint16_t* clist;
-    uint8_t* frz;
-    unsigned long long* red;
-};
-// (the layout SmallPlan::lds_bytes was sized for: bn_small.hip small_carve)
-__device__ __forceinline__ MpeSmallLds mpe_small_carve(char* base, const MpeSmallArgs& a) {
-    MpeSmallLds L;
-    double* d = reinterpret_cast<double*>(base);
-    L.pi = d; d += 2 * a.M;
-    L.lam = d; d += 2 * a.M;
-    L.npi = d; d += 2 * a.N;
-    L.nlam = d; d += 2 * a.N;
-    L.stg = d; d += a.T;
-    L.term = reinterpret_cast<uint32_t*>(d);
-    char* c = reinterpret_cast<char*>(L.term + (((a.TT > 0 ? a.TT : 1) + 1) & ~1));
-    L.clist = reinterpret_cast<uint16_t*>(c);
-    c += (size_t(a.CL > 0 ? a.CL : 1) * 2 + 7) & ~size_t(7);
-    L.frz = reinterpret_cast<uint8_t*>(c);
-    c += (size_t(a.N) + 7) & ~size_t(7);
-    L.red = reinterpret_cast<unsigned long long*>(c);
-    return L;
-}
-
 }  // namespace
 
 // ROUNDS = items of one kind per thread (1, 2 or kSmallMaxRounds)
@@ -204,7 +114,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
     const int set = blockIdx.x;
     double* state = a.state + int64_t(set) * (2 * int64_t(a.M) + 2 * int64_t(a.N));
     double* res_hist = a.res_hist + int64_t(set) * a.res_cap;
-    const MpeSmallLds L = mpe_small_carve(mpe_lds, a);
+    const SmallLds L = small_carve(mpe_lds, a);   // (the layout SmallPlan::lds_bytes is sized for: bn_small_plan.cpp)
     const int tid = threadIdx.x, nt = blockDim.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -232,42 +142,13 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
     int s = a.sweep_begin;
     {
         const int c0 = s & 1;
-        // the evidence arrays themselves (mapped host memory): nodes, offsets and values are requested together and the values wait in
-        // the staging array until the offsets say where they belong (bn_small.hip: one trip over PCIe instead of two dependent ones)
+        // the evidence arrays themselves (mapped host memory)
         const int32_t* meta = a.ev_meta + 8 * set;
         const int ne = meta[0], nval = meta[4];
         const int32_t* ev_node = a.ev_node + meta[1];
         const int32_t* ev_off = a.ev_off + meta[2];
         const double* ev_val = a.ev_val + meta[3];
-        int v0 = 0, o0 = 0;
-        double x0 = 0.0;
-        if (tid < ne) { v0 = ev_node[tid]; o0 = ev_off[tid]; }
-        if (tid < nval && s == 0) x0 = ev_val[tid];
-        for (int y = tid; y < a.N; y += nt) {
-            L.frz[y] = 0;
-            L.npi[c0 * a.N + y] = s == 0 ? a.npi_init[y] : state[2 * a.M + y];
-            L.nlam[c0 * a.N + y] = s == 0 ? 1.0 : state[2 * a.M + a.N + y];
-        }
-        __syncthreads();   // (the staging array has been zeroed by every thread's loop above)
-        const bool vals_in_lds = nval <= a.T;
-        if (s == 0 && vals_in_lds)
-            for (int t = tid; t < nval; t += nt) L.stg[t] = t == tid ? x0 : ev_val[t];
-        __syncthreads();
-        for (int j = tid; j < ne; j += nt) {  // both pi(v) and lambda(v) take the evidence vector (:68-73)
-            const int v = j == tid ? v0 : ev_node[j], o = j == tid ? o0 : ev_off[j];
-            const int lo = a.node_off[v], hi = a.node_off[v + 1];
-            for (int i = 0; i < hi - lo; ++i) {
-                L.frz[lo + i] = 1;
-                if (s == 0) {
-                    const double x = vals_in_lds ? L.stg[o + i] : ev_val[o + i];
-                    L.npi[c0 * a.N + lo + i] = x;
-                    L.nlam[c0 * a.N + lo + i] = x;
-                }
-            }
-        }
-        __syncthreads();
-        if (s == 0 && vals_in_lds)
-            for (int t = tid; t < nval; t += nt) L.stg[t] = 0.0;  // the padding of the runs is zero again
+#include "bn_small_evidence.inc"
         for (int x = tid; x < a.M; x += nt) {
             L.pi[c0 * a.M + x] = s == 0 ? 1.0 : state[x];
             L.lam[c0 * a.M + x] = s == 0 ? 1.0 : state[a.M + x];
@@ -292,7 +173,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
         // ---- phase 1: entry items
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r)
-            if (r < a.re) mpe_entry_any<kTermsInRegs>(it[r].e_mm, L.stg, L.term, pi_cur, nlam_cur, it[r].ent, it[r].ecpt, it[r].treg);
+            if (r < a.re) item_entry_any<kTermsInRegs, true>(it[r].e_mm, L.stg, L.term, pi_cur, nlam_cur, it[r].ent, it[r].ecpt, it[r].treg, LdPlain{});
         __syncthreads();
         // ---- phase 2a: accumulator items: the LARGEST term of the run (the one line that differs from sum-product)
 #pragma unroll
@@ -307,7 +188,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
             const bool frozen = L.frz[out_idx] != 0;
             const double acc = mpe_fold<(ROUNDS <= 2 ? 8 : 4), ROUNDS == 1>(L.stg + base, it[r].b_rmax);
             double* buf = kind == 1 ? npi_new : lam_new;
-            const double val = mpe_normalize(buf, on, out_idx, k, at, acc, it[r].b_kmax);
+            const double val = small_normalize(buf, on, out_idx, k, at, acc, it[r].b_kmax);
             if (kind == 1) npi_new[out_idx] = frozen ? old : val;  // evidence nodes are never updated (:177)
             if (kind == 2) {
                 lam_new[out_idx] = val;
@@ -339,7 +220,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
                 for (int u = 0; u < 4; ++u) val *= (x0 + u < deg && x0 + u != skip) ? f[u] : 1.0;  // x * 1.0 == x
             }
             double* buf = kind == 4 ? pi_new : nlam_new;
-            val = mpe_normalize(buf, on, out_idx, k, at, val, it[r].c_kmax);
+            val = small_normalize(buf, on, out_idx, k, at, val, it[r].c_kmax);
             if (kind == 3) nlam_new[out_idx] = frozen ? old : val;  // evidence nodes are never updated (:177)
             if (kind == 4) {
                 pi_new[out_idx] = val;
@@ -374,7 +255,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
         const bool on = (q.z & 0xffu) == 3;  // the lambda(v) items: one per node-vector element
         const int out_idx = int(q.y & 0xffffu), k = int((q.y >> 16) & 0xffu), at = lane - int(q.y >> 24);
         const double val = on ? L.npi[fin * a.N + out_idx] * L.nlam[fin * a.N + out_idx] : 0.0;
-        const double bel = mpe_normalize(L.stg, on, out_idx, on ? k : 0, at, val, it[r].c_kmax);
+        const double bel = small_normalize(L.stg, on, out_idx, on ? k : 0, at, val, it[r].c_kmax);
         if (on) { out_mm[out_idx] = bel; L.stg[out_idx] = bel; }
         lds_fence();
         if (node_of[r] >= 0) out_st[node_of[r]] = mpe_decode(L.stg + out_idx, k);
@@ -386,70 +267,16 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_small_kernel(MpeSm
     }
 }
 
-int prepare_mpe_small() {
-    (void)hipGetLastError();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mpe_small_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mpe_small_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mpe_small_kernel<kSmallMaxRounds>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    return e == hipSuccess ? 0 : int(e);
-}
+constexpr auto mpe_small_of = [](auto R) { return mpe_small_kernel<decltype(R)::value>; };
+
+int prepare_mpe_small() { return prepare_item_kernels(mpe_small_of); }
 
 int launch_mpe_small(const MpeSmallArgs& a, int waves, size_t lds_bytes, int n_sets, void* stream) {
-    (void)hipGetLastError();  // drop any stale error of this thread
-    const dim3 grid(n_sets > 1 ? n_sets : 1), block(waves * kWave);
-    const int rounds = a.re > a.rb ? (a.re > a.rc ? a.re : a.rc) : (a.rb > a.rc ? a.rb : a.rc);
-    if (rounds <= 1) hipLaunchKernelGGL(mpe_small_kernel<1>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else if (rounds <= 2) hipLaunchKernelGGL(mpe_small_kernel<2>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(mpe_small_kernel<kSmallMaxRounds>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launch_item_kernel(item_rounds(a.re, a.rb, a.rc), mpe_small_of, dim3(n_sets > 1 ? n_sets : 1), dim3(waves * kWave), lds_bytes, stream, a);
 }
 
 // ================================================================================================================================
 // several workgroups, one launch per sweep
-
-namespace {
-
-struct MpeMidLds {
-    double* stg;        // [T] this workgroup's staged terms
-    double* scratch;    // [waves][64] normalisation: a line per wave
-    unsigned long long* red;  // [16] per-wave residuals, [16]: the previous sweep's maximum over all workgroups
-    uint32_t* term;     // [TT]
-    uint16_t* clist;    // [CL]
-};
-// (within the layout MidPlan::lds_bytes was sized for: bn_mid.hip mid_carve)
-__device__ __forceinline__ MpeMidLds mpe_mid_carve(char* base, const MidPart& pt) {
-    MpeMidLds L;
-    double* d = reinterpret_cast<double*>(base);
-    L.stg = d; d += pt.T;
-    L.scratch = d; d += kSmallMaxWaves * kWave;
-    L.red = reinterpret_cast<unsigned long long*>(d); d += 2 * 16 + 2;
-    L.term = reinterpret_cast<uint32_t*>(d);
-    char* c = reinterpret_cast<char*>(L.term + (((pt.TT > 0 ? pt.TT : 1) + 1) & ~1));
-    L.clist = reinterpret_cast<uint16_t*>(c);
-    return L;
-}
-
-// normalisation through the wave's scratch line (:298-311); the line keeps the un-normalised vector afterwards
-__device__ __forceinline__ double mpe_mid_normalize(double* line, int lane, int k, int at, double val, int kmax) {
-    lds_fence();
-    line[lane] = val;
-    lds_fence();
-    const int first = lane - at;
-    double sum = 0.0;
-    for (int r0 = 0; r0 < kmax; r0 += 4) {
-        double x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] = line[first + (r0 + q < k ? r0 + q : 0)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sum += r0 + q < k ? x[q] : 0.0;
-    }
-    lds_fence();
-    return val / sum;
-}
-
-}  // namespace
 
 // Initial state (:33-64) of buffer 0, no evidence marks, the run goes on.  A flat grid over the elements.
 __global__ __launch_bounds__(256) void mpe_mid_init_kernel(MpeMidArgs a) {
@@ -484,12 +311,11 @@ template <int ROUNDS, bool FINISH>
 __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidArgs a, int32_t s) {
     extern __shared__ __attribute__((aligned(16))) char mpe_lds[];
     const MidPart pt = a.parts[blockIdx.x];
-    const MpeMidLds L = mpe_mid_carve(mpe_lds, pt);
+    const MidLds L = mid_carve(mpe_lds, pt);   // (the layout MidPlan::lds_bytes is sized for; `flag` is never touched here)
     const int tid = threadIdx.x, nt = blockDim.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     double* line = L.scratch + wave * kWave;
-    const bool mine = tid < pt.nt;   // (the launch is as wide as the widest part)
 
     // ONE thread reads the stop word (workgroup 0 of this very launch may be writing it: every thread of a workgroup must see the
     // same value, they meet at barriers below -- either value leads to the same decision)
@@ -528,18 +354,12 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
     if (!FINISH && stopped >= 0) return;   // a launch queued behind the stopping sweep
     if (FINISH && stopped < 0) return;     // the host reads done == 0 and queues the next group
 
-    // ---- this thread's items
-    constexpr bool kTermsInRegs = ROUNDS == 1 && !FINISH;
-    MpeItems it[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        it[r].ent = SmallEntry{0u, 0u}; it[r].ecpt = 0.0;
-        it[r].bs = SmallSlot{0u, 0u, 0u, 0u}; it[r].cs = SmallSlot{0u, 0u, 0u, 0u};
-        if (!FINISH && mine && r < pt.re) { it[r].ent = a.ent[pt.ent_off + r * pt.nt + tid]; it[r].ecpt = a.ent_cpt[pt.ent_off + r * pt.nt + tid]; }
-        if (!FINISH && mine && r < pt.rb) it[r].bs = a.bslot[pt.bslot_off + r * pt.nt + tid];
-        if (mine && r < pt.rc) it[r].cs = a.cslot[pt.cslot_off + r * pt.nt + tid];
-        mpe_items_finish<kTermsInRegs>(it[r], a.term + pt.term_off);
-    }
+    // ---- this thread's items (the finishing launch: its product items only)
+    const SmallEntry* const it_ent = a.ent + pt.ent_off; const double* const it_cpt = a.ent_cpt + pt.ent_off; const uint32_t* const it_term = a.term + pt.term_off;
+    const SmallSlot* const it_bslot = a.bslot + pt.bslot_off; const SmallSlot* const it_cslot = a.cslot + pt.cslot_off;
+    const int it_nt = pt.nt, it_re = FINISH ? 0 : pt.re, it_rb = FINISH ? 0 : pt.rb, it_rc = pt.rc;
+    const bool it_mine = tid < pt.nt;   // (the launch is as wide as the widest part)
+#include "bn_small_items.inc"
 
     if (FINISH) {
         // ---- max-marginal = normalize(pi % lambda) (:151-158) of this workgroup's nodes from the state the run stopped in; the state
@@ -547,11 +367,12 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
             if (r >= pt.rc) break;
-            const SmallSlot q = it[r].cs;
+            const SmallSlot q = cs[r];
             const bool on = (q.z & 0xffu) == 3;  // the lambda(v) items: one per node-vector element
             const int out_idx = int(q.y & 0xffffu), k = int((q.y >> 16) & 0xffu), at = lane - int(q.y >> 24);
             const double val = on ? a.npi[fin * a.N + out_idx] * a.nlam[fin * a.N + out_idx] : 0.0;
-            const double bel = mpe_mid_normalize(line, lane, on ? k : 0, on ? at : 0, val, it[r].c_kmax);
+            lds_fence();   // (the line is still being read: by mpe_decode of the round before)
+            const double bel = mid_normalize(line, lane, on ? k : 0, on ? at : 0, val, c_kmax[r]);
             if (on) a.max_marginals[out_idx] = bel;
             line[lane] = bel;
             lds_fence();
@@ -578,13 +399,13 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
     // ---- phase 1: entry items (gathers from memory, terms into LDS)
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r)
-        if (r < pt.re) mpe_entry_any<kTermsInRegs>(it[r].e_mm, L.stg, L.term, pi_cur, nlam_cur, it[r].ent, it[r].ecpt, it[r].treg);
+        if (r < pt.re) item_entry_any<kTermsInRegs, true>(e_mm[r], L.stg, L.term, pi_cur, nlam_cur, ent[r], ecpt[r], treg[r], LdPlain{});
     __syncthreads();
     // ---- phase 2a: accumulator items: the largest term of the run
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
         if (r >= pt.rb) break;
-        const SmallSlot q = it[r].bs;
+        const SmallSlot q = bs[r];
         const int kind = int(q.z & 0xffu);
         const int base = int(q.x & 0xffffu);
         const int out_idx = int(q.y & 0xffffu), k = int((q.y >> 16) & 0xffu), at = lane - int(q.y >> 24);
@@ -592,8 +413,9 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
         bool frozen = false;
         if (kind == 1) { old = npi_cur[out_idx]; frozen = a.frz[out_idx] != 0; }
         if (kind == 2) old = lam_cur[out_idx];
-        const double acc = mpe_fold<(ROUNDS <= 2 ? 8 : 4), ROUNDS == 1>(L.stg + base, it[r].b_rmax);
-        const double val = mpe_mid_normalize(line, lane, kind != 0 ? k : 0, kind != 0 ? at : 0, acc, it[r].b_kmax);
+        const double acc = mpe_fold<(ROUNDS <= 2 ? 8 : 4), ROUNDS == 1>(L.stg + base, b_rmax[r]);
+        lds_fence();   // (the line still holds the vector of the item before: its reads come first)
+        const double val = mid_normalize(line, lane, kind != 0 ? k : 0, kind != 0 ? at : 0, acc, b_kmax[r]);
         if (kind == 1) npi_new[out_idx] = frozen ? old : val;  // evidence nodes are never updated (:177)
         if (kind == 2) {
             lam_new[out_idx] = val;
@@ -604,7 +426,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
         if (r >= pt.rc) break;
-        const SmallSlot q = it[r].cs;
+        const SmallSlot q = cs[r];
         const int kind = int(q.z & 0xffu), skip = int((q.z >> 8) & 0xffffu);
         const int cl = int(q.x & 0xffffu), deg = int(q.x >> 16);
         const int out_idx = int(q.y & 0xffffu), k = int((q.y >> 16) & 0xffu), at = lane - int(q.y >> 24);
@@ -614,7 +436,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
         if (kind == 3) { old = nlam_cur[out_idx]; frozen = a.frz[out_idx] != 0; }
         // lambda(v): from 1.0 (:220-238); pi-message: from pi(v)[i] (:202-218); children in ascending order
         double val = kind == 4 ? npi_cur[q.w & 0xffffu] : 1.0;
-        for (int c0 = 0; c0 < it[r].c_dmax; c0 += 4) {
+        for (int c0 = 0; c0 < c_dmax[r]; c0 += 4) {
             double f[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -625,7 +447,8 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
 #pragma unroll
             for (int u = 0; u < 4; ++u) val *= (c0 + u < deg && c0 + u != skip) ? f[u] : 1.0;  // x * 1.0 == x
         }
-        val = mpe_mid_normalize(line, lane, kind != 0 ? k : 0, kind != 0 ? at : 0, val, it[r].c_kmax);
+        lds_fence();   // (as above)
+        val = mid_normalize(line, lane, kind != 0 ? k : 0, kind != 0 ? at : 0, val, c_kmax[r]);
         if (kind == 3) nlam_new[out_idx] = frozen ? old : val;
         if (kind == 4) {
             pi_new[out_idx] = val;
@@ -643,18 +466,10 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void mpe_mid_kernel(MpeMidA
     }
 }
 
-int prepare_mpe_mid() {
-    (void)hipGetLastError();
-    hipError_t e = hipSuccess;
-    auto set = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes); };
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<1, false>));
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<2, false>));
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<kSmallMaxRounds, false>));
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<1, true>));
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<2, true>));
-    set(reinterpret_cast<const void*>(mpe_mid_kernel<kSmallMaxRounds, true>));
-    return e == hipSuccess ? 0 : int(e);
-}
+constexpr auto mpe_mid_sweep_of = [](auto R) { return mpe_mid_kernel<decltype(R)::value, false>; };
+constexpr auto mpe_mid_finish_of = [](auto R) { return mpe_mid_kernel<decltype(R)::value, true>; };
+
+int prepare_mpe_mid() { return prepare_item_kernels(mpe_mid_sweep_of, mpe_mid_finish_of); }
 
 int launch_mpe_mid_init(const MpeMidArgs& a, void* stream) {
     (void)hipGetLastError();
@@ -671,20 +486,9 @@ int launch_mpe_mid_evidence(const MpeMidArgs& a, void* stream) {
     return e == hipSuccess ? 0 : int(e);
 }
 int launch_mpe_mid_sweep(const MpeMidArgs& a, int32_t s, bool finish, int waves, int rounds, size_t lds_bytes, void* stream) {
-    (void)hipGetLastError();
     const dim3 grid(a.nparts), block(waves * kWave);
-    hipStream_t st = (hipStream_t)stream;
-    if (finish) {
-        if (rounds <= 1) hipLaunchKernelGGL((mpe_mid_kernel<1, true>), grid, block, lds_bytes, st, a, s);
-        else if (rounds <= 2) hipLaunchKernelGGL((mpe_mid_kernel<2, true>), grid, block, lds_bytes, st, a, s);
-        else hipLaunchKernelGGL((mpe_mid_kernel<kSmallMaxRounds, true>), grid, block, lds_bytes, st, a, s);
-    } else {
-        if (rounds <= 1) hipLaunchKernelGGL((mpe_mid_kernel<1, false>), grid, block, lds_bytes, st, a, s);
-        else if (rounds <= 2) hipLaunchKernelGGL((mpe_mid_kernel<2, false>), grid, block, lds_bytes, st, a, s);
-        else hipLaunchKernelGGL((mpe_mid_kernel<kSmallMaxRounds, false>), grid, block, lds_bytes, st, a, s);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return finish ? launch_item_kernel(rounds, mpe_mid_finish_of, grid, block, lds_bytes, stream, a, s)
+                  : launch_item_kernel(rounds, mpe_mid_sweep_of, grid, block, lds_bytes, stream, a, s);
 }
 
 }  // namespace bnmi

@@ -9,22 +9,17 @@
 //   the workgroup's maximum_difference -> one atomic max -> GRID barrier (a flag word per workgroup: it stores the
 //   generation there, its first wave reads all flags) -> every workgroup reads the same word: same stop decision.
 // Sums and products keep the reference's order: bit-identical to the oracle, like bn_small.hip.
+// The thread's items (bn_small_items.inc), the entry item (item_entry, with agent-scope loads), the run sum, the LDS layout and the
+// normalisation through a scratch line are bn_small_dev.hpp's, shared with the other item kernels; the sweep's statements are this
+// file's own (agent-scope accesses, the preloads of the one-round kernel, the grid barrier).
 // Every wait is bounded: a workgroup that gives up raises *abort (page-locked host word) and leaves; the host redoes the
 // run with one launch per sweep.
 #include "bn_small.hpp"
 #include "bn_tiles.hpp"
 #include "bn_small_dev.hpp"
+#include "bn_item_launch.hpp"
 
 namespace bnmi {
-
-__device__ __forceinline__ double ld_state(const double* p) {
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void st_state(double* p, double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // diagnostic builds (make EXTRA=-DBN_TILE_CLOCK): thread 0 of every workgroup records the 100 MHz clock at the phase
 // boundaries of iteration 3 (scripts/experiments/mid_clock.py prints them)
@@ -34,93 +29,6 @@ __device__ unsigned long long g_mid_clock[kMidMaxParts][8];
 #else
 #define MID_STAMP(k) do { } while (0)
 #endif
-
-struct MidLds {
-    double* stg;        // [T] this workgroup's staged terms
-    uint32_t* term;     // [TT]
-    uint16_t* clist;    // [CL]
-    double* scratch;    // [waves][64] normalisation: a line per wave
-    unsigned long long* red;  // [2][16] + [32]: what the last grid barrier collected
-    unsigned* flag;     // [1] set by the polling thread: the grid wait gave up
-};
-
-__device__ __forceinline__ MidLds mid_carve(char* base, const MidPart& pt) {
-    MidLds L;
-    double* d = reinterpret_cast<double*>(base);
-    L.stg = d; d += pt.T;
-    L.scratch = d; d += kSmallMaxWaves * kWave;
-    L.red = reinterpret_cast<unsigned long long*>(d); d += 2 * 16 + 2;   // [2][16] per-wave residuals, [32]: the barrier's maximum
-    L.term = reinterpret_cast<uint32_t*>(d);
-    char* c = reinterpret_cast<char*>(L.term + (((pt.TT > 0 ? pt.TT : 1) + 1) & ~1));
-    L.clist = reinterpret_cast<uint16_t*>(c);
-    c += (size_t(pt.CL > 0 ? pt.CL : 1) * 2 + 7) & ~size_t(7);
-    L.flag = reinterpret_cast<unsigned*>(c);
-    return L;
-}
-
-// One CPT entry (bn_small.hip small_entry, state read from memory)
-template <int MM, bool REG>
-__device__ __forceinline__ void mid_entry(const MidLds& L, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
-                                          const uint32_t (&treg)[4]) {
-    if (((h.y >> 24) & 1u) == 0) return;
-    const int m = int((h.y >> 16) & 0xffu), tbase = int(h.y & 0xffffu);
-    const double li = ld_state(nlam_cur + (h.x & 0xffffu));
-    uint32_t tw[MM > 0 ? MM : 1];
-    double pj[MM > 0 ? MM : 1];
-#pragma unroll
-    for (int j = 0; j < MM; ++j) {
-        if (REG && MM <= 4) tw[j] = treg[j < 4 ? j : 0];
-        else tw[j] = j < m ? L.term[tbase + j] : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < MM; ++j) {
-        const double x = ld_state(pi_cur + (tw[j] & 0xffffu));
-        pj[j] = j < m ? x : 1.0;
-    }
-    double v = c;
-#pragma unroll
-    for (int j = 0; j < MM; ++j) v *= pj[j];
-    L.stg[h.x >> 16] = v;
-    const double lc = li * c;
-#pragma unroll
-    for (int jt = 0; jt < MM; ++jt) {
-        double w = lc;
-#pragma unroll
-        for (int j = 0; j < MM; ++j)
-            if (j != jt) w *= pj[j];
-        if (jt < m) L.stg[tw[jt] >> 16] = w;
-    }
-}
-template <bool REG>
-__device__ __forceinline__ void mid_entry_any(int mm, const MidLds& L, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
-                                              const uint32_t (&treg)[4]) {
-    switch (mm) {
-        case 0: return mid_entry<0, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 1: return mid_entry<1, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 2: return mid_entry<2, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 3: return mid_entry<3, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 4: return mid_entry<4, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 5: case 6: return mid_entry<6, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        default: return mid_entry<8, REG>(L, pi_cur, nlam_cur, h, c, treg);
-    }
-}
-
-// normalisation of the vector whose elements sit in adjacent lanes of this wave, through the wave's scratch line (:298-311)
-__device__ __forceinline__ double mid_normalize(double* line, int lane, int k, int at, double val, int kmax) {
-    line[lane] = val;
-    lds_fence();
-    const int first = lane - at;
-    double sum = 0.0;
-    for (int r0 = 0; r0 < kmax; r0 += 4) {
-        double x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] = line[first + (r0 + q < k ? r0 + q : 0)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sum += r0 + q < k ? x[q] : 0.0;  // + 0.0 past the end: a sum started from +0.0 is never -0.0
-    }
-    lds_fence();
-    return val / sum;
-}
 
 // Grid barrier number `gen` (1, 2, ...) that also carries maximum_difference (round 5; bn_resident.hip's granule form).  Once a
 // workgroup's stores are out, ONE thread stores a 16-byte granule {gen | residual high half}, {gen | residual low half} into a PACKED
@@ -234,33 +142,13 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_mid_kernel(MidArgs 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     double* line = L.scratch + wave * kWave;
     const unsigned long long t_first = wall_clock64();
-    const bool mine = tid < pt.nt;   // (the launch is as wide as the widest part)
 
     // ---- this thread's items, kept in registers for the whole run
-    SmallEntry ent[ROUNDS];
-    double ecpt[ROUNDS];
-    SmallSlot bs[ROUNDS], cs[ROUNDS];
-    constexpr bool kTermsInRegs = ROUNDS == 1;
-    uint32_t treg[ROUNDS][4];
-    int e_mm[ROUNDS], b_rmax[ROUNDS], b_kmax[ROUNDS], c_dmax[ROUNDS], c_kmax[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        ent[r] = SmallEntry{0u, 0u}; ecpt[r] = 0.0;
-        bs[r] = SmallSlot{0u, 0u, 0u, 0u}; cs[r] = SmallSlot{0u, 0u, 0u, 0u};
-        if (mine && r < pt.re) { ent[r] = a.ent[pt.ent_off + r * pt.nt + tid]; ecpt[r] = a.ent_cpt[pt.ent_off + r * pt.nt + tid]; }
-        if (mine && r < pt.rb) bs[r] = a.bslot[pt.bslot_off + r * pt.nt + tid];
-        if (mine && r < pt.rc) cs[r] = a.cslot[pt.cslot_off + r * pt.nt + tid];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            treg[r][j] = 0u;
-            if (kTermsInRegs && ((ent[r].y >> 24) & 1u) && j < int((ent[r].y >> 16) & 0xffu)) treg[r][j] = a.term[pt.term_off + (ent[r].y & 0xffffu) + j];
-        }
-        e_mm[r] = wave_imax(((ent[r].y >> 24) & 1u) ? int((ent[r].y >> 16) & 0xffu) : 0);
-        b_rmax[r] = wave_imax(int(bs[r].x >> 16));
-        b_kmax[r] = wave_imax(bs[r].z != 0 ? int((bs[r].y >> 16) & 0xffu) : 0);
-        c_dmax[r] = wave_imax(int(cs[r].x >> 16));
-        c_kmax[r] = wave_imax((cs[r].z & 0xffu) != 0 ? int((cs[r].y >> 16) & 0xffu) : 0);
-    }
+    const SmallEntry* const it_ent = a.ent + pt.ent_off; const double* const it_cpt = a.ent_cpt + pt.ent_off; const uint32_t* const it_term = a.term + pt.term_off;
+    const SmallSlot* const it_bslot = a.bslot + pt.bslot_off; const SmallSlot* const it_cslot = a.cslot + pt.cslot_off;
+    const int it_nt = pt.nt, it_re = pt.re, it_rb = pt.rb, it_rc = pt.rc;
+    const bool it_mine = tid < pt.nt;   // (the launch is as wide as the widest part)
+#include "bn_small_items.inc"
     for (int t = tid; t < pt.TT; t += nt) L.term[t] = a.term[pt.term_off + t];
     for (int t = tid; t < pt.CL; t += nt) L.clist[t] = a.clist[pt.clist_off + t];
     for (int t = tid; t < pt.T; t += nt) L.stg[t] = 0.0;  // the padding of the runs stays zero for the whole run
@@ -361,7 +249,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_mid_kernel(MidArgs 
         // ---- phase 1: entry items
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r)
-            if (r < pt.re) mid_entry_any<kTermsInRegs>(e_mm[r], L, pi_cur, nlam_cur, ent[r], ecpt[r], treg[r]);
+            if (r < pt.re) item_entry_any<kTermsInRegs, false>(e_mm[r], L.stg, L.term, pi_cur, nlam_cur, ent[r], ecpt[r], treg[r], LdAgent{});
         MID_STAMP(1);
         __syncthreads();
         MID_STAMP(2);
@@ -377,18 +265,7 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_mid_kernel(MidArgs 
             bool frozen = false;
             if (kind == 1) { if (!kPreload) old = ld_state(npi_cur + out_idx); frozen = frz_b[r]; }
             if (kind == 2 && !kPreload) old = ld_state(lam_cur + out_idx);
-            const double* ptr = L.stg + base;
-            const int n4 = b_rmax[r];  // a multiple of 4
-            double acc = 0.0;
-            double x0_ = ptr[0], x1_ = ptr[1], x2_ = ptr[2], x3_ = ptr[3];
-            int r0 = 0;
-            for (; r0 + 8 <= n4; r0 += 8) {
-                const double y0_ = ptr[r0 + 4], y1_ = ptr[r0 + 5], y2_ = ptr[r0 + 6], y3_ = ptr[r0 + 7];
-                acc += x0_; acc += x1_; acc += x2_; acc += x3_;
-                x0_ = ptr[r0 + 8]; x1_ = ptr[r0 + 9]; x2_ = ptr[r0 + 10]; x3_ = ptr[r0 + 11];
-                acc += y0_; acc += y1_; acc += y2_; acc += y3_;
-            }
-            if (r0 < n4) { acc += x0_; acc += x1_; acc += x2_; acc += x3_; }
+            const double acc = small_run_sum(L.stg + base, b_rmax[r]);
             const double val = mid_normalize(line, lane, kind != 0 ? k : 0, kind != 0 ? at : 0, acc, b_kmax[r]);
             if (kind == 1) st_state(npi_new + out_idx, frozen ? old : val);  // evidence nodes are never updated (:177)
             if (kind == 2) {
@@ -472,23 +349,12 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_mid_kernel(MidArgs 
     }
 }
 
-int prepare_bp_mid() {
-    (void)hipGetLastError();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_mid_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_mid_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_mid_kernel<kSmallMaxRounds>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    return e == hipSuccess ? 0 : int(e);
-}
+constexpr auto bp_mid_of = [](auto R) { return bp_mid_kernel<decltype(R)::value>; };
+
+int prepare_bp_mid() { return prepare_item_kernels(bp_mid_of); }
 
 int launch_bp_mid(const MidArgs& a, int waves, int rounds, size_t lds_bytes, int n_sets, void* stream) {
-    (void)hipGetLastError();  // drop any stale error of this thread
-    const dim3 grid(a.nparts, n_sets > 1 ? n_sets : 1), block(waves * kWave);
-    if (rounds <= 1) hipLaunchKernelGGL(bp_mid_kernel<1>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else if (rounds <= 2) hipLaunchKernelGGL(bp_mid_kernel<2>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bp_mid_kernel<kSmallMaxRounds>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launch_item_kernel(rounds, bp_mid_of, dim3(a.nparts, n_sets > 1 ? n_sets : 1), dim3(waves * kWave), lds_bytes, stream, a);
 }
 
 }  // namespace bnmi

@@ -10,10 +10,12 @@
 //   barrier   every wave reads the same words and takes the same stop decision (:147, strict <).
 // Old and new state are the two halves of double buffers (the reference's new_* maps, :135-143).
 // The thread's items and the iteration's statements are bn_small_items.inc and bn_small_sweep.inc, shared as text with
-// em_small_kernel (bn_em.hip); the pieces below them -- LDS layout, entry item, run sum, normalisation -- are bn_small_dev.hpp's.
+// em_small_kernel (bn_em.hip); the pieces below them -- LDS layout, entry item, run sum,
+// normalisation -- are bn_small_dev.hpp's.  The evidence prologue is bn_small_evidence.inc, shared as text with mpe_small_kernel.
 #include "bn_small.hpp"
 #include "bn_tiles.hpp"
 #include "bn_small_dev.hpp"
+#include "bn_item_launch.hpp"
 
 namespace bnmi {
 
@@ -41,6 +43,10 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_small_kernel(SmallA
     const unsigned long long t_first = wall_clock64();
 
     // ---- this thread's items, kept in registers for the whole run
+    const SmallEntry* const it_ent = a.ent; const double* const it_cpt = a.ent_cpt; const uint32_t* const it_term = a.term;
+    const SmallSlot* const it_bslot = a.bslot; const SmallSlot* const it_cslot = a.cslot;
+    const int it_nt = nt, it_re = a.re, it_rb = a.rb, it_rc = a.rc;
+    constexpr bool it_mine = true;
 #include "bn_small_items.inc"
     // ---- tables and initial state (:33-73) into LDS
     for (int t = tid; t < a.TT; t += nt) L.term[t] = a.term[t];
@@ -63,43 +69,13 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_small_kernel(SmallA
                 }
             }
         } else {
-            // the evidence arrays themselves (mapped host memory): nodes, offsets AND values are requested together -- the
-            // values' range is known from the set's header, so they travel while the initial state is written and wait in
-            // the staging array until the offsets say where they belong (one trip over PCIe instead of two dependent ones)
+            // the evidence arrays themselves (mapped host memory)
             const int32_t* meta = a.ev_meta ? a.ev_meta + 8 * set : nullptr;
             const int ne = meta ? meta[0] : a.ev_ne, nval = meta ? meta[4] : a.ev_nval;
             const int32_t* ev_node = a.ev_node + (meta ? meta[1] : 0);
             const int32_t* ev_off = a.ev_off + (meta ? meta[2] : 0);
             const double* ev_val = a.ev_val + (meta ? meta[3] : 0);
-            int v0 = 0, o0 = 0;
-            double x0 = 0.0;
-            if (tid < ne) { v0 = ev_node[tid]; o0 = ev_off[tid]; }
-            if (tid < nval && s == 0) x0 = ev_val[tid];
-            for (int y = tid; y < a.N; y += nt) {
-                L.frz[y] = 0;
-                L.npi[c0 * a.N + y] = s == 0 ? a.npi_init[y] : state[2 * a.M + y];
-                L.nlam[c0 * a.N + y] = s == 0 ? 1.0 : state[2 * a.M + a.N + y];
-            }
-            __syncthreads();   // (the staging array has been zeroed by every thread's loop above)
-            const bool vals_in_lds = nval <= a.T;
-            if (s == 0 && vals_in_lds)
-                for (int t = tid; t < nval; t += nt) L.stg[t] = t == tid ? x0 : ev_val[t];
-            __syncthreads();
-            for (int j = tid; j < ne; j += nt) {  // both pi(v) and lambda(v) take the evidence vector (:68-73)
-                const int v = j == tid ? v0 : ev_node[j], o = j == tid ? o0 : ev_off[j];
-                const int lo = a.node_off[v], hi = a.node_off[v + 1];
-                for (int i = 0; i < hi - lo; ++i) {
-                    L.frz[lo + i] = 1;
-                    if (s == 0) {
-                        const double x = vals_in_lds ? L.stg[o + i] : ev_val[o + i];
-                        L.npi[c0 * a.N + lo + i] = x;
-                        L.nlam[c0 * a.N + lo + i] = x;
-                    }
-                }
-            }
-            __syncthreads();
-            if (s == 0 && vals_in_lds)
-                for (int t = tid; t < nval; t += nt) L.stg[t] = 0.0;  // the padding of the runs is zero again
+#include "bn_small_evidence.inc"
         }
         for (int x = tid; x < a.M; x += nt) {
             L.pi[c0 * a.M + x] = s == 0 ? 1.0 : state[x];
@@ -142,25 +118,12 @@ __global__ __launch_bounds__(kSmallMaxWaves * kWave) void bp_small_kernel(SmallA
     }
 }
 
-// once per device before the first launch: the kernel's dynamic LDS may exceed the 64 KiB default
-int prepare_bp_small() {
-    (void)hipGetLastError();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_small_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_small_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_small_kernel<kSmallMaxRounds>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-    return e == hipSuccess ? 0 : int(e);
-}
+constexpr auto bp_small_of = [](auto R) { return bp_small_kernel<decltype(R)::value>; };
+
+int prepare_bp_small() { return prepare_item_kernels(bp_small_of); }
 
 int launch_bp_small(const SmallArgs& a, int waves, size_t lds_bytes, int n_sets, void* stream) {
-    (void)hipGetLastError();  // drop any stale error of this thread
-    const dim3 grid(n_sets > 1 ? n_sets : 1), block(waves * kWave);
-    const int rounds = a.re > a.rb ? (a.re > a.rc ? a.re : a.rc) : (a.rb > a.rc ? a.rb : a.rc);
-    if (rounds <= 1) hipLaunchKernelGGL(bp_small_kernel<1>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else if (rounds <= 2) hipLaunchKernelGGL(bp_small_kernel<2>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bp_small_kernel<kSmallMaxRounds>, grid, block, lds_bytes, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launch_item_kernel(item_rounds(a.re, a.rb, a.rc), bp_small_of, dim3(n_sets > 1 ? n_sets : 1), dim3(waves * kWave), lds_bytes, stream, a);
 }
 
 }  // namespace bnmi

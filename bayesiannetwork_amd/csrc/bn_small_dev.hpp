@@ -1,9 +1,15 @@
-// bn_small_dev.hpp -- device helpers shared by the item kernels: wave-level reductions without LDS traffic (bn_small.hip, bn_mid.hip,
-// bn_maxprod.hip), and the pieces of the one-workgroup iteration of sum-product belief propagation -- LDS layout, entry item, run sum,
-// normalisation -- which bn_small.hip (bp_small_kernel) and bn_em.hip (em_small_kernel) both run.  The thread's items and the
-// iteration's statements themselves are bn_small_items.inc and bn_small_sweep.inc, included by both kernels: one text, the same bits.  The kernels' argument
-// structs differ; what the helpers read of them (N, M, T, TT, CL, re, rb, rc and the item tables) has the same names in both, so they
-// take the struct as a template parameter.
+// bn_small_dev.hpp -- the device pieces the five item kernels share (bp_small_kernel, em_small_kernel, bp_mid_kernel, mpe_small_kernel,
+// mpe_mid_kernel: bn_small.hip, bn_em.hip, bn_mid.hip, bn_maxprod.hip):
+//   all five             wave-level reductions without LDS traffic; the entry item (item_entry: the ONE routine, told how a state word
+//                        is loaded and whether a bare table entry is canonicalised); the thread's items (bn_small_items.inc, as
+//                        text; mpe_small_kernel alone keeps its own)
+//   one workgroup        LDS layout (SmallLds), run sum, normalisation in place; the iteration's statements of bp_small_kernel and
+//                        em_small_kernel are bn_small_sweep.inc, as text (the same bits); the evidence prologue of
+//                        bp_small_kernel and mpe_small_kernel is bn_small_evidence.inc, as text
+//   several workgroups   LDS layout (MidLds), normalisation through a scratch line, agent-scope state accesses; bp_mid_kernel and
+//                        mpe_mid_kernel keep sweeps of their own (a grid barrier inside one launch against one launch per sweep)
+// The kernels' argument structs differ; what the helpers read of them (N, M, T, TT, CL, npi_init, node_off) has the same names in
+// all, so they take the struct as a template parameter.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -87,31 +93,47 @@ __device__ __forceinline__ SmallLds small_carve(char* base, const Args& a) {
     return L;
 }
 
+// How an entry item reads a word of the state: from LDS or from memory no other workgroup writes during the launch (a plain load), or
+// from memory other workgroups of the launch write (agent scope, sc1: through to L2 / memory, coherent across the XCDs).
+__device__ __forceinline__ double ld_state(const double* p) {
+    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ void st_state(double* p, double v) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+struct LdPlain { __device__ __forceinline__ double operator()(const double* p) const { return *p; } };
+struct LdAgent { __device__ __forceinline__ double operator()(const double* p) const { return ld_state(p); } };
+
 // One CPT entry: cpt * pi-messages in ascending parent order (:174-200) and, per target parent, (lambda(v)[i] * cpt)
-// * the OTHER parents' pi-messages in ascending order (:240-266).  MM = the wave's largest parent count: the loops are
-// unrolled to it, a lane with fewer parents multiplies by 1.0 (x * 1.0 == x).
-template <int MM, bool REG>
-__device__ __forceinline__ void small_entry(const SmallLds& L, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
-                                            const uint32_t (&treg)[4]) {
+// * the OTHER parents' pi-messages in ascending order (:240-266), into their places of the staging array `stg`.  MM = the wave's
+// largest parent count: the loops are unrolled to it, a lane with fewer parents multiplies by 1.0 (x * 1.0 == x).  REG: the entry's
+// parent terms are in `treg` (they never change: kept in registers when they fit -- one round of items, <= 4 parents), else in
+// `term`.  pi_cur / nlam_cur: the old state, read through `ld`.  CANON: a bare table entry (no parents) is staged quiet, like every
+// product (max-product: bn_maxprod.hip mpe_max).
+template <int MM, bool REG, bool CANON, class Ld>
+__device__ __forceinline__ void item_entry(double* stg, const uint32_t* term, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
+                                           const uint32_t (&treg)[4], Ld ld) {
     if (((h.y >> 24) & 1u) == 0) return;
     const int m = int((h.y >> 16) & 0xffu), tbase = int(h.y & 0xffffu);
-    const double li = nlam_cur[h.x & 0xffffu];
+    const double li = ld(nlam_cur + (h.x & 0xffffu));
     uint32_t tw[MM > 0 ? MM : 1];
     double pj[MM > 0 ? MM : 1];
 #pragma unroll
     for (int j = 0; j < MM; ++j) {
-        if (REG && MM <= 4) tw[j] = treg[j < 4 ? j : 0];  // (an entry's parent terms never change: kept in registers when they fit)
-        else tw[j] = j < m ? L.term[tbase + j] : 0u;
+        if (REG && MM <= 4) tw[j] = treg[j < 4 ? j : 0];
+        else tw[j] = j < m ? term[tbase + j] : 0u;
     }
 #pragma unroll
     for (int j = 0; j < MM; ++j) {
-        const double x = pi_cur[tw[j] & 0xffffu];
+        const double x = ld(pi_cur + (tw[j] & 0xffffu));
         pj[j] = j < m ? x : 1.0;
     }
-    double v = c;
+    double v = (CANON && MM == 0) ? __builtin_canonicalize(c) : c;
 #pragma unroll
     for (int j = 0; j < MM; ++j) v *= pj[j];
-    L.stg[h.x >> 16] = v;
+    stg[h.x >> 16] = v;
     const double lc = li * c;
 #pragma unroll
     for (int jt = 0; jt < MM; ++jt) {
@@ -119,21 +141,21 @@ __device__ __forceinline__ void small_entry(const SmallLds& L, const double* pi_
 #pragma unroll
         for (int j = 0; j < MM; ++j)
             if (j != jt) w *= pj[j];
-        if (jt < m) L.stg[tw[jt] >> 16] = w;
+        if (jt < m) stg[tw[jt] >> 16] = w;
     }
 }
 
-template <bool REG>
-__device__ __forceinline__ void small_entry_any(int mm, const SmallLds& L, const double* pi_cur, const double* nlam_cur, SmallEntry h, double c,
-                                                const uint32_t (&treg)[4]) {
+template <bool REG, bool CANON, class Ld>
+__device__ __forceinline__ void item_entry_any(int mm, double* stg, const uint32_t* term, const double* pi_cur, const double* nlam_cur, SmallEntry h,
+                                               double c, const uint32_t (&treg)[4], Ld ld) {
     switch (mm) {
-        case 0: return small_entry<0, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 1: return small_entry<1, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 2: return small_entry<2, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 3: return small_entry<3, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 4: return small_entry<4, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        case 5: case 6: return small_entry<6, REG>(L, pi_cur, nlam_cur, h, c, treg);
-        default: return small_entry<8, REG>(L, pi_cur, nlam_cur, h, c, treg);
+        case 0: return item_entry<0, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        case 1: return item_entry<1, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        case 2: return item_entry<2, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        case 3: return item_entry<3, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        case 4: return item_entry<4, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        case 5: case 6: return item_entry<6, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
+        default: return item_entry<8, REG, CANON>(stg, term, pi_cur, nlam_cur, h, c, treg, ld);
     }
 }
 
@@ -175,6 +197,53 @@ __device__ __forceinline__ double small_vector_sum(double* buf, bool on, int out
 // ... and the normalisation (:298-311, no zero guard)
 __device__ __forceinline__ double small_normalize(double* buf, bool on, int out_idx, int k, int at, double val, int kmax) {
     return val / small_vector_sum(buf, on, out_idx, k, at, val, kmax);
+}
+
+// ---- several workgroups (bn_mid.hip, bn_maxprod.hip mpe_mid_kernel): the state is in device memory, a workgroup's LDS holds its own
+// part's staged terms, parent terms and child lists.  MidPlan::lds_bytes (bn_small_plan.cpp build_plan_of_range, `part`) is sized
+// for this whole layout, `flag` and both halves of `red` included, and bn_engine_mpe.cpp launches mpe_mid_kernel with that figure:
+// the max-product kernel uses the same layout and simply never touches `flag`.
+
+struct MidLds {
+    double* stg;        // [T] this workgroup's staged terms
+    uint32_t* term;     // [TT]
+    uint16_t* clist;    // [CL]
+    double* scratch;    // [waves][64] normalisation: a line per wave
+    unsigned long long* red;  // [2][16] per-wave residuals, [32], [33]: what the last grid barrier collected (mpe_mid_kernel: [16] per-wave
+                              // residuals, [16], [17]: the previous sweep's maximum, the stop word)
+    unsigned* flag;     // [1] set by the polling thread: the grid wait gave up
+};
+
+__device__ __forceinline__ MidLds mid_carve(char* base, const MidPart& pt) {
+    MidLds L;
+    double* d = reinterpret_cast<double*>(base);
+    L.stg = d; d += pt.T;
+    L.scratch = d; d += kSmallMaxWaves * kWave;
+    L.red = reinterpret_cast<unsigned long long*>(d); d += 2 * 16 + 2;
+    L.term = reinterpret_cast<uint32_t*>(d);
+    char* c = reinterpret_cast<char*>(L.term + (((pt.TT > 0 ? pt.TT : 1) + 1) & ~1));
+    L.clist = reinterpret_cast<uint16_t*>(c);
+    c += (size_t(pt.CL > 0 ? pt.CL : 1) * 2 + 7) & ~size_t(7);
+    L.flag = reinterpret_cast<unsigned*>(c);
+    return L;
+}
+
+// normalisation of the vector whose elements sit in adjacent lanes of this wave, through the wave's scratch line (:298-311); the line
+// keeps the un-normalised vector afterwards
+__device__ __forceinline__ double mid_normalize(double* line, int lane, int k, int at, double val, int kmax) {
+    line[lane] = val;
+    lds_fence();
+    const int first = lane - at;
+    double sum = 0.0;
+    for (int r0 = 0; r0 < kmax; r0 += 4) {
+        double x[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = line[first + (r0 + q < k ? r0 + q : 0)];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sum += r0 + q < k ? x[q] : 0.0;  // + 0.0 past the end: a sum started from +0.0 is never -0.0
+    }
+    lds_fence();
+    return val / sum;
 }
 
 }  // namespace bnmi

@@ -2,14 +2,16 @@
 // TEXT: included inside the sweep loop of bp_small_kernel (bn_small.hip) and of em_small_kernel (bn_em.hip), so that both run the
 // same statements and give the same bits.  (A function would do for the bits, but not for the code: with the phases behind a call
 // boundary the compiler allocates the one-round kernel's registers differently -- 69 scalar spills instead of 34 -- and the sweep
-// of the ALARM-shaped network takes 2.00 us instead of 1.83.)
+// of the ALARM-shaped network takes 2.00 us instead of 1.83.  mpe_small_kernel (bn_maxprod.hip) keeps a copy of these statements with
+// its own fold: included here, with the fold as a macro, its one-round sweep was 11-14 ns slower -- DESIGN 4.16.)
 //   phase 1   entry items: the terms of pi(v) (:174-200) and of the lambda-messages (:240-266) -> staging;  barrier
 //   phase 2   accumulator items: each adds its run of staged terms front to back, normalises (:298-311), stores;
 //             product items: lambda(v) (:220-238) and the pi-messages (:202-218) from the OLD state, normalised, stored;
 //             maximum_difference (:105-131) of the wave -> LDS;  barrier;  every wave reduces the same words.
-// In scope where it is included: the items bn_small_items.inc declares (ent, ecpt, bs, cs, treg, e_mm, b_rmax, b_kmax, c_dmax, c_kmax, kTermsInRegs); SmallLds L; the kernel's arguments `a` (N, M, re,
-// rb, rc); int s (the iteration's number), lane, wave; the macro SMALL_STAMP(k).  It defines `cur`, the pointers to the two halves of
-// the state, and `double rr`: the iteration's maximum_difference, never below numeric_limits<double>::min() (:105).
+// In scope where it is included: the items bn_small_items.inc declares (ent, ecpt, bs, cs, treg, e_mm, b_rmax, b_kmax, c_dmax, c_kmax,
+// kTermsInRegs); SmallLds L; the kernel's arguments `a` (N, M, re, rb, rc); int s (the iteration's number), lane, wave; the macro
+// SMALL_STAMP(k).  It defines `cur`, the pointers to the two halves of the state, and `double rr`: the iteration's maximum_difference, never below
+// numeric_limits<double>::min() (:105).
 const int cur = s & 1;
 const double* pi_cur = L.pi + cur * a.M;
 const double* lam_cur = L.lam + cur * a.M;
@@ -24,7 +26,7 @@ SMALL_STAMP(0);
 // ---- phase 1: entry items
 #pragma unroll
 for (int r = 0; r < ROUNDS; ++r)
-    if (r < a.re) small_entry_any<kTermsInRegs>(e_mm[r], L, pi_cur, nlam_cur, ent[r], ecpt[r], treg[r]);
+    if (r < a.re) item_entry_any<kTermsInRegs, false>(e_mm[r], L.stg, L.term, pi_cur, nlam_cur, ent[r], ecpt[r], treg[r], LdPlain{});
 SMALL_STAMP(1);
 __syncthreads();
 SMALL_STAMP(2);
@@ -40,10 +42,7 @@ for (int r = 0; r < ROUNDS; ++r) {
     // what the stores behind the sum need of the old state is requested before it
     const double old = kind == 1 ? npi_cur[out_idx] : lam_cur[out_idx];
     const bool frozen = L.frz[out_idx] != 0;
-    // The run is added strictly front to back (the reference's order): the chain of dependent additions IS the
-    // phase's critical path.  Runs are padded with zeros to the wave's common length (bn_small_plan.cpp), so a step
-    // is four loads at immediate offsets -- issued one step ahead -- and four additions, nothing else.
-    const double acc = small_run_sum(L.stg + base, b_rmax[r]);
+    const double acc = small_run_sum(L.stg + base, b_rmax[r]);   // (front to back: bn_small_dev.hpp)
     if (r == 0) SMALL_STAMP(6);
     double* buf = kind == 1 ? npi_new : lam_new;
     const double val = small_normalize(buf, on, out_idx, k, at, acc, b_kmax[r]);

@@ -1,5 +1,5 @@
-"""Networks whose nodes have five to eight parents, for the item kernels (bn_small.hip, bn_mid.hip, bn_maxprod.hip, bn_em.hip): their
-entry routine runs a wave at its largest parent count, 5 and 6 in the MM = 6 instantiation and 7 and 8 in MM = 8, and a lane with
+"""Networks whose nodes have five to eight parents, for the item kernels (bn_small.hip, bn_mid.hip, bn_maxprod.hip, bn_em.hip): the one
+entry routine they all call (item_entry, bn_small_dev.hpp) runs a wave at its largest parent count, 5 and 6 in the MM = 6 instantiation and 7 and 8 in MM = 8, and a lane with
 fewer parents loads element 0 of the pi-message array for each factor it lacks and multiplies by 1.0 instead.  Builders only, shared
 by tests/test_many_parents_refs.py (the plans, on the CPU) and tests/test_many_parents_gpu.py (the kernels)."""
 import numpy as np

@@ -275,7 +275,7 @@ def test_hot_kernels_do_not_spill(bnlib):
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "bayesiannetwork_amd", "csrc")
-    need = ["bn_sweep_u.o", "bn_resident.o", "bn_lw_kernels.o", "bn_small.o", "bn_mid.o"]
+    need = ["bn_sweep_u.o", "bn_resident.o", "bn_lw_kernels.o", "bn_small.o", "bn_mid.o", "bn_maxprod.o", "bn_em.o"]
     if not all(os.path.exists(os.path.join(csrc, f)) for f in need) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("object files / llvm tools not on this box")
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(root, "scripts", "kernel_resources.py"))
@@ -328,6 +328,21 @@ def test_hot_kernels_do_not_spill(bnlib):
             assert r["spill"] == 0 and r["scratch"] == 0, (name, r)
         else:
             assert r["spill"] <= 16, (name, r)
+    # max-product and EM in one workgroup run bp_small_kernel's text (bn_small_items.inc, bn_small_sweep.inc): its bounds
+    for obj, kernel in (("bn_maxprod.o", "mpe_small_kernel"), ("bn_em.o", "em_small_kernel")):
+        hit = {name: r for name, r in kr.kernel_resources(os.path.join(csrc, obj)).items() if kernel + "<" in name}
+        assert len(hit) == 3, (obj, sorted(hit))
+        for name, r in hit.items():
+            rounds = int(re.search(kernel + r"<(\d+)>", name).group(1))
+            assert r["vgpr"] <= 128, (name, r)
+            if rounds <= 2:
+                assert r["spill"] == 0 and r["scratch"] == 0, (name, r)
+            else:
+                assert r["spill"] <= 16, (name, r)
+    mpe_mid = {name: r for name, r in kr.kernel_resources(os.path.join(csrc, "bn_maxprod.o")).items() if "mpe_mid_kernel<" in name}
+    assert len(mpe_mid) == 6   # {1, 2, 4 rounds} x {sweep, finishing launch}
+    for name, r in mpe_mid.items():
+        assert r["vgpr"] <= 128 and r["spill"] == 0, (name, r)
 
 
 def test_small_plan_emulated_equals_oracle(bnlib, oracle_mod):

@@ -1,5 +1,6 @@
 """The item kernels on nodes with five to eight parents (the networks of tests/many_parents.py): a wave whose largest parent count is
-5 or 6 runs the entry routine's MM = 6 instantiation, 7 or 8 the MM = 8 one -- parent terms from LDS on every sweep, and a lane with
+5 or 6 runs the MM = 6 instantiation of item_entry (bn_small_dev.hpp: the one entry routine of all five kernels), 7 or 8 the MM = 8
+one -- parent terms from LDS on every sweep, and a lane with
 fewer parents than MM loads element 0 of the pi-message array for each missing factor and takes 1.0 instead.  Sum-product in one
 workgroup (bn_small.hip) and in several (bn_mid.hip) against the oracle, max-product in both forms (bn_maxprod.hip) against
 tests/maxprod_refs.py, EM (bn_em.hip) against tests/em_refs.py: all BIT FOR BIT -- beliefs, sweep counts, residual histories, both
