@@ -53,6 +53,10 @@ class EmOptions(ctypes.Structure):   # bn_em_options
                 ("prior", ctypes.c_double)]
 
 
+class JtEmOptions(ctypes.Structure):   # bn_jt_em_options
+    _fields_ = [("max_iters", ctypes.c_int32), ("tol", ctypes.c_double), ("prior", ctypes.c_double)]
+
+
 class ScoreSpec(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("ess", ctypes.c_double)]
 
@@ -119,6 +123,9 @@ SYMBOLS = [
     ("bn_jt_mpe_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, f64p, f64p, i32p, f64p]),
     ("bn_jt_mpe_run_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, f64p, f64p, i32p, f64p]),
     ("bn_jt_scales", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, f64p, ctypes.c_int32]),
+    ("bn_jt_em_expected_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, u8p, ctypes.POINTER(ctypes.c_uint64), f64p, f64p]),
+    ("bn_jt_em_fit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(JtEmOptions), f64p, f64p,
+                                    i32p, f64p, f64p, ctypes.c_int32]),
     ("bn_jt_plan_dims", ctypes.c_int, [ctypes.c_void_p, i64p]),
     ("bn_jt_plan_dump", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]),
     ("bn_set_option", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),

@@ -385,6 +385,11 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
         const int rc = em_set_option(e, name, value, &known);
         if (known) return rc;
     }
+    if (std::strncmp(name, "jt_em_", 6) == 0) {   // exact expectation-maximisation: "jt_em_scratch_cells" (bn_engine_jt_em.cpp)
+        bool known = false;
+        const int rc = jt_em_set_option(e, name, value, &known);
+        if (known) return rc;
+    }
     if (std::strncmp(name, "jt_", 3) == 0) {   // junction tree: "jt_form", "jt_scratch_cells" (bn_engine_jt.cpp)
         bool known = false;
         const int rc = jt_set_option(e, name, value, &known);
@@ -464,6 +469,11 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strncmp(name, "em_", 3) == 0) {   // expectation-maximisation: "em_eligible", "em_last_iters", ... (bn_engine_em.cpp)
         bool known = false;
         const int64_t v = em_get_info(e, name, &known);
+        if (known) return v;
+    }
+    if (std::strncmp(name, "jt_em_", 6) == 0) {   // exact expectation-maximisation: "jt_em_last_iters", ... (bn_engine_jt_em.cpp)
+        bool known = false;
+        const int64_t v = jt_em_get_info(e, name, &known);
         if (known) return v;
     }
     if (std::strncmp(name, "jt_", 3) == 0) {   // junction tree: "jt_eligible", "jt_form", "jt_cliques", ... (bn_engine_jt.cpp)

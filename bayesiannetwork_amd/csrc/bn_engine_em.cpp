@@ -90,24 +90,10 @@ int reserve(bn_engine* e, int64_t n_patterns, const bn_policy::EmPlan& plan) {
 
 // the checks of the table and of what both entry points share, in the order bn_mi355x.h gives: arguments, eligibility, device
 int check_call(bn_engine* e, int64_t n_patterns, const uint8_t* patterns, const uint64_t* counts, double bp_eps, int32_t bp_max_sweeps) {
-    if (!e) return fail(BN_ERR_ARG, "null engine");
-    if (n_patterns < 1) return fail(BN_ERR_ARG, "n_patterns must be at least 1");
-    if (!patterns) return fail(BN_ERR_ARG, "null patterns");
-    if (!counts) return fail(BN_ERR_ARG, "null counts");
+    if (int rc = em_check_table_args(e, n_patterns, patterns, counts)) return rc;
     if (std::isnan(bp_eps)) return fail(BN_ERR_ARG, "bp_eps is not a number");
     if (bp_max_sweeps < 0) return fail(BN_ERR_ARG, "bp_max_sweeps < 0");
-    const Plan& p = e->plan;
-    bool any = false;
-    for (int64_t r = 0; r < n_patterns; ++r) {
-        const uint8_t* row = patterns + r * p.n;
-        for (int32_t v = 0; v < p.n; ++v)
-            if (row[v] != kEmMissing && int32_t(row[v]) >= p.k[v])
-                return fail(BN_ERR_ARG, "pattern " + std::to_string(r) + ": state " + std::to_string(int(row[v])) + " of node " + std::to_string(v) +
-                                            " is not below its arity " + std::to_string(p.k[v]) + " (and not BN_EM_MISSING)");
-        any = any || counts[r] != 0;
-    }
-    if (!any) return fail(BN_ERR_ARG, "the table's counts sum to zero");
-    return BN_OK;
+    return em_check_table_cells(e, n_patterns, patterns, counts);
 }
 int check_engine(bn_engine* e) {
     if (e->plan.nranks > 1 || !e->small.ok) return fail(BN_ERR_STATE, not_eligible_text(e));

@@ -9,8 +9,8 @@
 // (dense) engine, the entry points and their dispatch; bn_engine_batch_paths.cpp: the five runs of a batch and what they share;
 // bn_batch_stage.hpp / .cpp: the layout of a batch's evidence staging block (no HIP either); bn_engine_shard.cpp: RCCL communicator
 // and the in-kernel exchange of sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and
-// the fit's entry points; bn_engine_mpe.cpp, bn_engine_em.cpp, bn_engine_jt.cpp: max-product, expectation-maximisation and
-// junction-tree propagation, each over a state of its own.  No CPU compute path exists in any of them: every result comes from the
+// the fit's entry points; bn_engine_mpe.cpp, bn_engine_em.cpp, bn_engine_jt.cpp, bn_engine_jt_em.cpp: max-product,
+// expectation-maximisation, junction-tree propagation and exact expectation-maximisation, each over a state of its own.  No CPU compute path exists in any of them: every result comes from the
 // kernels.
 #ifndef BN_ENGINE_INTERNAL_HPP
 #define BN_ENGINE_INTERNAL_HPP
@@ -239,6 +239,33 @@ struct JtState {
     int32_t n_sets = 0, last_launches = 0;
     int64_t last_kernel_ns = 0;         // option "timing": HIP events around the run's launches
     std::vector<double> scales;         // [n_sets][nc]
+};
+
+// Exact expectation-maximisation (bn_engine_jt_em.cpp, jt_em_kernel of bn_jt.hip): the family tables on the device, its own theta
+// and base potentials, the table, the scratch of family posteriors (and, in form 2, of the rows' states), the sums -- allocated at
+// the first call.  It reads the junction tree's plan and item tables; nothing else of the engine is read or written, and nothing
+// here by any other call family.
+struct JtEmState {
+    int64_t scratch_cells = bn_policy::kJtEmScratchCells;   // option "jt_em_scratch_cells": doubles of the posteriors' scratch array
+    bool ready = false;                 // family tables uploaded, theta, potentials and sums allocated
+    DeviceBuf<JtFamily> d_families;
+    DeviceBuf<int32_t> d_f_node, d_f_base, d_f_res;
+    DeviceBuf<double> d_theta, d_psi0;  // [entries] flat; [pot_cells] the base potentials of theta
+    DeviceBuf<double> d_E, d_partial;   // [entries] the sum, and the 256-block in hand
+    DeviceBuf<unsigned long long> d_words;   // [0] skipped families, [1] L (a double), [2] delta's bit pattern
+    DeviceBuf<uint8_t> d_patterns;      // the table of the call
+    DeviceBuf<unsigned long long> d_counts;
+    DeviceBuf<double> d_loglik;         // [patterns] of the last E-step
+    DeviceBuf<int32_t> d_skipped;       // [patterns] of the last E-step
+    int64_t cap_patterns = 0;
+    DeviceBuf<double> d_b;              // [rows of a launch][entries]
+    int64_t cap_b = 0;
+    DeviceBuf<double> d_scratch;        // form 2: [rows of a launch][state_cells]
+    int64_t cap_scratch = 0;
+    EventOwner ev[3];                   // E-step begins, E-step ends, M-step ends
+    // the last call
+    int32_t last_iters = 0, last_form = 0;
+    int64_t skipped = 0, estep_ns = 0, mstep_ns = 0, last_launches = 0;
 };
 
 struct bn_engine {
@@ -477,6 +504,7 @@ struct bn_engine {
     MpeState mpe;
     EmState em;
     JtState jt;
+    JtEmState jt_em;
 };
 
 
@@ -615,6 +643,33 @@ int64_t em_get_info(bn_engine* e, const char* name, bool* known);
 int jt_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t jt_get_info(bn_engine* e, const char* name, bool* known);
 void jt_cpt_reloaded(bn_engine* e);    // bn_reload_cpt: the base potentials are computed again at the next run
+void jt_ensure_plan(bn_engine* e);     // the plan, built once (also on engines without a device)
+int jt_ensure_tables(bn_engine* e);    // the plan's item tables on the device, once (not the base potentials)
+// the "jt_em_*" names (bn_engine_jt_em.cpp)
+int jt_em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
+int64_t jt_em_get_info(bn_engine* e, const char* name, bool* known);
+// The table of bn_em_* and bn_jt_em_*: its arguments, then (behind whatever else the entry point checks of its arguments) its cells
+inline int em_check_table_args(const bn_engine* e, int64_t n_patterns, const uint8_t* patterns, const uint64_t* counts) {
+    if (!e) return fail(BN_ERR_ARG, "null engine");
+    if (n_patterns < 1) return fail(BN_ERR_ARG, "n_patterns must be at least 1");
+    if (!patterns) return fail(BN_ERR_ARG, "null patterns");
+    if (!counts) return fail(BN_ERR_ARG, "null counts");
+    return BN_OK;
+}
+inline int em_check_table_cells(const bn_engine* e, int64_t n_patterns, const uint8_t* patterns, const uint64_t* counts) {
+    const Plan& p = e->plan;
+    bool any = false;
+    for (int64_t r = 0; r < n_patterns; ++r) {
+        const uint8_t* row = patterns + r * p.n;
+        for (int32_t v = 0; v < p.n; ++v)
+            if (row[v] != kEmMissing && int32_t(row[v]) >= p.k[v])
+                return fail(BN_ERR_ARG, "pattern " + std::to_string(r) + ": state " + std::to_string(int(row[v])) + " of node " + std::to_string(v) +
+                                            " is not below its arity " + std::to_string(p.k[v]) + " (and not BN_EM_MISSING)");
+        any = any || counts[r] != 0;
+    }
+    if (!any) return fail(BN_ERR_ARG, "the table's counts sum to zero");
+    return BN_OK;
+}
 }  // namespace bn_eng
 
 #endif  // BN_ENGINE_INTERNAL_HPP

@@ -27,8 +27,8 @@ void ensure_plan(bn_engine* e) {
 
 std::string refusal(const bn_engine* e) { return "not eligible for junction-tree propagation: " + e->jt.plan.why; }
 
-// the item tables, once; the base potentials, once per set of CPTs
-int ensure_device(bn_engine* e) {
+// the item tables, once
+int ensure_tables(bn_engine* e) {
     JtState& j = e->jt;
     const JtPlan& P = j.plan;
     hipStream_t s = e->stream;
@@ -56,6 +56,15 @@ int ensure_device(bn_engine* e) {
         j.uploaded = true;
         j.psi_ready = false;
     }
+    return BN_OK;
+}
+
+// ... and the base potentials, once per set of CPTs
+int ensure_device(bn_engine* e) {
+    JtState& j = e->jt;
+    const JtPlan& P = j.plan;
+    hipStream_t s = e->stream;
+    if (int r = ensure_tables(e)) return r;
     if (!j.psi_ready) {
         const size_t entries = size_t(e->plan.cpt_off[e->plan.n]);
         if (entries) HIPCHK(hipMemcpyAsync(j.d_cpt, e->plan.cpt_flat.data(), entries * sizeof(double), hipMemcpyHostToDevice, s));
@@ -282,3 +291,5 @@ int64_t bn_eng::jt_get_info(bn_engine* e, const char* name, bool* known) {
 }
 
 void bn_eng::jt_cpt_reloaded(bn_engine* e) { e->jt.psi_ready = false; }
+void bn_eng::jt_ensure_plan(bn_engine* e) { ensure_plan(e); }
+int bn_eng::jt_ensure_tables(bn_engine* e) { return ensure_tables(e); }

@@ -330,4 +330,18 @@ EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c) {
     return k;
 }
 
+// Exact expectation-maximisation: em_plan's rows, and in form 2 at most the state slices the junction tree's scratch budget holds.
+EmPlan jt_em_plan(int64_t n_patterns, int32_t entries, int64_t b_scratch_cells, int form, int64_t state_cells, int64_t state_scratch_cells) {
+    EmPlan p = em_plan(n_patterns, entries, b_scratch_cells);
+    if (form == 2) {
+        const int64_t slices = std::max<int64_t>(1, state_scratch_cells / std::max<int64_t>(state_cells, 1));
+        if (slices < p.chunk) {
+            p.chunk = int32_t(slices);
+            p.n_chunks = (n_patterns + p.chunk - 1) / p.chunk;
+            p.scratch = int64_t(p.chunk) * entries;
+        }
+    }
+    return p;
+}
+
 }  // namespace bn_policy

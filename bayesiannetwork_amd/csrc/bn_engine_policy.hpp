@@ -169,6 +169,13 @@ struct EmChunk {
 EmPlan em_plan(int64_t n_patterns, int32_t entries, int64_t scratch_cells);
 EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c);
 
+// ---- exact expectation-maximisation (bn_jt_em_*, bn_jt.hpp): the rows of one launch of the junction-tree E-step.  As em_plan under
+// option "jt_em_scratch_cells" (the launch's family posteriors); in form 2 (jt_form: the per-row state in device scratch) also no
+// more rows than state slices fit option "jt_scratch_cells", at least one.  em_chunk cuts the table as for em_plan: launch edges
+// need not fall on block edges.
+constexpr int64_t kJtEmScratchCells = kEmScratchCells;
+EmPlan jt_em_plan(int64_t n_patterns, int32_t entries, int64_t b_scratch_cells, int form, int64_t state_cells, int64_t state_scratch_cells);
+
 }  // namespace bn_policy
 
 #endif  // BN_ENGINE_POLICY_HPP

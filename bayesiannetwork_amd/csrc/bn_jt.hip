@@ -1,5 +1,7 @@
 // bn_jt.hip -- junction-tree propagation on gfx950: the base potentials, and the two-pass run of one evidence set per workgroup,
-// as a sum run (jt_kernel: marginals) and as a max run (jt_mpe_kernel: exact MPE) (rules: bn_jt.hpp; item tables: bn_jt_plan.hpp).  The same item code runs over LDS (form 1) and over the set's slice of device
+// as a sum run (jt_kernel: marginals), as a max run (jt_mpe_kernel: exact MPE) and as the E-step of exact expectation-maximisation
+// (jt_em_kernel: the sum run of a pattern row and its family posteriors, with the small kernels of its sums and its M-step)
+// (rules: bn_jt.hpp; item tables: bn_jt_plan.hpp).  The same item code runs over LDS (form 1) and over the set's slice of device
 // scratch (form 2): the kernel is a template over where the state lives, so the compiler sees the address space.  A workgroup
 // reads and writes its own state only; every phase ends in __syncthreads(), and no lane waits on anything else.
 #include <hip/hip_runtime.h>
@@ -44,45 +46,10 @@ __device__ inline double sum_two_level(P tab, const int32_t* res, int cnt) {
     return total;
 }
 
-extern __shared__ double jt_lds[];
-
-template <bool kLds>
-__global__ void __launch_bounds__(kLds ? kJtLdsThreads : kJtMemThreads) jt_kernel(JtArgs a) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int slot = blockIdx.x, set = a.set_base + slot;
-    double* const st = kLds ? jt_lds : a.scratch + size_t(slot) * size_t(a.state_cells);
-    double* const pot = st;
-    double* const sep = pot + a.pot_cells;
-    double* const marg = sep + a.sep_cells;
-    double* const scl = marg + a.N;
-    int32_t* const evs = a.ev_slot + size_t(slot) * size_t(a.n);
-    const int32_t* meta = a.ev_meta + 8 * set;
-    const int ne = meta[0];
-    const int32_t* ev_node = a.ev_node + meta[1];
-    const int32_t* ev_off = a.ev_off + meta[2];
-    const double* ev_val = a.ev_val + meta[3];
-
-    // where every node's evidence vector starts
-    for (int v = tid; v < a.n; v += nt) evs[v] = -1;
-    __syncthreads();
-    for (int j = tid; j < ne; j += nt) evs[ev_node[j]] = ev_off[j];
-    __syncthreads();
-    // psi = psi0 x the evidence of the clique's home nodes, ascending node id
-    for (int g = tid; g < a.pot_cells; g += nt) {
-        const JtClique q = a.cliques[a.ent_clique[g]];
-        const int e = g - q.pot_off;
-        double v = a.psi0[g];
-        for (int h = q.home_lo; h < q.home_hi; ++h) {
-            const int node = a.home_nodes[h];
-            const int at = evs[node];
-            if (at >= 0) {
-                const JtNode nd = a.nodes[node];
-                v *= ev_val[at + (e / nd.stride) % nd.k];
-            }
-        }
-        pot[g] = v;
-    }
-    __syncthreads();
+// collect and distribute of a sum run (bn_jt.hpp) over the state of one evidence set: the one text of jt_kernel and jt_em_kernel.
+// In: the potentials, a barrier behind them.  Out: every clique's table proportional to P(clique, e), the scales; a barrier behind.
+template <class Args, class P>
+__device__ __forceinline__ void jt_walk(const Args& a, P pot, P sep, P scl, const int tid, const int nt) {
     // ---- collect: deepest level first
     for (int l = a.nlev - 1; l >= 0; --l) {
         const JtLevel L = a.levels[l];
@@ -134,6 +101,48 @@ __global__ void __launch_bounds__(kLds ? kJtLdsThreads : kJtMemThreads) jt_kerne
         }
         __syncthreads();
     }
+}
+
+extern __shared__ double jt_lds[];
+
+template <bool kLds>
+__global__ void __launch_bounds__(kLds ? kJtLdsThreads : kJtMemThreads) jt_kernel(JtArgs a) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int slot = blockIdx.x, set = a.set_base + slot;
+    double* const st = kLds ? jt_lds : a.scratch + size_t(slot) * size_t(a.state_cells);
+    double* const pot = st;
+    double* const sep = pot + a.pot_cells;
+    double* const marg = sep + a.sep_cells;
+    double* const scl = marg + a.N;
+    int32_t* const evs = a.ev_slot + size_t(slot) * size_t(a.n);
+    const int32_t* meta = a.ev_meta + 8 * set;
+    const int ne = meta[0];
+    const int32_t* ev_node = a.ev_node + meta[1];
+    const int32_t* ev_off = a.ev_off + meta[2];
+    const double* ev_val = a.ev_val + meta[3];
+
+    // where every node's evidence vector starts
+    for (int v = tid; v < a.n; v += nt) evs[v] = -1;
+    __syncthreads();
+    for (int j = tid; j < ne; j += nt) evs[ev_node[j]] = ev_off[j];
+    __syncthreads();
+    // psi = psi0 x the evidence of the clique's home nodes, ascending node id
+    for (int g = tid; g < a.pot_cells; g += nt) {
+        const JtClique q = a.cliques[a.ent_clique[g]];
+        const int e = g - q.pot_off;
+        double v = a.psi0[g];
+        for (int h = q.home_lo; h < q.home_hi; ++h) {
+            const int node = a.home_nodes[h];
+            const int at = evs[node];
+            if (at >= 0) {
+                const JtNode nd = a.nodes[node];
+                v *= ev_val[at + (e / nd.stride) % nd.k];
+            }
+        }
+        pot[g] = v;
+    }
+    __syncthreads();
+    jt_walk(a, pot, sep, scl, tid, nt);
     // ---- read-out
     for (int i = tid; i < a.N; i += nt) {
         const JtNode nd = a.nodes[a.elem_node[i]];
@@ -159,6 +168,127 @@ __global__ void __launch_bounds__(kLds ? kJtLdsThreads : kJtMemThreads) jt_kerne
     }
     double* const out = a.scales + size_t(set) * size_t(a.nc);
     for (int c = tid; c < a.nc; c += nt) out[c] = scl[c];
+}
+
+// ---- exact expectation-maximisation (bn_jt.hpp, "Exact EM"): the sum run of one pattern row -- evidence from the row's bytes --
+// and, from the tables distribute leaves, the family posteriors of every CPT into the launch's slice of `b`.  The state is that of
+// jt_kernel; the region of the unnormalised marginals holds the n family totals.  No atomics, nothing shared between workgroups.
+template <bool kLds>
+__global__ void __launch_bounds__(kLds ? kJtLdsThreads : kJtMemThreads) jt_em_kernel(JtEmArgs a) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int row = blockIdx.x;
+    double* const st = kLds ? jt_lds : a.scratch + size_t(row) * size_t(a.state_cells);
+    double* const pot = st;
+    double* const sep = pot + a.pot_cells;
+    double* const tot = sep + a.sep_cells;   // [n] of the region's N
+    double* const scl = tot + a.N;
+    const uint8_t* const pat = a.patterns + size_t(row) * size_t(a.n);
+
+    // psi = psi0 x the one-hot vectors of the clique's observed home nodes, ascending node id
+    for (int g = tid; g < a.pot_cells; g += nt) {
+        const JtClique q = a.cliques[a.ent_clique[g]];
+        const int e = g - q.pot_off;
+        double v = a.psi0[g];
+        for (int h = q.home_lo; h < q.home_hi; ++h) {
+            const int node = a.home_nodes[h];
+            const int cell = pat[node];
+            if (cell != kJtEmMissing) {
+                const JtNode nd = a.nodes[node];
+                v *= (e / nd.stride) % nd.k == cell ? 1.0 : 0.0;
+            }
+        }
+        pot[g] = v;
+    }
+    __syncthreads();
+    jt_walk(a, pot, sep, scl, tid, nt);
+    // ---- family read-out: u[q], flat CPT order
+    double* const out = a.b + size_t(row) * size_t(a.S);
+    for (int q = tid; q < a.S; q += nt) {
+        const JtFamily F = a.families[a.f_node[q]];
+        out[q] = sum_two_level(pot + F.pot_off + a.f_base[q], a.f_res + F.res_off, F.res_cnt);
+    }
+    __syncthreads();
+    // s_v: one lane per node, its entries in flat order
+    for (int v = tid; v < a.n; v += nt) {
+        const JtFamily F = a.families[v];
+        const double* u = out + F.cpt_lo;
+        double total = 0.0;
+        for (int r = 0; r < F.cpt_cnt; r += kJtRun) {
+            const int hi = r + kJtRun < F.cpt_cnt ? r + kJtRun : F.cpt_cnt;
+            double run = 0.0;
+            for (int t = r; t < hi; ++t) run += u[t];
+            total += run;
+        }
+        tot[v] = total;
+    }
+    __syncthreads();
+    for (int q = tid; q < a.S; q += nt) {
+        const double s = tot[a.f_node[q]];
+        out[q] = s > 0.0 ? out[q] / s : 0.0;   // false for zero and for NaN: the family contributes nothing
+    }
+    // the row's skipped families and log-likelihood: the first wave, reduced across its lanes (no stated order)
+    if (tid < 64) {
+        int skipped = 0;
+        for (int v = tid; v < a.n; v += 64) skipped += tot[v] > 0.0 ? 0 : 1;
+        double ll = 0.0;
+        for (int c = tid; c < a.nc; c += 64) ll += log(scl[c]);
+        for (int off = 32; off > 0; off >>= 1) {
+            skipped += __shfl_down(skipped, off, 64);
+            ll += __shfl_down(ll, off, 64);
+        }
+        if (tid == 0) {
+            a.skipped[row] = skipped;
+            a.loglik[row] = ll;
+        }
+    }
+}
+
+// L = sum_p (count_p > 0 ? double(count_p) x ll_p : 0.0) and the skipped families of one E-step: one workgroup over the table
+__global__ void __launch_bounds__(256) jt_em_total_kernel(JtEmTotalArgs a) {
+    __shared__ double s_l[256];
+    __shared__ unsigned long long s_k[256];
+    const int tid = threadIdx.x;
+    double l = 0.0;
+    unsigned long long k = 0;
+    for (int64_t p = tid; p < a.n_patterns; p += 256) {
+        const unsigned long long c = a.counts[p];
+        if (c > 0) l += double(c) * a.loglik[p];
+        k += (unsigned long long)a.skipped[p];
+    }
+    s_l[tid] = l;
+    s_k[tid] = k;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) { s_l[tid] += s_l[tid + h]; s_k[tid] += s_k[tid + h]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *a.L = s_l[0];
+        *a.skipped_total += s_k[0];
+    }
+}
+
+// the M-step of bn_em.hpp (em_mstep_kernel's arithmetic) on the flat array alone: one thread per CPT entry
+__global__ void __launch_bounds__(256) jt_em_mstep_kernel(JtEmMstepArgs a) {
+    const int q = int(blockIdx.x * blockDim.x + threadIdx.x);
+    double d = 0.0;
+    if (q < a.S) {
+        const JtFamily F = a.families[a.f_node[q]];
+        const int k = a.nodes[a.f_node[q]].k;
+        const int first = F.cpt_lo + (q - F.cpt_lo) / k * k;
+        double tot = 0.0;
+        for (int i = 0; i < k; ++i) tot += a.E[first + i] + a.prior;
+        const double th = tot > 0.0 ? (a.E[q] + a.prior) / tot : 1.0 / double(k);
+        d = fabs(th - a.theta[q]);
+        a.theta[q] = th;
+    }
+    // md = (md < d) ? d : md from +0.0: a NaN never enters; the bit patterns of the rest order like the values
+    unsigned long long bits = (unsigned long long)__double_as_longlong(0.0 < d ? d : 0.0);
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(bits, off, 64);
+        bits = bits < o ? o : bits;
+    }
+    if ((threadIdx.x & 63) == 0 && bits) atomicMax(a.delta_bits, bits);
 }
 
 // ---- max-propagation with backtracking (bn_jt.hpp, "Exact MPE"): the walk of jt_kernel with every sum replaced by the max fold,
@@ -351,6 +481,29 @@ int launch_jt(const JtArgs& a, int form, int kind, int n_sets, void* stream) {
         if (form == 1) hipLaunchKernelGGL(jt_mpe_kernel<true>, dim3(n_sets), dim3(kJtLdsThreads), lds, s, a);
         else hipLaunchKernelGGL(jt_mpe_kernel<false>, dim3(n_sets), dim3(kJtMemThreads), 0, s, a);
     }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : int(e);
+}
+
+int launch_jt_em(const JtEmArgs& a, int form, int n_rows, void* stream) {
+    (void)hipGetLastError();
+    hipStream_t s = (hipStream_t)stream;
+    if (form == 1) hipLaunchKernelGGL(jt_em_kernel<true>, dim3(n_rows), dim3(kJtLdsThreads), size_t(a.state_cells) * sizeof(double), s, a);
+    else hipLaunchKernelGGL(jt_em_kernel<false>, dim3(n_rows), dim3(kJtMemThreads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : int(e);
+}
+
+int launch_jt_em_total(const JtEmTotalArgs& a, void* stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(jt_em_total_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : int(e);
+}
+
+int launch_jt_em_mstep(const JtEmMstepArgs& a, void* stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(jt_em_mstep_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : int(e);
 }

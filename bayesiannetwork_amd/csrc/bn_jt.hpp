@@ -42,6 +42,24 @@
 //     disturbed by the rounding of the ratio, and the pick of a level rides the phase that computes the level's ratios (it needs
 //     pick[parent] of the phase before only), so decoding adds no barrier.  states[v] = (pick[home[v]] / stride_v) % k_v.
 //     With P(e) = 0 the states are what the rule gives: meaningless, but pinned by the restatement.
+//
+// Exact EM (bn_jt_em_expected_counts, bn_jt_em_fit, jt_em_kernel): bn_em.hpp's table, sums, M-step and loop with the E-step taken
+// from this propagation instead of loopy belief propagation -- exact wherever the tree fits, not on polytrees only.  Restated by
+// tests/jtem_refs.py; E, theta after every iteration, the deltas and the skipped count are equal bit for bit.
+//   The table: patterns [P][n] uint8, counts [P] uint64, 255 for a cell that is not observed (bn_em.hpp).
+//   Per iteration the base potentials are computed from the current theta (jt_base_kernel), into an array the EM state owns.
+//   Per row: psi_c[e] = psi0_c[e] x, for every OBSERVED node whose home is c in ascending node id, 1.0 where the node's digit in e
+//     equals the cell and 0.0 elsewhere -- the bits of bn_jt_run with a one-hot vector.  Collect and distribute as above.
+//   Family read-out: node v's CPT lies in clique c = cpt_clique[v], which holds pa(v) and v.  For a flat CPT entry q of v (first
+//     parent most significant, own state last): u[q] = two-level sum of the entries of clique c whose digits match q, in ascending
+//     entry index; s_v = two-level sum of u[q] over v's entries in flat order; b[q] = u[q] / s_v where s_v > 0.  Where `s_v > 0` is
+//     false (zero or NaN: the row has probability 0 under theta in v's tree) the family contributes nothing (b = 0.0) and is counted.
+//     A fully observed family has one non-zero u, so b is exactly 1.0: on a complete table with theta > 0, E is the integer counts.
+//   Row log-likelihood: ll_p = the sum of log(scale_c) over the cliques, -inf when a factor is 0; computed on the device (its log
+//     is not libm's) and added in no stated order: the one quantity that is not pinned bit for bit.
+//     L = sum_p (count_p > 0 ? double(count_p) x ll_p : 0.0), reported per iteration; it does not steer the loop.
+//   E[q] = sum_p double(count_p) x b_p[q] in bn_em.hpp's block-of-256 order (em_accumulate_kernel); the M-step, delta and the stop
+//     rule are bn_em.hpp's, bit for bit.
 #ifndef BN_JT_HPP
 #define BN_JT_HPP
 #include <cstddef>
@@ -95,6 +113,59 @@ struct JtBaseArgs {
 };
 
 int launch_jt_base(const JtBaseArgs& a, void* stream);
+
+// ---- exact EM: one workgroup per pattern row of the launch (blockIdx.x), the state in LDS (form 1) or in slice blockIdx.x of scratch
+constexpr int kJtEmMissing = 255;   // BN_EM_MISSING
+struct JtEmArgs {
+    int32_t n, N, nc, nlev;
+    int32_t pot_cells, sep_cells, state_cells;
+    int32_t S;                      // CPT entries
+    const JtClique* cliques;
+    const JtLevel* levels;
+    const JtNode* nodes;
+    const int32_t* ent_clique;
+    const int32_t* dn_map;
+    const int32_t* sep_clique;
+    const int32_t* c_base;
+    const int32_t* p_base;
+    const int32_t* c_res;
+    const int32_t* p_res;
+    const int32_t* up_map;
+    const int32_t* home_nodes;
+    const JtFamily* families;       // [n]
+    const int32_t* f_node;          // [S]
+    const int32_t* f_base;          // [S]
+    const int32_t* f_res;
+    const double* psi0;             // [pot_cells] of the current theta
+    const uint8_t* patterns;        // the launch's rows, [rows][n]
+    double* scratch;                // form 2: [rows][state_cells]
+    double* b;                      // [rows][S] family posteriors, flat CPT order
+    double* loglik;                 // [rows] of the launch
+    int32_t* skipped;               // [rows] families with s_v not > 0
+};
+int launch_jt_em(const JtEmArgs& a, int form, int n_rows, void* stream);
+
+struct JtEmTotalArgs {
+    int64_t n_patterns;
+    const unsigned long long* counts;
+    const double* loglik;           // [n_patterns]
+    const int32_t* skipped;         // [n_patterns]
+    double* L;                      // written
+    unsigned long long* skipped_total;   // added to
+};
+int launch_jt_em_total(const JtEmTotalArgs& a, void* stream);
+
+struct JtEmMstepArgs {
+    int32_t S;
+    double prior;
+    const double* E;                // [S]
+    const JtFamily* families;
+    const JtNode* nodes;
+    const int32_t* f_node;
+    double* theta;                  // [S] in: the current tables, out: the new ones
+    unsigned long long* delta_bits; // max |theta_new - theta|, bit pattern of a non-negative double (zeroed by the host)
+};
+int launch_jt_em_mstep(const JtEmMstepArgs& a, void* stream);
 // form 1: state in LDS; form 2: in a.scratch.  One workgroup per set.  kind: kJtSum (jt_kernel) or kJtMax (jt_mpe_kernel).
 int launch_jt(const JtArgs& a, int form, int kind, int n_sets, void* stream);
 

@@ -2,6 +2,7 @@
 #include "bn_jt_plan.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <set>
 #include <tuple>
@@ -374,6 +375,36 @@ void build_jt_plan(int32_t n, const int32_t* k, const int32_t* in_ptr, const int
             P.asg.push_back(a);
         }
         P.asg_ptr.push_back(int32_t(P.asg.size()));
+    }
+    // the families: per flat CPT entry (first parent most significant, own state last) the first term of its sum over the rest of
+    // the clique, per node the offsets of the other terms -- the clique's variables outside the family, so ascending entry index
+    if (cpt_off[n] > int64_t(INT32_MAX)) return;
+    P.families.assign(size_t(n), JtFamily());
+    P.f_node.resize(size_t(cpt_off[n]));
+    P.f_base.resize(size_t(cpt_off[n]));
+    for (int32_t v = 0; v < n; ++v) {
+        const int32_t c = P.cpt_clique[v];
+        const std::vector<int32_t> cs = strides_of(cv[c], k);
+        std::vector<int32_t> members(in_idx + in_ptr[v], in_idx + in_ptr[v + 1]), weight, rest, rest_w;
+        members.push_back(v);
+        for (int32_t u : members) weight.push_back(cs[size_t(std::lower_bound(cv[c].begin(), cv[c].end(), u) - cv[c].begin())]);
+        int64_t rest_size = 1;
+        for (size_t i = 0; i < cv[c].size(); ++i)
+            if (std::find(members.begin(), members.end(), cv[c][i]) == members.end()) {
+                rest.push_back(cv[c][i]);
+                rest_w.push_back(cs[i]);
+                rest_size *= k[cv[c][i]];
+            }
+        JtFamily& F = P.families[size_t(v)];
+        F.pot_off = P.cliques[c].pot_off;
+        F.cpt_lo = int32_t(cpt_off[v]);
+        F.cpt_cnt = int32_t(cpt_off[v + 1] - cpt_off[v]);
+        F.res_off = int32_t(P.f_res.size());
+        F.res_cnt = int32_t(rest_size);
+        std::fill(P.f_node.begin() + F.cpt_lo, P.f_node.begin() + F.cpt_lo + F.cpt_cnt, v);
+        project(members, k, weight, P.f_base.data() + F.cpt_lo, F.cpt_cnt);
+        P.f_res.resize(size_t(F.res_off) + size_t(rest_size));
+        project(rest, k, rest_w, P.f_res.data() + F.res_off, rest_size);
     }
 }
 

@@ -10,6 +10,8 @@
 //   CPT of node v   -> the clique that absorbed the elimination clique of v's earliest-eliminated family member (it holds the family);
 //   home of node v  -> the clique with the smallest table among those that hold v (ties: lowest clique id): it receives v's evidence
 //                      vector and is where v's marginal is read.
+// Exact expectation-maximisation (bn_jt.hpp, "Exact EM") reads every family's posterior from the clique of its CPT: the family tables
+// below (families, f_node, f_base, f_res; tests/cpp/test_jt_em_plan.cpp walks them).
 // Limits (facts of the plan, `ok` / `why`): an elimination clique of more than kJtMaxClique entries stops the planner where it
 // meets it; a per-set state above the scratch budget makes the network ineligible too (jt_apply_budget: re-checked when the option
 // changes, nothing is rebuilt).
@@ -42,6 +44,9 @@ struct JtLevel { int32_t c_lo, c_hi, pot_lo, pot_hi, sep_lo, sep_hi, pad0_, pad1
 struct JtNode { int32_t home, stride, k, bel_off; };   // digit of the node in entry e of its home clique: (e / stride) % k
 struct JtFam { int32_t stride, k, cstride; };           // a family member: its digit in the clique entry, times cstride into the CPT
 struct JtAsg { int64_t cpt_off; int32_t node, fam_lo, fam_hi, pad_; };
+// a node's family inside the clique of its CPT (exact EM's read-out, bn_jt.hpp): flat CPT entries [cpt_lo, cpt_lo + cpt_cnt), the
+// clique's potential at pot_off, f_res[res_off .. res_off + res_cnt): the offsets of one entry's terms from its first, ascending
+struct JtFamily { int32_t pot_off, cpt_lo, cpt_cnt, res_off, res_cnt, pad_; };
 
 struct JtPlan {
     bool built = false;             // the structure is complete (`why` may still name the scratch budget)
@@ -65,6 +70,10 @@ struct JtPlan {
     std::vector<int32_t> asg_ptr;               // [nc + 1] the CPTs of a clique, ascending node id
     std::vector<JtAsg> asg;
     std::vector<JtFam> fam;
+    // family tables, in the style of c_base / c_res: present where the flat CPT array has fewer than 2^31 entries (else empty)
+    std::vector<JtFamily> families;             // [n]
+    std::vector<int32_t> f_node, f_base;        // [CPT entries]: the entry's node; the offset, inside the clique, of its sum's first term
+    std::vector<int32_t> f_res;
 };
 
 // state of one evidence set, in doubles: potentials | separators | unnormalised marginals [N] | scales [nc]

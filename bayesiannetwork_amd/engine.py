@@ -327,6 +327,38 @@ class Engine:
             self.reload_cpt(cpt)
         return cpt, int(iters.value), hist[:iters.value].copy()
 
+    # ---- exact expectation-maximisation: the E-step on the junction tree (bn_jt_em_*) ------------
+    def jt_em_expected_counts(self, patterns, counts):
+        """bn_jt_em_expected_counts: ONE exact E-step under the engine's current tables; the table is em_expected_counts'.
+        Returns (E [entries], the expected family counts in the flat CPT layout; row_loglik [P], log P(e_p) of every row, -inf
+        where the row has probability 0).  Exact on every network the junction tree takes (info("jt_eligible"))."""
+        patterns, counts = self._em_table(patterns, counts)
+        E = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        ll = np.zeros(max(patterns.shape[0], 1), dtype=np.float64)
+        _lib.check(_lib.lib().bn_jt_em_expected_counts(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64),
+                                                       _p(E, ctypes.c_double), _p(ll, ctypes.c_double)))
+        return E, ll[:patterns.shape[0]]
+
+    def jt_em_fit(self, patterns, counts, max_iters: int = 100, tol: float = 1e-6, prior: float = 0.0, cpt_init=None, reload: bool = False):
+        """bn_jt_em_fit: em_fit with the exact E-step.  Returns (cpt [entries], iterations, delta_history [iterations],
+        loglik_history [iterations]: the observed-data log-likelihood of the table under the tables each iteration started
+        from).  The engine's tables are not touched unless reload=True, which applies the result with reload_cpt()."""
+        patterns, counts = self._em_table(patterns, counts)
+        opt = _lib.JtEmOptions(int(max_iters), float(tol), float(prior))
+        init = None if cpt_init is None else np.ascontiguousarray(cpt_init, dtype=np.float64)
+        if init is not None and init.shape[0] != int(self.model.cpt_off[-1]):
+            raise ValueError("cpt_init must have one value per CPT entry")
+        cpt = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        cap = max(1, min(int(max_iters), 10000))
+        hist, lls = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.float64)
+        iters = ctypes.c_int32(0)
+        _lib.check(_lib.lib().bn_jt_em_fit(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), ctypes.byref(opt),
+                                           None if init is None else _p(init, ctypes.c_double), _p(cpt, ctypes.c_double), ctypes.byref(iters),
+                                           _p(hist, ctypes.c_double), _p(lls, ctypes.c_double), cap))
+        if reload:
+            self.reload_cpt(cpt)
+        return cpt, int(iters.value), hist[:iters.value].copy(), lls[:iters.value].copy()
+
     def bp_stats(self) -> dict:
         st = _lib.BpStats()
         _lib.check(_lib.lib().bn_bp_last_stats(self._h, ctypes.byref(st)))
@@ -584,6 +616,14 @@ def em_fit(model: FlatModel, patterns, counts, device: int = _lib.BN_DEVICE_CURR
         return eng.em_fit(patterns, counts, **kw)
 
 
+def jt_em_fit(model: FlatModel, patterns, counts, device: int = _lib.BN_DEVICE_CURRENT, **kw):
+    """Engine.jt_em_fit on an engine made for the call: (cpt, iterations, delta_history, loglik_history), starting from model.cpt
+    unless cpt_init is given."""
+    kw.pop("reload", None)
+    with Engine(model, device=device) as eng:
+        return eng.jt_em_fit(patterns, counts, **kw)
+
+
 class Sampler:
     """Mirror of bn::sampler (reference bayesian/sampler.hpp:17-215): a table of joint patterns with
     occurrence counts, and make_cpt() fitting every CPT of a structure to it on the GPU."""
@@ -804,6 +844,14 @@ class JunctionTree:
         the decoded assignment attains the maximum.  ``self.last["max_marginals"]`` holds the max-marginals of the call."""
         self.last = self.engine.jt_mpe_run(self._evidence(precondition))
         return self.last["states"], self.last["log_p"]
+
+    def em_fit(self, patterns, counts, **kw):
+        """Engine.jt_em_fit on this functor's engine: CPTs fitted from a table with unobserved cells (255), the E-step exact.
+        (cpt, iterations, delta_history, loglik_history); ``reload=True`` makes the fitted tables those of later calls."""
+        out = self.engine.jt_em_fit(patterns, counts, **kw)
+        if kw.get("reload"):
+            self.model = self.engine.model
+        return out
 
 
 class LikelihoodWeighting:

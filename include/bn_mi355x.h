@@ -364,6 +364,58 @@ int bn_jt_mpe_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int3
 int bn_jt_mpe_run_batch(bn_engine *eng, int32_t n_sets, const int32_t *ne, const int32_t *ev_node, const int32_t *ev_off,
                         const double *ev_val, double *max_marginals_out, int32_t *states_out, double *log_p_out);
 
+/*
+ * Exact EM: bn_em_fit with its E-step taken from the junction tree -- the pair of bn_em_fit as bn_jt_run is the pair of bn_bp_run.
+ * bn_em_fit's family posteriors come from loopy belief propagation and are P(x_v, pa(v) | e) on polytrees only; here they are
+ * exact on every network the junction tree takes.  One workgroup per pattern row, the row's state in LDS (form 1) or device
+ * scratch (form 2), as bn_jt_run_batch.  All in fp64; every sum but the row log-likelihood has a stated order that depends on
+ * the plan only (tests/jtem_refs.py restates it: E, the tables after every iteration, the deltas and the skipped count are
+ * equal bit for bit).
+ *   The table is bn_em_fit's: patterns [n_patterns][n_nodes] uint8, counts [n_patterns] uint64, BN_EM_MISSING for a cell that is
+ *   not observed; rows may be fully observed, fully missing or have count 0.  Its checks, their texts and their order are
+ *   bn_em_fit's (without bp_eps and bp_max_sweeps).
+ * E-step per row, under the current tables theta: the base potentials are computed from theta once per iteration, into an array of
+ *   the call's own; an observed node multiplies the entries of its home clique by 1.0 where its digit equals the cell and by 0.0
+ *   elsewhere (ascending node id) -- the bits of bn_jt_run with a one-hot vector; collect and distribute as bn_jt_run.
+ * Family read-out: node v's CPT lies in the clique cpt_clique[v] (bn_jt_plan_dump), which holds v and its parents.  For a flat CPT
+ *   entry q of v (first parent most significant, own state last): u[q] = two-level sum (runs of 64) of that clique's entries whose
+ *   digits match q, in ascending entry index; s_v = two-level sum of u[q] over v's entries in flat order; b[q] = u[q] / s_v where
+ *   s_v > 0.  Where `s_v > 0` is false the family contributes nothing and is counted.  A fully observed family has one non-zero u,
+ *   so b is exactly 1.0: on a complete table with strictly positive tables E is the exact counts and the M-step has bn_fit_cpt's
+ *   bits.
+ * Row log-likelihood: ll_p = sum over the cliques of log(scale), -inf when a factor is 0; computed on the device (its log is not
+ *   libm's), added in no stated order -- the one quantity that is not pinned bit for bit.
+ *   L = sum_p (counts[p] > 0 ? double(counts[p]) x ll_p : 0.0): the observed-data log-likelihood of the table.
+ * E[q] = sum_p double(counts[p]) x b_p[q] in bn_em_fit's order (blocks of 256 consecutive patterns); the M-step, delta and the stop
+ *   rule (strict delta < tol, max_iters in 1..10 000) are bn_em_fit's, bit for bit.  L is reported and does not steer the loop.
+ *   bn_jt_em_expected_counts: ONE E-step under the engine's current tables: ecounts_out [n_entries]; row_loglik_out [n_patterns]
+ *     (ll_p) or NULL.
+ *   bn_jt_em_fit: starts from cpt_init or, if NULL, the engine's current tables; cpt_out [n_entries]; iters_out, delta_hist_out
+ *     [hist_cap] and loglik_hist_out [hist_cap] may be NULL: entry i of the latter is L under the tables iteration i STARTED from.
+ *     The engine's own tables are never written: apply cpt_out with bn_reload_cpt if wanted.
+ * Eligible: what the junction tree takes (bn_get_info "jt_eligible"), whatever the one-workgroup plan of bn_em_fit says; options
+ * "jt_form" and "jt_scratch_cells" hold as for bn_jt_run_batch.  Errors follow bn_jt_run: BN_ERR_ARG first; BN_ERR_STATE with the
+ * planner's reason on ineligible or sharded engines or a forced form that does not fit; BN_ERR_NO_DEVICE on BN_DEVICE_HOST_ONLY
+ * engines after both.
+ * bn_get_info: "jt_em_last_iters"; "jt_em_skipped": row-families with s_v not > 0 in the last call, summed over its iterations;
+ * "jt_em_estep_ns" / "jt_em_mstep_ns": device time of the last call's E-steps (potentials included) / M-steps; "jt_em_last_form";
+ * "jt_em_last_launches": launches of jt_em_kernel per E-step.  bn_set_option "jt_em_scratch_cells": doubles of the scratch array
+ * that holds one launch's posteriors (0: the default, 2^22); it bounds the rows per launch -- as "jt_scratch_cells" does in form
+ * 2 -- and changes no result.
+ * A bn_jt_em_* call leaves everything the other call families use as it was: the engine's potentials, the scales bn_jt_scales
+ * reports, "jt_last_kind" and the other "jt_last_*" values among it.
+ */
+typedef struct bn_jt_em_options {
+    int32_t max_iters;
+    double tol;
+    double prior;
+} bn_jt_em_options;
+int bn_jt_em_expected_counts(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const uint64_t *counts, double *ecounts_out,
+                             double *row_loglik_out);
+int bn_jt_em_fit(bn_engine *eng, int64_t n_patterns, const uint8_t *patterns, const uint64_t *counts, const bn_jt_em_options *opt,
+                 const double *cpt_init, double *cpt_out, int32_t *iters_out, double *delta_hist_out, double *loglik_hist_out,
+                 int32_t hist_cap);
+
 int bn_jt_plan_dims(bn_engine *eng, int64_t *dims_out);
 int bn_jt_plan_dump(bn_engine *eng, int32_t *order, int32_t *parent, int32_t *level, int32_t *var_ptr, int32_t *vars, int32_t *sep_ptr,
                     int32_t *sep_vars, int32_t *cpt_clique, int32_t *home);

@@ -1,0 +1,205 @@
+"""Host restatement of exact expectation-maximisation (bn_jt_em_*, bayesiannetwork_amd/csrc/bn_jt.hpp "Exact EM") over the plan the
+library dumps: jtree_refs.Restatement's potentials, collect and distribute, then the family read-out, the row log-likelihood and
+em_refs' sums, M-step and loop.  Plain numpy fp64 with axes and index arithmetic of its own (no item tables); E, theta after every
+iteration, the deltas and the skipped count are compared with the device bit for bit, ll_p and L within a bound.
+
+E-step per row under theta: an observed node multiplies its home clique by its one-hot vector (1.0 / 0.0), ascending node id; collect
+and distribute as bn_jt_run.  Node v's CPT lies in clique cpt_clique[v]; for a flat CPT entry q (first parent most significant, own
+state last) u[q] = two-level sum of that clique's entries whose digits match q, ascending entry index; s_v = two-level sum of u over
+v's entries in flat order; b = u / s_v where s_v > 0, else the family contributes nothing and is counted.  ll_p = sum of log(scale).
+L = sum_p (count_p > 0 ? float(count_p) x ll_p : 0.0).
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import em_refs  # noqa: E402
+import jtree_refs  # noqa: E402
+from jtree_refs import _left_to_right, _onto, _spread, _two_level  # noqa: E402
+
+MISSING = em_refs.MISSING
+BLOCK = em_refs.BLOCK
+LD = np.longdouble
+
+
+class ExactE(jtree_refs.Restatement):
+    """The E-step of one row under the model's tables: ``row(cells)`` -> (b [entries], skipped families, scales [cliques])."""
+
+    def tables(self, cells):
+        """The clique tables after distribute and the scales, evidence from the row's bytes."""
+        k, cl, sp, par = self.k, self.cl, self.sp, self.par
+        nc = len(cl)
+        pot = []
+        for c in range(nc):
+            arr = self.psi0[c]
+            for v in self.homed[c]:                             # ascending node id
+                if int(cells[v]) != MISSING:
+                    hot = np.zeros(k[v])
+                    hot[int(cells[v])] = 1.0
+                    arr = arr * _spread(hot, {v}, cl[c], k)
+            pot.append(arr)
+        scales = np.zeros(nc)
+        msg = [None] * nc
+        with np.errstate(all="ignore"):
+            for l in range(len(self.by_level) - 1, -1, -1):
+                for c in self.by_level[l]:
+                    raw = _onto(pot[c], cl[c], set(sp[c]), k)
+                    s = _left_to_right(raw)
+                    scales[c] = s
+                    msg[c] = raw / s if s > 0 else raw
+                if l == 0:
+                    break
+                for p in self.by_level[l - 1]:
+                    for c in self.kids[p]:
+                        pot[p] = pot[p] * _spread(msg[c], set(sp[c]), cl[p], k)
+            for l in range(1, len(self.by_level)):
+                for c in self.by_level[l]:
+                    new = _onto(pot[par[c]], cl[par[c]], set(sp[c]), k)
+                    ratio = np.where(msg[c] == 0.0, 0.0, new / msg[c])
+                    pot[c] = pot[c] * _spread(ratio, set(sp[c]), cl[c], k)
+        return pot, scales
+
+    def row(self, cells):
+        model, k, cl = self.model, self.k, self.cl
+        pot, scales = self.tables(cells)
+        out = np.zeros(int(model.cpt_off[-1]))
+        skipped = 0
+        with np.errstate(all="ignore"):
+            for v in range(model.n):
+                c = int(self.plan["cpt_clique"][v])
+                fam = [int(p) for p in model.parents(v)] + [v]     # the flat CPT order: first parent most significant, own state last
+                first = [cl[c].index(u) for u in fam]
+                rest = [i for i in range(len(cl[c])) if i not in first]   # ascending: the terms in ascending entry index
+                size = int(np.prod([k[u] for u in fam], dtype=np.int64))
+                u = _two_level(np.transpose(pot[c], first + rest).reshape(size, -1))
+                s = _two_level(u.reshape(1, -1))[0]
+                if s > 0:
+                    out[int(model.cpt_off[v]):int(model.cpt_off[v + 1])] = u / s
+                else:
+                    skipped += 1
+        return out, skipped, scales
+
+
+def row_loglik(scales):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lg = 0.0
+        for s in scales:
+            lg = lg + float(np.log(s))
+    return lg
+
+
+def expected_counts(model, plan, patterns, counts):
+    """One exact E-step under model.cpt: dict(E [entries], loglik [P], L, skipped, bound: sum_p |count_p x log scale| over the finite
+    terms -- what 1e-12 of bounds the device's ll_p and L)."""
+    patterns = np.asarray(patterns, np.uint8).reshape(-1, model.n)
+    counts = np.asarray(counts, np.uint64)
+    P, S = len(counts), int(model.cpt_off[-1])
+    step = ExactE(model, plan)
+    E = np.zeros(S)
+    ll = np.zeros(P)
+    row_bound = np.zeros(P)
+    skipped = 0
+    memo = {}
+    for b0 in range(0, P, BLOCK):
+        part = np.zeros(S)
+        for p in range(b0, min(b0 + BLOCK, P)):
+            key = patterns[p].tobytes()
+            if key not in memo:
+                b, sk, scales = step.row(patterns[p])
+                with np.errstate(divide="ignore"):
+                    logs = np.log(scales)
+                memo[key] = (b, sk, row_loglik(scales), float(np.abs(logs[np.isfinite(logs)]).sum()))
+            b, sk, ll[p], row_bound[p] = memo[key]
+            skipped += sk
+            part = part + np.float64(counts[p]) * b
+        E = E + part
+    L, bound = 0.0, 0.0
+    for p in range(P):
+        if int(counts[p]) > 0:
+            L = L + float(counts[p]) * ll[p]
+            bound = bound + float(counts[p]) * row_bound[p]
+    return {"E": E, "loglik": ll, "L": L, "skipped": skipped, "bound": bound, "row_bound": row_bound}
+
+
+def em_fit(model, plan, patterns, counts, max_iters=100, tol=1e-6, prior=0.0, cpt_init=None):
+    """dict(cpt, iters, deltas [iters], thetas [iters], E and L of every iteration (L under the tables the iteration started from),
+    bounds, skipped summed over the iterations)."""
+    theta = np.asarray(model.cpt if cpt_init is None else cpt_init, dtype=np.float64).copy()
+    out = {"deltas": [], "thetas": [], "E": [], "L": [], "bounds": [], "skipped": 0}
+    for _ in range(max_iters):
+        e = expected_counts(em_refs.with_cpt(model, theta), plan, patterns, counts)
+        new = em_refs.m_step(model, e["E"], prior)
+        d = np.abs(new - theta)
+        d = d[~np.isnan(d)]
+        delta = float(d.max()) if d.size else 0.0
+        theta = new
+        out["deltas"].append(delta)
+        out["thetas"].append(theta.copy())
+        out["E"].append(e["E"])
+        out["L"].append(e["L"])
+        out["bounds"].append(e["bound"])
+        out["skipped"] += e["skipped"]
+        if delta < tol:
+            break
+    out["cpt"], out["iters"], out["deltas"] = theta, len(out["deltas"]), np.asarray(out["deltas"])
+    return out
+
+
+# ---- enumeration of the joint in long double: the reference of the family posteriors and of log P(e) --------------------------------
+
+def joint(model):
+    """P(x) as an n-axis long double array (networks of a few hundred thousand joint states)."""
+    k = [int(x) for x in model.k]
+    arr = np.ones([1] * model.n, dtype=LD)
+    for v in range(model.n):
+        fam = [int(p) for p in model.parents(v)] + [v]
+        t = np.asarray(model.cpt_of(v), dtype=LD).reshape([k[u] for u in fam])
+        order = np.argsort(fam)
+        t = np.transpose(t, order)
+        arr = arr * t.reshape([k[u] if u in fam else 1 for u in range(model.n)])
+    return arr
+
+
+def enumerated_row(model, jnt, cells):
+    """(family posteriors [entries] in the flat layout, log P(e)) of one row, by summing the joint."""
+    k = [int(x) for x in model.k]
+    w = jnt
+    for v in range(model.n):
+        if int(cells[v]) != MISSING:
+            hot = np.zeros(k[v], dtype=LD)
+            hot[int(cells[v])] = 1
+            w = w * hot.reshape([k[v] if u == v else 1 for u in range(model.n)])
+    pe = w.sum()
+    out = np.zeros(int(model.cpt_off[-1]), dtype=LD)
+    for v in range(model.n):
+        fam = [int(p) for p in model.parents(v)] + [v]
+        others = tuple(u for u in range(model.n) if u not in fam)
+        m = w.sum(axis=others)                                  # axes: the family, ascending node id
+        asc = sorted(fam)
+        m = np.transpose(m, [asc.index(u) for u in fam])        # -> flat CPT order
+        out[int(model.cpt_off[v]):int(model.cpt_off[v + 1])] = (m / pe).reshape(-1)
+    return out, np.log(pe)
+
+
+# ---- the cases of "L never falls" (tests/test_jtem_refs.py): (model, samples, blanked, table seed, seed of the starting tables) ----
+
+def likelihood_cases():
+    from bayesiannetwork_amd import synth
+    return [(synth.grid(3, 3, 2, seed=1), 300, 0.3, 302, 22),
+            (synth.grid(3, 3, 4, seed=1), 300, 0.3, 303, 23),
+            (synth.random_dag(12, 3, 6, [2, 3], seed=4), 300, 0.35, 304, 24)]
+
+
+def enumeration_networks():
+    from bayesiannetwork_amd import synth
+    return {"pearl": synth.pearl(), "grid3x3k2": synth.grid(3, 3, 2, seed=1), "grid3x3k4": synth.grid(3, 3, 4, seed=1),
+            "dag12": synth.random_dag(12, 3, 6, [2, 3], seed=4)}
+
+
+def enumeration_table(model):
+    """12 rows of em_refs.sampled_table(m, 12, 0.4, seed=77) plus one fully missing row."""
+    pats, _ = em_refs.sampled_table(model, 12, 0.4, seed=77)
+    return np.concatenate([pats, np.full((1, model.n), MISSING, np.uint8)])
