@@ -643,8 +643,13 @@ int64_t em_get_info(bn_engine* e, const char* name, bool* known);
 int jt_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t jt_get_info(bn_engine* e, const char* name, bool* known);
 void jt_cpt_reloaded(bn_engine* e);    // bn_reload_cpt: the base potentials are computed again at the next run
-void jt_ensure_plan(bn_engine* e);     // the plan, built once (also on engines without a device)
+// What every call that runs on the tree refuses, in the order it reports them: a sharded engine and a plan that is not eligible
+// (jt_check_plan, which builds the plan, once, also on engines without a device), then a forced form 1 that does not fit and an
+// engine without a device (jt_check_form; *form_out: 1 or 2).  Two steps: exact EM has a refusal of its own between them.
+int jt_check_plan(bn_engine* e);
+int jt_check_form(bn_engine* e, int* form_out);
 int jt_ensure_tables(bn_engine* e);    // the plan's item tables on the device, once (not the base potentials)
+JtTables jt_tables_of(const JtState& j, const double* psi0);   // ... as the kernels take them, with the base potentials to run on
 // the "jt_em_*" names (bn_engine_jt_em.cpp)
 int jt_em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t jt_em_get_info(bn_engine* e, const char* name, bool* known);

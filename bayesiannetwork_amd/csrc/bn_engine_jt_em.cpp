@@ -56,18 +56,9 @@ int reserve(bn_engine* e, int64_t n_patterns, const bn_policy::EmPlan& plan, int
 
 // what both entry points check behind their arguments: the plan's eligibility, the form, the device.  *form_out: 1 or 2
 int check_engine(bn_engine* e, int* form_out) {
-    if (e->plan.nranks > 1) return fail(BN_ERR_STATE, "junction-tree propagation is not available on sharded engines");
-    jt_ensure_plan(e);
-    const JtPlan& P = e->jt.plan;
-    if (!P.ok) return fail(BN_ERR_STATE, "not eligible for junction-tree propagation: " + P.why);
-    if (P.families.empty()) return fail(BN_ERR_STATE, "exact expectation-maximisation: the CPT array has 2^31 entries or more");
-    const int form = jt_form(P, e->jt.form_option);
-    if (form == 0)
-        return fail(BN_ERR_STATE, "option jt_form = 1, but the state of one evidence set, " + std::to_string(P.state_cells) + " doubles, does not fit the " +
-                                      std::to_string(kJtLdsCells) + " doubles of LDS that form 1 keeps it in");
-    if (int rc = refuse_unusable(e, BN_ERR_NO_DEVICE)) return rc;
-    *form_out = form;
-    return BN_OK;
+    if (int rc = jt_check_plan(e)) return rc;
+    if (e->jt.plan.families.empty()) return fail(BN_ERR_STATE, "exact expectation-maximisation: the CPT array has 2^31 entries or more");
+    return jt_check_form(e, form_out);
 }
 
 struct JtEmCall {
@@ -107,13 +98,9 @@ int run(bn_engine* e, const JtEmCall& c) {
 
     const JtBaseArgs base{int32_t(P.pot_cells), j.d_cliques, j.d_ent_clique, j.d_asg_ptr, j.d_asg, j.d_fam, m.d_theta, m.d_psi0};
     JtEmArgs a{};
-    a.n = P.n; a.N = P.N; a.nc = P.nc; a.nlev = P.nlev;
-    a.pot_cells = int32_t(P.pot_cells); a.sep_cells = int32_t(P.sep_cells); a.state_cells = int32_t(P.state_cells); a.S = S;
-    a.cliques = j.d_cliques; a.levels = j.d_levels; a.nodes = j.d_nodes; a.ent_clique = j.d_ent_clique; a.dn_map = j.d_dn_map;
-    a.sep_clique = j.d_sep_clique; a.c_base = j.d_c_base; a.p_base = j.d_p_base; a.c_res = j.d_c_res; a.p_res = j.d_p_res;
-    a.up_map = j.d_up_map; a.home_nodes = j.d_home_nodes;
-    a.families = m.d_families; a.f_node = m.d_f_node; a.f_base = m.d_f_base; a.f_res = m.d_f_res;
-    a.psi0 = m.d_psi0; a.scratch = m.d_scratch; a.b = m.d_b;
+    a.t = jt_tables_of(j, m.d_psi0);
+    a.S = S; a.families = m.d_families; a.f_node = m.d_f_node; a.f_base = m.d_f_base; a.f_res = m.d_f_res;
+    a.scratch = m.d_scratch; a.b = m.d_b;
     EmAccArgs acc{};
     acc.S = S; acc.n_patterns = c.n_patterns; acc.b = m.d_b; acc.counts = m.d_counts; acc.partial = m.d_partial; acc.E = m.d_E;
     const JtEmTotalArgs tot{c.n_patterns, m.d_counts, m.d_loglik, m.d_skipped, reinterpret_cast<double*>(m.d_words + 1), m.d_words};

@@ -69,10 +69,11 @@
 
 namespace bnmi {
 
-struct JtArgs {
+// The plan's dimensions and item tables on the device (bn_jt_plan.hpp) and the base potentials of one set of CPTs: what every walk
+// over the tree reads.  Filled by bn_eng::jt_tables_of.
+struct JtTables {
     int32_t n, N, nc, nlev;
     int32_t pot_cells, sep_cells, state_cells;
-    int32_t set_base;               // the launch's first set: workgroup b runs set set_base + b in state slot b
     const JtClique* cliques;
     const JtLevel* levels;
     const JtNode* nodes;
@@ -87,6 +88,11 @@ struct JtArgs {
     const int32_t* home_nodes;
     const int32_t* elem_node;
     const double* psi0;             // [pot_cells]
+};
+
+struct JtArgs {
+    JtTables t;
+    int32_t set_base;               // the launch's first set: workgroup b runs set set_base + b in state slot b
     // evidence: the caller's arrays in a staging block (bn_batch_stage.hpp), set q's header at ev_meta + 8 q
     const int32_t* ev_node;
     const int32_t* ev_off;
@@ -117,26 +123,12 @@ int launch_jt_base(const JtBaseArgs& a, void* stream);
 // ---- exact EM: one workgroup per pattern row of the launch (blockIdx.x), the state in LDS (form 1) or in slice blockIdx.x of scratch
 constexpr int kJtEmMissing = 255;   // BN_EM_MISSING
 struct JtEmArgs {
-    int32_t n, N, nc, nlev;
-    int32_t pot_cells, sep_cells, state_cells;
+    JtTables t;                     // psi0: of the current theta
     int32_t S;                      // CPT entries
-    const JtClique* cliques;
-    const JtLevel* levels;
-    const JtNode* nodes;
-    const int32_t* ent_clique;
-    const int32_t* dn_map;
-    const int32_t* sep_clique;
-    const int32_t* c_base;
-    const int32_t* p_base;
-    const int32_t* c_res;
-    const int32_t* p_res;
-    const int32_t* up_map;
-    const int32_t* home_nodes;
     const JtFamily* families;       // [n]
     const int32_t* f_node;          // [S]
     const int32_t* f_base;          // [S]
     const int32_t* f_res;
-    const double* psi0;             // [pot_cells] of the current theta
     const uint8_t* patterns;        // the launch's rows, [rows][n]
     double* scratch;                // form 2: [rows][state_cells]
     double* b;                      // [rows][S] family posteriors, flat CPT order

@@ -160,6 +160,22 @@ def tie_grid():
     return FlatModel(g.k, g.in_ptr, g.in_idx, g.cpt_off, np.full(g.cpt.shape, 0.5), name="tie_grid")
 
 
+# ---- the decode's two special paths: roots only (one level: the states pay a barrier of their own), and a childless root beside
+# deeper cliques.  name -> model.  Every case passes the margin of the small cases with both kinds of forest_evidence.
+def forest_cases():
+    a = np.asarray
+    return {"lone": from_parent_lists([3], [[]], [a([0.2, 0.5, 0.3])], name="lone"),                                   # 1 clique, 1 level
+            "two": from_parent_lists([2, 3], [[], []], [a([0.25, 0.75]), a([0.2, 0.5, 0.3])], name="two"),             # 2 roots, 1 level
+            "forest": from_parent_lists([3, 2, 2, 2], [[], [], [1], [2]],                                              # levels [0, 0, 1]
+                                        [a([0.2, 0.5, 0.3]), a([0.25, 0.75]), a([0.9, 0.1, 0.3, 0.7]), a([0.6, 0.4, 0.2, 0.8])], name="forest")}
+
+
+def forest_evidence(model):
+    """[(kind, evidence)]: none; one strictly positive soft vector on node n // 2."""
+    v = model.n // 2
+    return [("none", None), ("soft", Evidence.from_dict(model, {v: 0.1 + np.random.default_rng(7).random(int(model.k[v]))}))]
+
+
 # ---- networks too large to enumerate -------------------------------------------------------------------------------------------
 
 def _log_terms(model, states, ev):

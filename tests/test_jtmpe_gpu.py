@@ -115,6 +115,21 @@ def test_tie_cases_decode_to_a_maximiser(bnlib):
             assert got["states"].tolist() == [0] * 9
 
 
+@pytest.mark.parametrize("form", [1, 2])
+@pytest.mark.parametrize("name", sorted(jm.forest_cases()))
+def test_forests_equal_the_restatement_in_both_forms(bnlib, name, form):
+    """Roots only (one level: the states pay their own barrier), and a childless root beside a deeper tree."""
+    m = jm.forest_cases()[name]
+    with Engine(m, device=0) as e:
+        e.set_option("jt_form", form)
+        plan = e.jt_plan()
+        assert plan["levels"] == (2 if name == "forest" else 1) and list(plan["parent"]).count(-1) == min(m.n, 2)
+        rs = jm.Restatement(m, plan)
+        for kind, ev in jm.forest_evidence(m):
+            check_run(e.jt_mpe_run(ev), rs.run_max(ev), (name, kind, form))
+            assert e.info("jt_last_form") == form and e.info("jt_last_kind") == 2
+
+
 @pytest.fixture(scope="module")
 def alarm_singles(bnlib):
     m = jr.alarm()

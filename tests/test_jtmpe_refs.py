@@ -50,6 +50,19 @@ def test_restatement_equals_enumeration(host_engine, name):
             _check_against_enumeration(rs, m, ev, (name, kind, "brute_max_marginals"), (mm, st, best, second))
 
 
+@pytest.mark.parametrize("kind", [0, 1], ids=["none", "soft"])
+@pytest.mark.parametrize("name", sorted(jm.forest_cases()))
+def test_forests_equal_enumeration(host_engine, name, kind):
+    """Roots only (one level), and a childless root beside a deeper tree: the decode's two special paths."""
+    m = jm.forest_cases()[name]
+    with host_engine(m) as e:
+        plan = e.jt_plan()
+    shape = {"lone": ([-1], [0]), "two": ([-1, -1], [0, 0]), "forest": ([-1, -1, 1], [0, 0, 1])}[name]
+    assert (list(plan["parent"]), list(plan["level"])) == shape
+    what, ev = jm.forest_evidence(m)[kind]
+    _check_against_enumeration(jm.Restatement(m, plan), m, ev, (name, what))
+
+
 @pytest.mark.parametrize("case", mr.POLYTREE_CASES, ids=lambda c: "n%d_s%d_e%d" % c)
 def test_polytree_cases_with_their_own_evidence(host_engine, case):
     m, ev, ev_state = mr.polytree_case(*case)
