@@ -15,10 +15,12 @@
 //   em_accumulate_kernel   one thread per CPT entry: the chunk's count x b, pattern after pattern, into the sum of the 256-block in
 //                          hand; a finished block's sum into E.  The block in hand survives a chunk boundary in `partial`.
 //   em_mstep_kernel        one thread per CPT entry: row total, division or the uniform row, |change| -> the maximum (bit patterns of
-//                          non-negative doubles order like the values), theta_new into the flat array and the two device images.
+//                          non-negative doubles order like the values), theta_new into the flat array and, where the caller has them (the
+//                          one-workgroup E-step; not the junction tree's, bn_jt.hip), the two device images.
 #include "bn_em.hpp"
 #include "bn_small_dev.hpp"
 #include "bn_item_launch.hpp"
+#include "bn_launch.hpp"
 
 namespace bnmi {
 
@@ -133,15 +135,17 @@ __global__ __launch_bounds__(256) void em_mstep_kernel(EmMstepArgs a) {
     const int q = int(blockIdx.x * blockDim.x + threadIdx.x);
     double d = 0.0;
     if (q < a.S) {
-        const uint32_t rw = a.row[q];
-        const int first = int(rw & 0xffffu), k = int(rw >> 16);
+        const bn_policy::EmRow rw = a.row[q];
+        const int first = rw.first, k = rw.k;
         double tot = 0.0;
         for (int i = 0; i < k; ++i) tot += a.E[first + i] + a.prior;
         const double th = tot > 0.0 ? (a.E[q] + a.prior) / tot : 1.0 / double(k);   // (bn_fit_kernels.hip: count / total, else uniform)
         d = fabs(th - a.theta[q]);
         a.theta[q] = th;
-        a.ent_cpt[a.slot_of[q]] = th;
-        if (a.init_of[q] >= 0) a.npi_init[a.init_of[q]] = th;
+        if (a.slot_of) {   // (the junction tree's E-step reads theta itself: no images)
+            a.ent_cpt[a.slot_of[q]] = th;
+            if (a.init_of[q] >= 0) a.npi_init[a.init_of[q]] = th;
+        }
     }
     // md = (md < d) ? d : md from +0.0: a NaN never enters -- it is dropped here, the bit patterns of the rest order like the values
     const unsigned long long bits = wave_umax64_dpp((unsigned long long)__double_as_longlong(res_acc(0.0, d)));
@@ -157,17 +161,11 @@ int launch_em_small(const EmSmallArgs& a, int waves, size_t lds_bytes, int32_t c
 }
 
 int launch_em_accumulate(const EmAccArgs& a, void* stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(em_accumulate_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launched([&] { hipLaunchKernelGGL(em_accumulate_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a); });
 }
 
 int launch_em_mstep(const EmMstepArgs& a, void* stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(em_mstep_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
+    return launched([&] { hipLaunchKernelGGL(em_mstep_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a); });
 }
 
 }  // namespace bnmi

@@ -37,6 +37,7 @@
 
 #include <cstdint>
 
+#include "bn_engine_policy.hpp"
 #include "bn_maxprod.hpp"
 #include "bn_small.hpp"
 
@@ -79,13 +80,13 @@ struct EmAccArgs {
 };
 int launch_em_accumulate(const EmAccArgs& a, void* stream);
 
-// ---- M-step (one thread per CPT entry)
+// ---- M-step (one thread per CPT entry), of this E-step and of the junction tree's (bn_jt.hpp, "Exact EM")
 struct EmMstepArgs {
     int32_t S;
     double prior;
     const double* E;              // [S]
-    const uint32_t* row;          // [S] first entry of the entry's CPT row | arity << 16
-    const int32_t* slot_of;       // [S] flat entry -> its slot in ent_cpt
+    const bn_policy::EmRow* row;  // [S] the entry's CPT row: first entry, arity (bn_policy::em_rows)
+    const int32_t* slot_of;       // [S] flat entry -> its slot in ent_cpt; null: no images to rewrite (the three below are not read)
     const int32_t* init_of;       // [S] flat entry -> element of npi_init (a root's), -1: none
     double* theta;                // [S] in: the current tables, out: the new ones
     double* ent_cpt;

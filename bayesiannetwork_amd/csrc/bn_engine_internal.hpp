@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -180,31 +181,40 @@ struct MpeState {
     std::vector<int32_t> sweeps;
 };
 
-// Expectation-maximisation (bn_engine_em.cpp, bn_em.hip): its own images of the CPT values (the entry items' table, the roots' initial
-// pi(v)), the index maps between them and the flat array, the table, the scratch of family posteriors and the sums -- allocated at the
-// first call.  Nothing here is read or written by a bn_bp_* / bn_mpe_* call, and a bn_em_* call touches nothing else of the engine.
-struct EmState {
-    int64_t scratch_cells = bn_policy::kEmScratchCells;   // option "em_scratch_cells": doubles of the posteriors' scratch array
-    bool ready = false;                 // kernels prepared, maps uploaded, images and sums allocated
-    std::vector<int32_t> slot_of;       // [entries] flat CPT entry -> its slot in the entry items' table
-    std::vector<int32_t> init_of;       // [entries] flat CPT entry -> element of the initial pi(v) (a root's), -1: none
-    DeviceBuf<int32_t> d_ent_flat;      // [slots] the inverse | (first entry of its family) << 16, -1: no entry
-    DeviceBuf<int32_t> d_slot_of, d_init_of;
-    DeviceBuf<uint32_t> d_row;          // [entries] first entry of the CPT row | arity << 16
-    DeviceBuf<double> d_cpt, d_init;    // the images the E-step kernel reads, rewritten by every M-step
+// What the two expectation-maximisation states below share, and all that the loop of both (em_drive, bn_engine_em.cpp) works on:
+// theta, the sums, the table, the scratch of family posteriors, the M-step's row array -- allocated by em_reserve.
+struct EmCore {
+    int64_t scratch_cells;              // option "em_scratch_cells" / "jt_em_scratch_cells": doubles of the posteriors' scratch array
+    bool ready = false;                 // theta, sums, words allocated, the row array uploaded, the events created
     DeviceBuf<double> d_theta;          // [entries] flat
     DeviceBuf<double> d_E, d_partial;   // [entries] the sum, and the 256-block in hand
-    DeviceBuf<unsigned long long> d_words;   // [0] runs cut by the cap, [1] skipped families, [2] delta's bit pattern
+    DeviceBuf<unsigned long long> d_words;   // [0] runs cut by the cap, [1] skipped families, [2] delta's bit pattern, [3] L (a double)
+    DeviceBuf<bn_policy::EmRow> d_row;  // [entries] bn_policy::em_rows
     DeviceBuf<uint8_t> d_patterns;      // the table of the call
     DeviceBuf<unsigned long long> d_counts;
-    DeviceBuf<int32_t> d_sweeps;        // [patterns] of the last E-step
     int64_t cap_patterns = 0;
-    DeviceBuf<double> d_b;              // [chunk][entries] family posteriors of the launch in hand
+    DeviceBuf<double> d_b;              // [rows of a launch][entries] family posteriors of the launch in hand
     int64_t cap_b = 0;
     EventOwner ev[3];                   // E-step begins, E-step ends, M-step ends
     // the last call
     int32_t last_iters = 0;
-    int64_t capped = 0, skipped = 0, estep_ns = 0, mstep_ns = 0;
+    int64_t skipped = 0, estep_ns = 0, mstep_ns = 0;
+};
+
+// Expectation-maximisation (bn_engine_em.cpp, bn_em.hip): its own images of the CPT values (the entry items' table, the roots' initial
+// pi(v)) and the index maps between them and the flat array, beside the core -- allocated at the first call.  Nothing here is read or
+// written by a bn_bp_* / bn_mpe_* / bn_jt_em_* call, and a bn_em_* call touches nothing else of the engine.
+struct EmState {
+    EmCore core{bn_policy::kEmScratchCells};
+    bool ready = false;                 // kernels prepared, maps uploaded, images allocated
+    std::vector<int32_t> slot_of;       // [entries] flat CPT entry -> its slot in the entry items' table
+    std::vector<int32_t> init_of;       // [entries] flat CPT entry -> element of the initial pi(v) (a root's), -1: none
+    DeviceBuf<int32_t> d_ent_flat;      // [slots] the inverse | (first entry of its family) << 16, -1: no entry
+    DeviceBuf<int32_t> d_slot_of, d_init_of;
+    DeviceBuf<double> d_cpt, d_init;    // the images the E-step kernel reads, rewritten by every M-step
+    DeviceBuf<int32_t> d_sweeps;        // [patterns] of the last E-step
+    int64_t cap_rows = 0;
+    int64_t capped = 0;                 // the last call
 };
 
 // Junction-tree propagation (bn_engine_jt.cpp, bn_jt.hip): the plan (built at the first call that asks for it), its tables on the
@@ -241,31 +251,22 @@ struct JtState {
     std::vector<double> scales;         // [n_sets][nc]
 };
 
-// Exact expectation-maximisation (bn_engine_jt_em.cpp, jt_em_kernel of bn_jt.hip): the family tables on the device, its own theta
-// and base potentials, the table, the scratch of family posteriors (and, in form 2, of the rows' states), the sums -- allocated at
-// the first call.  It reads the junction tree's plan and item tables; nothing else of the engine is read or written, and nothing
-// here by any other call family.
+// Exact expectation-maximisation (bn_engine_jt_em.cpp, jt_em_kernel of bn_jt.hip): the family tables on the device, the base
+// potentials of its theta and, in form 2, the scratch of the rows' states, beside the core -- allocated at the first call.  It reads
+// the junction tree's plan and item tables; nothing else of the engine is read or written, and nothing here by any other call family.
 struct JtEmState {
-    int64_t scratch_cells = bn_policy::kJtEmScratchCells;   // option "jt_em_scratch_cells": doubles of the posteriors' scratch array
-    bool ready = false;                 // family tables uploaded, theta, potentials and sums allocated
+    EmCore core{bn_policy::kJtEmScratchCells};
+    bool ready = false;                 // family tables uploaded, potentials allocated
     DeviceBuf<JtFamily> d_families;
     DeviceBuf<int32_t> d_f_node, d_f_base, d_f_res;
-    DeviceBuf<double> d_theta, d_psi0;  // [entries] flat; [pot_cells] the base potentials of theta
-    DeviceBuf<double> d_E, d_partial;   // [entries] the sum, and the 256-block in hand
-    DeviceBuf<unsigned long long> d_words;   // [0] skipped families, [1] L (a double), [2] delta's bit pattern
-    DeviceBuf<uint8_t> d_patterns;      // the table of the call
-    DeviceBuf<unsigned long long> d_counts;
+    DeviceBuf<double> d_psi0;           // [pot_cells] the base potentials of theta
     DeviceBuf<double> d_loglik;         // [patterns] of the last E-step
     DeviceBuf<int32_t> d_skipped;       // [patterns] of the last E-step
-    int64_t cap_patterns = 0;
-    DeviceBuf<double> d_b;              // [rows of a launch][entries]
-    int64_t cap_b = 0;
+    int64_t cap_rows = 0;
     DeviceBuf<double> d_scratch;        // form 2: [rows of a launch][state_cells]
     int64_t cap_scratch = 0;
-    EventOwner ev[3];                   // E-step begins, E-step ends, M-step ends
-    // the last call
-    int32_t last_iters = 0, last_form = 0;
-    int64_t skipped = 0, estep_ns = 0, mstep_ns = 0, last_launches = 0;
+    int32_t last_form = 0;              // the last call
+    int64_t last_launches = 0;
 };
 
 struct bn_engine {
@@ -639,6 +640,43 @@ void mpe_cpt_reloaded(bn_engine* e);   // bn_reload_cpt: what max-product built 
 // the "em_*" names (bn_engine_em.cpp)
 int em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t em_get_info(bn_engine* e, const char* name, bool* known);
+// ---- what bn_em_* and bn_jt_em_* share (bn_engine_em.cpp): one call, one E-step as the loop sees it, one loop
+struct EmCall {
+    int64_t n_patterns;
+    const uint8_t* patterns;
+    const uint64_t* counts;
+    const double* theta0;     // flat, [entries]
+    bool fit;                 // false: one E-step, no M-step
+    int32_t max_iters;
+    double tol, prior;
+    double* E_out;            // the last E-step's sums (may be null)
+    void* rows_out;           // ... and its per-row array, EmEstep::d_rows (may be null)
+    double* cpt_out;          // (fit)
+    int32_t* iters_out;
+    double* delta_hist;
+    double* loglik_hist;      // (the tree only)
+    int32_t hist_cap;
+};
+// The launches return 0 or the hipError_t; `begin` and `end` may be empty.  They queue on the engine's stream and do not wait.
+struct EmEstep {
+    const char* what[3];                                   // begin, chunk, end: the kernel's name in "... launch failed"
+    std::function<int()> begin;                            // once per iteration, before the chunks
+    std::function<int(const bn_policy::EmChunk&)> chunk;   // one launch's rows: their family posteriors into EmCore::d_b
+    std::function<int()> end;                              // once per iteration, behind the chunks
+    const int32_t* slot_of;                                // the M-step's images (EmMstepArgs); all null: none
+    const int32_t* init_of;
+    double* ent_cpt;
+    double* npi_init;
+    const void* d_rows;                                    // [patterns] of row_bytes each: what the last E-step says of every row
+    size_t row_bytes;
+    bool has_L;                                            // `end` leaves L in word 3
+    int64_t* capped;                                       // where word 0 of the call goes (null: nowhere)
+};
+int em_reserve(bn_engine* e, EmCore& m, int64_t n_patterns, const bn_policy::EmPlan& plan);
+int em_drive(bn_engine* e, EmCore& m, const EmCall& c, const bn_policy::EmPlan& plan, const EmEstep& es);
+int em_check_fit_args(const double* cpt_out, int32_t max_iters, double tol, double prior, bool any_hist, int32_t hist_cap);
+// bn_set_option of either family: the option `own` ("em_scratch_cells" / "jt_em_scratch_cells"; 0: the default `dflt`)
+int em_scratch_option(const char* own, int64_t dflt, EmCore& m, const char* name, int32_t value, bool* known);
 // the "jt_*" names (bn_engine_jt.cpp)
 int jt_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t jt_get_info(bn_engine* e, const char* name, bool* known);

@@ -330,6 +330,13 @@ EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c) {
     return k;
 }
 
+std::vector<EmRow> em_rows(int32_t n, const int64_t* cpt_off, const int32_t* k) {
+    std::vector<EmRow> rows(static_cast<size_t>(cpt_off[n]));
+    for (int32_t v = 0; v < n; ++v)
+        for (int64_t q = cpt_off[v]; q < cpt_off[v + 1]; ++q) rows[size_t(q)] = {int32_t(cpt_off[v] + (q - cpt_off[v]) / k[v] * k[v]), k[v]};
+    return rows;
+}
+
 // Exact expectation-maximisation: em_plan's rows, and in form 2 at most the state slices the junction tree's scratch budget holds.
 EmPlan jt_em_plan(int64_t n_patterns, int32_t entries, int64_t b_scratch_cells, int form, int64_t state_cells, int64_t state_scratch_cells) {
     EmPlan p = em_plan(n_patterns, entries, b_scratch_cells);

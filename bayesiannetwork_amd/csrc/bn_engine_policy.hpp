@@ -168,6 +168,12 @@ struct EmChunk {
 // n_patterns >= 1, entries >= 1; scratch_cells < entries still gives one row per launch
 EmPlan em_plan(int64_t n_patterns, int32_t entries, int64_t scratch_cells);
 EmChunk em_chunk(const EmPlan& p, int64_t n_patterns, int64_t c);
+// The M-step's view of the flat CPT array (bn_em.hpp EmMstepArgs): for every entry q, the CPT row it is normalised in -- the row's
+// first entry and the node's arity.  From the plan's cpt_off [n + 1] and k [n] alone; cpt_off[n] < 2^31.
+struct EmRow {
+    int32_t first, k;
+};
+std::vector<EmRow> em_rows(int32_t n, const int64_t* cpt_off, const int32_t* k);
 
 // ---- exact expectation-maximisation (bn_jt_em_*, bn_jt.hpp): the rows of one launch of the junction-tree E-step.  As em_plan under
 // option "jt_em_scratch_cells" (the launch's family posteriors); in form 2 (jt_form: the per-row state in device scratch) also no

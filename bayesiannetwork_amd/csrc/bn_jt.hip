@@ -1,6 +1,6 @@
 // bn_jt.hip -- junction-tree propagation on gfx950: the base potentials, and the two-pass run of one evidence set per workgroup,
 // as a sum run (jt_kernel: marginals), as a max run (jt_mpe_kernel: exact MPE) and as the E-step of exact expectation-maximisation
-// (jt_em_kernel: the sum run of a pattern row and its family posteriors, with the small kernels of its sums and its M-step)
+// (jt_em_kernel: the sum run of a pattern row and its family posteriors, with the small kernel of its sums; the M-step is bn_em.hip's)
 // (rules: bn_jt.hpp; item tables: bn_jt_plan.hpp).  Every phase is written once: the potentials over a source of the home nodes'
 // factors, the walk (collect and distribute) over an operation -- JtSum or JtMax, the decode riding the max walk as hooks that the
 // sum walk does not have -- and the read-out over the same operation; the three kernels are entry points that put them together.
@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bn_jt.hpp"
+#include "bn_launch.hpp"
 
 namespace bnmi {
 namespace {
@@ -375,38 +376,6 @@ __global__ void __launch_bounds__(256) jt_em_total_kernel(JtEmTotalArgs a) {
     }
 }
 
-// the M-step of bn_em.hpp (em_mstep_kernel's arithmetic) on the flat array alone: one thread per CPT entry
-__global__ void __launch_bounds__(256) jt_em_mstep_kernel(JtEmMstepArgs a) {
-    const int q = int(blockIdx.x * blockDim.x + threadIdx.x);
-    double d = 0.0;
-    if (q < a.S) {
-        const JtFamily F = a.families[a.f_node[q]];
-        const int k = a.nodes[a.f_node[q]].k;
-        const int first = F.cpt_lo + (q - F.cpt_lo) / k * k;
-        double tot = 0.0;
-        for (int i = 0; i < k; ++i) tot += a.E[first + i] + a.prior;
-        const double th = tot > 0.0 ? (a.E[q] + a.prior) / tot : 1.0 / double(k);
-        d = fabs(th - a.theta[q]);
-        a.theta[q] = th;
-    }
-    // md = (md < d) ? d : md from +0.0: a NaN never enters; the bit patterns of the rest order like the values
-    unsigned long long bits = (unsigned long long)__double_as_longlong(0.0 < d ? d : 0.0);
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(bits, off, 64);
-        bits = bits < o ? o : bits;
-    }
-    if ((threadIdx.x & 63) == 0 && bits) atomicMax(a.delta_bits, bits);
-}
-
-// drop any stale error of this thread, launch, 0 or the hipError_t
-template <class F>
-int launched(F launch) {
-    (void)hipGetLastError();
-    launch();
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : int(e);
-}
-
 // one workgroup per set (row) of `blocks`: the state in LDS (form 1) or in the arguments' scratch (form 2)
 template <class Args>
 int launch_form(void (*lds)(Args), void (*mem)(Args), const Args& a, int form, int blocks, void* stream) {
@@ -435,10 +404,6 @@ int launch_jt_em(const JtEmArgs& a, int form, int n_rows, void* stream) {
 
 int launch_jt_em_total(const JtEmTotalArgs& a, void* stream) {
     return launched([&] { hipLaunchKernelGGL(jt_em_total_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a); });
-}
-
-int launch_jt_em_mstep(const JtEmMstepArgs& a, void* stream) {
-    return launched([&] { hipLaunchKernelGGL(jt_em_mstep_kernel, dim3(unsigned((a.S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a); });
 }
 
 }  // namespace bnmi

@@ -147,17 +147,6 @@ struct JtEmTotalArgs {
 };
 int launch_jt_em_total(const JtEmTotalArgs& a, void* stream);
 
-struct JtEmMstepArgs {
-    int32_t S;
-    double prior;
-    const double* E;                // [S]
-    const JtFamily* families;
-    const JtNode* nodes;
-    const int32_t* f_node;
-    double* theta;                  // [S] in: the current tables, out: the new ones
-    unsigned long long* delta_bits; // max |theta_new - theta|, bit pattern of a non-negative double (zeroed by the host)
-};
-int launch_jt_em_mstep(const JtEmMstepArgs& a, void* stream);
 // form 1: state in LDS; form 2: in a.scratch.  One workgroup per set.  kind: kJtSum (jt_kernel) or kJtMax (jt_mpe_kernel).
 int launch_jt(const JtArgs& a, int form, int kind, int n_sets, void* stream);
 

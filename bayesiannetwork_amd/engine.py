@@ -295,16 +295,38 @@ class Engine:
             raise ValueError("one count per pattern")
         return patterns, counts
 
+    def _em_one_step(self, call, patterns, counts, extra, row_dtype):
+        """One E-step of either path: (E [entries], the path's per-row array [P] of row_dtype); extra: the call's arguments between
+        the table and the outputs."""
+        patterns, counts = self._em_table(patterns, counts)
+        E = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        rows = np.zeros(max(patterns.shape[0], 1), dtype=row_dtype)
+        _lib.check(call(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), *extra,
+                        _p(E, ctypes.c_double), _p(rows, np.ctypeslib.as_ctypes_type(row_dtype))))
+        return E, rows[:patterns.shape[0]]
+
+    def _em_fit(self, call, patterns, counts, opt, max_iters, cpt_init, reload, n_hist):
+        """The fit of either path: (cpt, iterations, n_hist histories [iterations])."""
+        patterns, counts = self._em_table(patterns, counts)
+        init = None if cpt_init is None else np.ascontiguousarray(cpt_init, dtype=np.float64)
+        if init is not None and init.shape[0] != int(self.model.cpt_off[-1]):
+            raise ValueError("cpt_init must have one value per CPT entry")
+        cpt = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
+        cap = max(1, min(int(max_iters), 10000))
+        hists = [np.zeros(cap, dtype=np.float64) for _ in range(n_hist)]
+        iters = ctypes.c_int32(0)
+        _lib.check(call(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), ctypes.byref(opt),
+                        None if init is None else _p(init, ctypes.c_double), _p(cpt, ctypes.c_double), ctypes.byref(iters),
+                        *[_p(h, ctypes.c_double) for h in hists], cap))
+        if reload:
+            self.reload_cpt(cpt)
+        return (cpt, int(iters.value), *[h[:iters.value].copy() for h in hists])
+
     def em_expected_counts(self, patterns, counts, bp_eps: float = 1e-3, bp_max_sweeps: int = 0):
         """bn_em_expected_counts: ONE E-step under the engine's current tables.  patterns [P][n] uint8 with MISSING (255) for an
         unobserved cell, counts [P].  Returns (E [entries], the expected family counts in the flat CPT layout; sweeps int32 [P], the
         belief-propagation sweeps of each row's run).  bp_max_sweeps == 0: a cap of 10 000 sweeps."""
-        patterns, counts = self._em_table(patterns, counts)
-        E = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
-        sweeps = np.zeros(max(patterns.shape[0], 1), dtype=np.int32)
-        _lib.check(_lib.lib().bn_em_expected_counts(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64),
-                                                    float(bp_eps), int(bp_max_sweeps), _p(E, ctypes.c_double), _p(sweeps, ctypes.c_int32)))
-        return E, sweeps[:patterns.shape[0]]
+        return self._em_one_step(_lib.lib().bn_em_expected_counts, patterns, counts, (float(bp_eps), int(bp_max_sweeps)), np.int32)
 
     def em_fit(self, patterns, counts, max_iters: int = 100, tol: float = 1e-6, bp_eps: float = 1e-3, bp_max_sweeps: int = 0,
                prior: float = 0.0, cpt_init=None, reload: bool = False):
@@ -312,52 +334,22 @@ class Engine:
         largest change of a table entry is below tol or max_iters iterations have run.  Returns (cpt [entries], iterations,
         delta_history [iterations]).  The engine's tables are not touched unless reload=True, which applies the result with
         reload_cpt()."""
-        patterns, counts = self._em_table(patterns, counts)
-        opt = _lib.EmOptions(int(max_iters), float(tol), float(bp_eps), int(bp_max_sweeps), float(prior))
-        init = None if cpt_init is None else np.ascontiguousarray(cpt_init, dtype=np.float64)
-        if init is not None and init.shape[0] != int(self.model.cpt_off[-1]):
-            raise ValueError("cpt_init must have one value per CPT entry")
-        cpt = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
-        cap = max(1, min(int(max_iters), 10000))
-        hist = np.zeros(cap, dtype=np.float64)
-        iters = ctypes.c_int32(0)
-        _lib.check(_lib.lib().bn_em_fit(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), ctypes.byref(opt),
-                                        None if init is None else _p(init, ctypes.c_double), _p(cpt, ctypes.c_double), ctypes.byref(iters), _p(hist, ctypes.c_double), cap))
-        if reload:
-            self.reload_cpt(cpt)
-        return cpt, int(iters.value), hist[:iters.value].copy()
+        return self._em_fit(_lib.lib().bn_em_fit, patterns, counts, _lib.EmOptions(int(max_iters), float(tol), float(bp_eps), int(bp_max_sweeps), float(prior)),
+                            max_iters, cpt_init, reload, n_hist=1)
 
     # ---- exact expectation-maximisation: the E-step on the junction tree (bn_jt_em_*) ------------
     def jt_em_expected_counts(self, patterns, counts):
         """bn_jt_em_expected_counts: ONE exact E-step under the engine's current tables; the table is em_expected_counts'.
         Returns (E [entries], the expected family counts in the flat CPT layout; row_loglik [P], log P(e_p) of every row, -inf
         where the row has probability 0).  Exact on every network the junction tree takes (info("jt_eligible"))."""
-        patterns, counts = self._em_table(patterns, counts)
-        E = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
-        ll = np.zeros(max(patterns.shape[0], 1), dtype=np.float64)
-        _lib.check(_lib.lib().bn_jt_em_expected_counts(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64),
-                                                       _p(E, ctypes.c_double), _p(ll, ctypes.c_double)))
-        return E, ll[:patterns.shape[0]]
+        return self._em_one_step(_lib.lib().bn_jt_em_expected_counts, patterns, counts, (), np.float64)
 
     def jt_em_fit(self, patterns, counts, max_iters: int = 100, tol: float = 1e-6, prior: float = 0.0, cpt_init=None, reload: bool = False):
         """bn_jt_em_fit: em_fit with the exact E-step.  Returns (cpt [entries], iterations, delta_history [iterations],
         loglik_history [iterations]: the observed-data log-likelihood of the table under the tables each iteration started
         from).  The engine's tables are not touched unless reload=True, which applies the result with reload_cpt()."""
-        patterns, counts = self._em_table(patterns, counts)
-        opt = _lib.JtEmOptions(int(max_iters), float(tol), float(prior))
-        init = None if cpt_init is None else np.ascontiguousarray(cpt_init, dtype=np.float64)
-        if init is not None and init.shape[0] != int(self.model.cpt_off[-1]):
-            raise ValueError("cpt_init must have one value per CPT entry")
-        cpt = np.zeros(int(self.model.cpt_off[-1]), dtype=np.float64)
-        cap = max(1, min(int(max_iters), 10000))
-        hist, lls = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.float64)
-        iters = ctypes.c_int32(0)
-        _lib.check(_lib.lib().bn_jt_em_fit(self._h, patterns.shape[0], _p(patterns, ctypes.c_uint8), _p(counts, ctypes.c_uint64), ctypes.byref(opt),
-                                           None if init is None else _p(init, ctypes.c_double), _p(cpt, ctypes.c_double), ctypes.byref(iters),
-                                           _p(hist, ctypes.c_double), _p(lls, ctypes.c_double), cap))
-        if reload:
-            self.reload_cpt(cpt)
-        return cpt, int(iters.value), hist[:iters.value].copy(), lls[:iters.value].copy()
+        return self._em_fit(_lib.lib().bn_jt_em_fit, patterns, counts, _lib.JtEmOptions(int(max_iters), float(tol), float(prior)),
+                            max_iters, cpt_init, reload, n_hist=2)
 
     def bp_stats(self) -> dict:
         st = _lib.BpStats()

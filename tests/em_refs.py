@@ -195,13 +195,14 @@ def m_step(model, E, prior=0.0):
     return out
 
 
-def em_fit(model, patterns, counts, max_iters=100, tol=1e-6, bp_eps=1e-3, bp_max_sweeps=0, prior=0.0, cpt_init=None):
-    """dict(cpt, iters, deltas [iters], thetas [iters] (the tables after every iteration), E and sweeps of every iteration, capped and
-    skipped summed over the iterations)."""
+def em_loop(model, e_step, max_iters, tol, prior, cpt_init, listed, summed):
+    """The loop of both EM restatements (this module's and jtem_refs'): e_step(model under theta) -> dict with "E" and more.
+    listed: {key of the result: key of the E-step's dict} collected per iteration beside E; summed: keys added up over the
+    iterations.  dict(cpt, iters, deltas [iters], thetas [iters] (the tables after every iteration), E, the listed, the summed)."""
     theta = np.asarray(model.cpt if cpt_init is None else cpt_init, dtype=np.float64).copy()
-    out = {"deltas": [], "thetas": [], "E": [], "sweeps": [], "capped": 0, "skipped": 0}
+    out = {"deltas": [], "thetas": [], "E": [], **{name: [] for name in listed}, **{name: 0 for name in summed}}
     for it in range(max_iters):
-        e = expected_counts(with_cpt(model, theta), patterns, counts, bp_eps, bp_max_sweeps)
+        e = e_step(with_cpt(model, theta))
         new = m_step(model, e["E"], prior)
         d = np.abs(new - theta)
         d = d[~np.isnan(d)]
@@ -210,13 +211,21 @@ def em_fit(model, patterns, counts, max_iters=100, tol=1e-6, bp_eps=1e-3, bp_max
         out["deltas"].append(delta)
         out["thetas"].append(theta.copy())
         out["E"].append(e["E"])
-        out["sweeps"].append(e["sweeps"])
-        out["capped"] += e["capped"]
-        out["skipped"] += e["skipped"]
+        for name, key in listed.items():
+            out[name].append(e[key])
+        for name in summed:
+            out[name] += e[name]
         if delta < tol:
             break
     out["cpt"], out["iters"], out["deltas"] = theta, len(out["deltas"]), np.asarray(out["deltas"])
     return out
+
+
+def em_fit(model, patterns, counts, max_iters=100, tol=1e-6, bp_eps=1e-3, bp_max_sweeps=0, prior=0.0, cpt_init=None):
+    """dict(cpt, iters, deltas [iters], thetas [iters] (the tables after every iteration), E and sweeps of every iteration, capped and
+    skipped summed over the iterations)."""
+    return em_loop(model, lambda m: expected_counts(m, patterns, counts, bp_eps, bp_max_sweeps), max_iters, tol, prior, cpt_init,
+                   listed={"sweeps": "sweeps"}, summed=("capped", "skipped"))
 
 
 def log_likelihood(model, patterns, counts):

@@ -127,25 +127,8 @@ def expected_counts(model, plan, patterns, counts):
 def em_fit(model, plan, patterns, counts, max_iters=100, tol=1e-6, prior=0.0, cpt_init=None):
     """dict(cpt, iters, deltas [iters], thetas [iters], E and L of every iteration (L under the tables the iteration started from),
     bounds, skipped summed over the iterations)."""
-    theta = np.asarray(model.cpt if cpt_init is None else cpt_init, dtype=np.float64).copy()
-    out = {"deltas": [], "thetas": [], "E": [], "L": [], "bounds": [], "skipped": 0}
-    for _ in range(max_iters):
-        e = expected_counts(em_refs.with_cpt(model, theta), plan, patterns, counts)
-        new = em_refs.m_step(model, e["E"], prior)
-        d = np.abs(new - theta)
-        d = d[~np.isnan(d)]
-        delta = float(d.max()) if d.size else 0.0
-        theta = new
-        out["deltas"].append(delta)
-        out["thetas"].append(theta.copy())
-        out["E"].append(e["E"])
-        out["L"].append(e["L"])
-        out["bounds"].append(e["bound"])
-        out["skipped"] += e["skipped"]
-        if delta < tol:
-            break
-    out["cpt"], out["iters"], out["deltas"] = theta, len(out["deltas"]), np.asarray(out["deltas"])
-    return out
+    return em_refs.em_loop(model, lambda m: expected_counts(m, plan, patterns, counts), max_iters, tol, prior, cpt_init,
+                           listed={"L": "L", "bounds": "bound"}, summed=("skipped",))
 
 
 # ---- enumeration of the joint in long double: the reference of the family posteriors and of log P(e) --------------------------------

@@ -247,6 +247,46 @@ def test_a_fit_leaves_the_other_call_families_alone(bnlib):
         assert jr.same_bits(got["beliefs"], alone_jt["beliefs"])
 
 
+EM_INFO = ("em_eligible", "em_last_iters", "em_capped", "em_skipped", "em_estep_ns", "em_mstep_ns", "em_scratch_cells")
+JT_EM_INFO = ("jt_em_last_iters", "jt_em_skipped", "jt_em_estep_ns", "jt_em_mstep_ns", "jt_em_last_form", "jt_em_last_launches",
+              "jt_em_scratch_cells")
+
+
+def test_the_two_fits_share_the_loop_and_no_state(bnlib):
+    """em_fit, jt_em_fit, em_fit on one engine: the two families run the same loop over states of their own.  257 rows (a block edge
+    inside the table), 100 rows per launch on both paths (launch edges inside a block)."""
+    from test_em_gpu import random_table, tiny
+    model = tiny("collider")
+    pats, counts = random_table(model, 257, 0.3, seed=257)
+    S = int(model.cpt_off[-1])
+    want_bp = em_refs.em_fit(model, pats, counts, max_iters=2, tol=0.0)
+    with Engine(model, device=0) as e:
+        want_jt = jtem_refs.em_fit(model, e.jt_plan(), pats, counts, max_iters=2, tol=0.0)
+        e.set_option("em_scratch_cells", 100 * S)
+        e.set_option("jt_em_scratch_cells", 100 * S + 3)
+        info = lambda names: {name: e.info(name) for name in names}
+
+        def bp_fit():
+            cpt, iters, hist = e.em_fit(pats, counts, max_iters=2, tol=0.0)
+            assert iters == want_bp["iters"] and np.array_equal(cpt, want_bp["cpt"], equal_nan=True) and np.array_equal(hist, want_bp["deltas"])
+            assert e.info("em_capped") == want_bp["capped"] and e.info("em_skipped") == want_bp["skipped"]
+            return cpt, hist, [e.info(name) for name in ("em_last_iters", "em_capped", "em_skipped")]
+
+        first = bp_fit()
+        em_before, jt_start = info(EM_INFO), info(JT_EM_INFO)
+        cpt, iters, hist, lls = e.jt_em_fit(pats, counts, max_iters=2, tol=0.0)
+        assert iters == want_jt["iters"] and jr.same_bits(cpt, want_jt["cpt"]) and jr.same_bits(hist, want_jt["deltas"])
+        assert close_ll(lls, want_jt["L"], want_jt["bounds"])
+        assert e.info("jt_em_skipped") == want_jt["skipped"] and e.info("jt_em_last_iters") == want_jt["iters"]
+        assert e.info("jt_em_last_launches") == 3
+        assert info(EM_INFO) == em_before                      # the tree's fit wrote nothing the em_* names read
+        jt_before = info(JT_EM_INFO)
+        assert jt_before != jt_start
+        third = bp_fit()
+        assert info(JT_EM_INFO) == jt_before                   # ... and the other way round
+        assert jr.same_bits(first[0], third[0]) and jr.same_bits(first[1], third[1]) and first[2] == third[2]
+
+
 def test_junction_tree_functor_and_reload(bnlib):
     model = synth.grid(3, 3, 2, seed=1)
     pats, counts = em_refs.sampled_table(model, 40, 0.3, seed=80)
