@@ -11,7 +11,8 @@ _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_
 _LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure", "TermTable",
              "SimulatedAnnealing", "StepwiseStructureHC")
 _EM = ("MISSING", "em_expected_counts", "em_fit", "jt_em_fit")
-__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING, *_EM]
+_INFERENCE = ("GibbsSampling",)
+__all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING, *_EM, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -23,6 +24,9 @@ def __getattr__(name):
         from . import learning
         return getattr(learning, name)
     if name in _EM:   # expectation-maximisation (engine.py): CPTs from a table with unobserved cells
+        from . import engine
+        return getattr(engine, name)
+    if name in _INFERENCE:   # Gibbs sampling (engine.py), beside engine.LikelihoodWeighting
         from . import engine
         return getattr(engine, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -395,6 +395,11 @@ extern "C" int bn_set_option(bn_engine* e, const char* name, int32_t value) {
         const int rc = jt_set_option(e, name, value, &known);
         if (known) return rc;
     }
+    if (std::strncmp(name, "gibbs_", 6) == 0) {   // Gibbs sampling: "gibbs_sweeps_per_launch" (bn_engine_gibbs.cpp)
+        bool known = false;
+        const int rc = gibbs_set_option(e, name, value, &known);
+        if (known) return rc;
+    }
     return fail(BN_ERR_ARG, std::string("unknown option ") + name);
 }
 // Introspection for tests and tools: a named integer property of the engine / its last run.
@@ -479,6 +484,11 @@ extern "C" int64_t bn_get_info(bn_engine* e, const char* name) {
     if (std::strncmp(name, "jt_", 3) == 0) {   // junction tree: "jt_eligible", "jt_form", "jt_cliques", ... (bn_engine_jt.cpp)
         bool known = false;
         const int64_t v = jt_get_info(e, name, &known);
+        if (known) return v;
+    }
+    if (std::strncmp(name, "gibbs_", 6) == 0) {   // Gibbs sampling: "gibbs_eligible", "gibbs_colours", ... (bn_engine_gibbs.cpp)
+        bool known = false;
+        const int64_t v = gibbs_get_info(e, name, &known);
         if (known) return v;
     }
     return fail(BN_ERR_ARG, std::string("unknown info ") + name);

@@ -9,8 +9,8 @@
 // (dense) engine, the entry points and their dispatch; bn_engine_batch_paths.cpp: the five runs of a batch and what they share;
 // bn_batch_stage.hpp / .cpp: the layout of a batch's evidence staging block (no HIP either); bn_engine_shard.cpp: RCCL communicator
 // and the in-kernel exchange of sharded engines; bn_engine_tools.cpp: plan / layout introspection, bn_reload_cpt, the samplers' and
-// the fit's entry points; bn_engine_mpe.cpp, bn_engine_em.cpp, bn_engine_jt.cpp, bn_engine_jt_em.cpp: max-product,
-// expectation-maximisation, junction-tree propagation and exact expectation-maximisation, each over a state of its own.  No CPU compute path exists in any of them: every result comes from the
+// the fit's entry points; bn_engine_mpe.cpp, bn_engine_em.cpp, bn_engine_jt.cpp, bn_engine_jt_em.cpp, bn_engine_gibbs.cpp: max-product,
+// expectation-maximisation, junction-tree propagation, exact expectation-maximisation and Gibbs sampling, each over a state of its own.  No CPU compute path exists in any of them: every result comes from the
 // kernels.
 #ifndef BN_ENGINE_INTERNAL_HPP
 #define BN_ENGINE_INTERNAL_HPP
@@ -44,6 +44,7 @@
 #include "bn_maxprod.hpp"
 #include "bn_em.hpp"
 #include "bn_jt.hpp"
+#include "bn_gibbs.hpp"
 
 using namespace bnmi;
 
@@ -267,6 +268,29 @@ struct JtEmState {
     int64_t cap_scratch = 0;
     int32_t last_form = 0;              // the last call
     int64_t last_launches = 0;
+};
+
+// Gibbs sampling (bn_engine_gibbs.cpp, bn_gibbs.hip): the plan (built at the first call that asks for it), its tables and its own
+// copy of the flat CPTs on the device, the chains' states, the histogram -- allocated at the first run.  A bn_gibbs_run call
+// that starts its chains itself draws them with the sampler (bn_lw_run's state, as a bn_lw_run call of the same range leaves it);
+// nothing else of the engine is read or written, and nothing here by any other call family.
+struct GibbsState {
+    int32_t sweeps_option = 0;          // option "gibbs_sweeps_per_launch" (0: the plan's default)
+    GibbsPlan plan;
+    bool tried = false;                 // the planner has run
+    bool uploaded = false;              // the tables are on the device
+    bool cpt_ready = false;             // ... and the CPTs in force
+    DeviceBuf<int32_t> d_colour_ptr;
+    DeviceBuf<GibbsSlot> d_slots;
+    DeviceBuf<GibbsChild> d_children;
+    DeviceBuf<GibbsTerm> d_terms;
+    DeviceBuf<double> d_cpt;
+    DeviceBuf<int16_t> d_clamp;         // [n]
+    DeviceBuf<unsigned long long> d_words;   // [cells] the histogram, then [1] the stuck count
+    DeviceBuf<uint8_t> d_states;        // [cap_chains][n]
+    uint64_t cap_chains = 0;
+    // the last call
+    int64_t last_launches = 0, last_kernel_ns = 0;
 };
 
 struct bn_engine {
@@ -506,6 +530,7 @@ struct bn_engine {
     EmState em;
     JtState jt;
     JtEmState jt_em;
+    GibbsState gibbs;
 };
 
 
@@ -691,6 +716,10 @@ JtTables jt_tables_of(const JtState& j, const double* psi0);   // ... as the ker
 // the "jt_em_*" names (bn_engine_jt_em.cpp)
 int jt_em_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
 int64_t jt_em_get_info(bn_engine* e, const char* name, bool* known);
+// the "gibbs_*" names (bn_engine_gibbs.cpp)
+int gibbs_set_option(bn_engine* e, const char* name, int32_t value, bool* known);
+int64_t gibbs_get_info(bn_engine* e, const char* name, bool* known);
+void gibbs_cpt_reloaded(bn_engine* e);   // bn_reload_cpt: the tables are copied again at the next run
 // The table of bn_em_* and bn_jt_em_*: its arguments, then (behind whatever else the entry point checks of its arguments) its cells
 inline int em_check_table_args(const bn_engine* e, int64_t n_patterns, const uint8_t* patterns, const uint64_t* counts) {
     if (!e) return fail(BN_ERR_ARG, "null engine");

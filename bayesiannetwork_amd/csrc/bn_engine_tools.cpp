@@ -136,6 +136,7 @@ extern "C" int bn_reload_cpt(bn_engine* e, const double* cpt, int64_t n_entries)
         e->score.ready = false;   // (the log table of bn_score_*: taken again from the new values at the next call)
         mpe_cpt_reloaded(e);      // (max-product's own several-workgroup tables, where it built any: rebuilt at its next run)
         jt_cpt_reloaded(e);       // (the junction tree's base potentials: computed from the new tables at its next run)
+        gibbs_cpt_reloaded(e);    // (Gibbs sampling's copy of the flat tables: taken again at its next run)
         memo0_invalidate(e);      // (the first-sweep image of the resident path: rebuilt by the next run that can use it)
         if (e->host_only) return BN_OK;
         e->poisoned = true;   // until every image has arrived

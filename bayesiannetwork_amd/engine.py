@@ -554,6 +554,42 @@ class Engine:
                                            _p(weights, ctypes.c_double)))
         return states, weights
 
+    # ---- Gibbs sampling ----------------------------------------------------------------
+    def gibbs_run(self, ev_state, n_chains: int, n_sweeps: int, seed: int, burn_in: int = 0, thin: int = 1, chain_begin: int = 0,
+                  sweep_begin: int = 0, init_states=None) -> dict:
+        """bn_gibbs_run: sweeps [sweep_begin, +n_sweeps) of chains [chain_begin, +n_chains), evidence nodes (ev_state >= 0) clamped.
+        Returns dict(counts uint64 [sum k], states uint8 [n_chains][n] after the last sweep, stuck, kept = kept sweeps x chains).
+        init_states None: the chains start from the states lw_run draws for the same seed, evidence and ids."""
+        ev_state = np.asarray(ev_state, dtype=np.int32)
+        nodes = np.ascontiguousarray(np.nonzero(ev_state >= 0)[0], dtype=np.int32)
+        states = np.ascontiguousarray(ev_state[nodes], dtype=np.int32)
+        n = self.model.n
+        init = None
+        if init_states is not None:
+            init = np.ascontiguousarray(init_states, dtype=np.uint8)
+            if init.size != n_chains * n:
+                raise ValueError("init_states must hold n_chains x n states")
+        counts = np.zeros(max(self._nbel, 1), dtype=np.uint64)
+        out = np.zeros((n_chains, n), dtype=np.uint8)
+        stuck, kept = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(_lib.lib().bn_gibbs_run(self._h, nodes.size, _p(nodes, ctypes.c_int32), _p(states, ctypes.c_int32),
+                                           ctypes.c_uint64(chain_begin), ctypes.c_uint64(n_chains), ctypes.c_uint64(sweep_begin),
+                                           ctypes.c_uint64(n_sweeps), ctypes.c_uint64(burn_in), ctypes.c_uint64(thin), ctypes.c_uint64(seed),
+                                           None if init is None else _p(init, ctypes.c_uint8), _p(counts, ctypes.c_uint64),
+                                           _p(out, ctypes.c_uint8), ctypes.byref(stuck), ctypes.byref(kept)))
+        return {"counts": counts[:self._nbel], "states": out, "stuck": stuck.value, "kept": kept.value}
+
+    def gibbs_plan(self) -> dict:
+        """bn_gibbs_plan_info: the colouring of the moral graph and the launch shape (also on host-only engines).  Raises BnError
+        (BN_ERR_STATE, with the planner's reason) where the network is beyond the limits of the form."""
+        d = np.zeros(8, dtype=np.int64)
+        colour = np.zeros(max(self.model.n, 1), dtype=np.int32)
+        _lib.check(_lib.lib().bn_gibbs_plan_info(self._h, _p(colour, ctypes.c_int32), _p(d, ctypes.c_int64)))
+        names = ("eligible", "colours", "threads", "chains_per_workgroup", "lds_bytes", "sweeps_per_launch", "max_class", "reads_per_sweep")
+        plan = {k: int(v) for k, v in zip(names, d)}
+        plan["colour"] = colour[:self.model.n]
+        return plan
+
     # ---- layout ------------------------------------------------------------------------
     def layout(self) -> dict:
         li = _lib.LayoutInfo()
@@ -900,6 +936,30 @@ class LikelihoodWeighting:
                 break
         patterns = {tuple(np.frombuffer(key, dtype=np.uint8).tolist()): c for key, c in table.items()}
         return patterns, _split(self.model, prob)
+
+
+class GibbsSampling:
+    """Gibbs sampling (bn_gibbs_run; the reference has no counterpart): ``gs = GibbsSampling(model); marg = gs({node: state})``.
+    Chains move inside the evidence, so the marginals converge where the evidence is unlikely and likelihood weighting's weights
+    vanish.  ``self.last``: the raw result of the last call (counts, states, stuck, kept)."""
+
+    def __init__(self, model: FlatModel, device: int = _lib.BN_DEVICE_CURRENT, seed: int = 0x5EED):
+        self.engine = Engine(model, device)
+        self.model = model
+        self.seed = seed
+        self._next = 0
+        self.last = None
+
+    def __call__(self, evidence=None, chains: int = 4096, sweeps: int = 200, burn_in: int = 100, thin: int = 1):
+        """Per-node marginals counts / kept over `chains` fresh chains of `sweeps` sweeps, the first `burn_in` not counted."""
+        ev_state = np.full(self.model.n, -1, dtype=np.int32)
+        for v, s in (evidence or {}).items():
+            ev_state[v] = s
+        self.last = self.engine.gibbs_run(ev_state, chains, sweeps, self.seed, burn_in=burn_in, thin=thin, chain_begin=self._next)
+        self._next += chains  # successive calls run fresh chains, as the sampler's calls draw fresh samples
+        if self.last["kept"] == 0:
+            raise ValueError("Gibbs sampling: no sweep was kept (burn_in is not below sweeps, or no chains)")
+        return _split(self.model, self.last["counts"].astype(np.float64) / float(self.last["kept"]))
 
 
 def normalize_histogram(model: FlatModel, hist: np.ndarray) -> np.ndarray:

@@ -589,6 +589,53 @@ int bn_fit_cpt(const bn_model_desc *structure, int64_t n_patterns, const uint8_t
 /* Sampled states of the first `n` samples of the last bn_lw_run, sample-major [s][node]. */
 int bn_lw_states(bn_engine *eng, uint64_t n, uint8_t *states_out, double *weights_out);
 
+/*
+ * Gibbs sampling: independent Markov chains over the states of all nodes, hard evidence clamped.  The reference has no
+ * counterpart.  Unlike likelihood weighting and rejection sampling, which draw from the prior, a chain moves inside the evidence:
+ * it converges where P(e) is small, on networks too dense for the junction tree.
+ * Runs sweeps [sweep_begin, sweep_begin + n_sweeps) of chains [chain_begin, chain_begin + n_chains) (64-bit chain ids).
+ *   Start: init_states == NULL: chain c starts from the states bn_lw_run with the same `seed` and evidence draws for sample id c
+ *     (the weight is ignored): bn_lw_states after a bn_lw_run of the same range returns exactly the chains' starting states.  The
+ *     call uses the sampler to draw them, so it leaves the sampler's last batch as that bn_lw_run would.  init_states
+ *     [n_chains][n]: those; evidence nodes are overwritten by their clamp; a state >= the node's arity elsewhere is BN_ERR_ARG.
+ *   Scan order: the moral graph (a node joined to its parents, its children and its children's other parents) is coloured once
+ *     per engine, whatever the evidence: nodes in ascending index, each takes the smallest colour no moral neighbour holds.  A
+ *     sweep visits the colours 0, 1, ... and inside a colour every free node.  Nodes of one colour share no family: the GPU
+ *     updates them at once, which equals the sequential scan in (colour, node index) order.
+ *   One update of node v, fp64, no contraction: for x = 0 .. k[v] - 1
+ *       w[x] = cpt_v[row_v][x] x cpt_c[row_c(x)][s_c] for every child c of v in ascending child index (one multiply each);
+ *       row_c(x) is c's row with v at x, first parent most significant;
+ *     T = w[0] + w[1] + ... left to right.  T not a finite number above 0: the state is kept and `stuck` goes up by one.  Else
+ *     t = u x T (one multiply) and the new state is the first x with t < c_x, c_x the same running sum; none: the last x with
+ *     w[x] > 0.
+ *   The uniform is a pure function of (seed, chain c, sweep g, node v): ONE Philox4x32-10 block, counter {v, g, c_lo, c_hi}, key
+ *     {seed_lo, seed_hi ^ 0x47494253} (the tag keeps these blocks apart from the sampler's stream seeds);
+ *     U = (out0 << 21) | (out1 >> 11), u = U x 2^-53.  g is the global sweep number, below 2^32 (else BN_ERR_ARG).
+ *   Kept: after sweep g with g >= burn_in and (g - burn_in) % thin == 0 every node's state (evidence nodes too) adds 1 to
+ *     counts_out[node_off[v] + state]: unsigned 64-bit counts, the same whatever the order of the additions.
+ *     *kept_out = kept sweeps x n_chains: marginals are counts / kept.  *stuck_out: updates that kept the state because T was
+ *     not a finite number above 0 (a start that contradicts the evidence in a network with zeros).  Both may be NULL.
+ *   states_out (may be NULL) [n_chains][n]: the states after the last sweep.  n_sweeps == 0: the starting states, zero counts.
+ *   Continuity: sweeps [0, a) and then [a, b) from the first run's states_out (sweep_begin = a) give the states of one run of
+ *     [0, b), and the two counts add up to its counts; disjoint chain ranges add up the same way (several GPUs, several calls).
+ * thin == 0, an unknown evidence node or state, a node listed twice: BN_ERR_ARG.
+ * Eligible (bn_get_info "gibbs_eligible"; bn_gibbs_plan_info): n <= 4096 nodes and arities summing to <= 8192 -- a chain's states and
+ * a workgroup's histogram live in LDS; beyond, and on sharded engines, BN_ERR_STATE with the planner's reason in bn_last_error and
+ * no launch.  BN_DEVICE_HOST_ONLY engines: BN_ERR_NO_DEVICE.  The plan is built at first use and survives bn_reload_cpt, after
+ * which the runs read the new tables.  A run is split into launches of at most bn_set_option "gibbs_sweeps_per_launch" sweeps
+ * (0: the default, bn_get_info "gibbs_sweeps_per_launch": up to 256, fewer where a sweep reads many table entries); the chains'
+ * states rest in device memory between launches and the split changes no bit.  bn_get_info "gibbs_colours", "gibbs_lds_bytes",
+ * "gibbs_last_launches", "gibbs_last_kernel_ns" (option "timing" 1: HIP events around the launches).
+ */
+int bn_gibbs_run(bn_engine *eng, int32_t ne, const int32_t *ev_node, const int32_t *ev_state,
+                 uint64_t chain_begin, uint64_t n_chains, uint64_t sweep_begin, uint64_t n_sweeps,
+                 uint64_t burn_in, uint64_t thin, uint64_t seed, const uint8_t *init_states,
+                 uint64_t *counts_out, uint8_t *states_out, uint64_t *stuck_out, uint64_t *kept_out);
+/* The plan of bn_gibbs_run (also on host-only engines): colour_out [n] (may be NULL) the colour of every node; dims_out[8] =
+ * eligible (1), colours, threads of a workgroup, chains of a workgroup, LDS bytes of a workgroup, sweeps per launch, nodes of
+ * the largest colour, table entries one chain reads per sweep.  Not eligible: BN_ERR_STATE, bn_last_error has the reason. */
+int bn_gibbs_plan_info(bn_engine *eng, int32_t *colour_out, int64_t *dims_out);
+
 /* ---- entropy and mutual information over a pattern table ----
  * Replaces: bn::evaluation::entropy / mutual_information (bayesian/evaluation/transinformation.hpp:10-84),
  * which the reference declares but cannot compile (entropy::operator() calls lower_bound / key_comp on an
