@@ -48,6 +48,12 @@ class HcParams(ctypes.Structure):
                 ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
 
 
+class ClimbParams(ctypes.Structure):
+    _fields_ = [("max_parents", ctypes.c_int32), ("tabu_len", ctypes.c_int32), ("max_worse", ctypes.c_uint32),
+                ("max_steps", ctypes.c_uint32), ("perturb", ctypes.c_uint32), ("trace_run", ctypes.c_int32),
+                ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
 class EmOptions(ctypes.Structure):   # bn_em_options
     _fields_ = [("max_iters", ctypes.c_int32), ("tol", ctypes.c_double), ("bp_eps", ctypes.c_double), ("bp_max_sweeps", ctypes.c_int32),
                 ("prior", ctypes.c_double)]
@@ -191,6 +197,8 @@ SYMBOLS = [
                                        ctypes.c_void_p, i32p]),
     ("bn_learn_hc", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HcParams), ctypes.c_int32, ctypes.c_uint64, f64p, f64p,
                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p, i32p]),
+    ("bn_learn_climb", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ClimbParams), ctypes.c_int32, ctypes.c_uint64, f64p,
+                                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p]),
     ("bn_learn_score_groups_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, i32p, i32p, i32p, i32p, i32p,
                                                   f64p, ctypes.POINTER(ctypes.c_uint64)]),
     ("bn_learn_score_subsets_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, ctypes.c_int32, i32p,

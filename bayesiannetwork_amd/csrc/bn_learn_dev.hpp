@@ -27,8 +27,8 @@ __device__ __forceinline__ void wave_sync() {
 
 __device__ __forceinline__ uint32_t draw_below(uint4& g, uint32_t m) { return uint32_t((uint64_t(xoshiro_next(g)) * m) >> 32); }
 
-// ll(c, mask) from the term table; mask has at most q bits, all below n, and not bit c
-__device__ __forceinline__ double term_of(const double* __restrict__ terms, int64_t T, const uint32_t* tab, int c, uint64_t mask) {
+// the index of parent set `mask` in child c's row of the term table; mask has at most q bits, all below n, and not bit c
+__device__ __forceinline__ uint32_t rank_of(const uint32_t* tab, int c, uint64_t mask) {
     uint32_t rank = 0;
     int j = 0;
     while (mask) {
@@ -37,8 +37,12 @@ __device__ __forceinline__ double term_of(const double* __restrict__ terms, int6
         ++j;
         rank += tab[kAnnealTabBinom + j * 64 + (s - (s > c ? 1 : 0))];
     }
-    rank += tab[j];
-    return terms[int64_t(c) * T + rank];
+    return rank + tab[j];
+}
+
+// ll(c, mask) from the term table
+__device__ __forceinline__ double term_of(const double* __restrict__ terms, int64_t T, const uint32_t* tab, int c, uint64_t mask) {
+    return terms[int64_t(c) * T + rank_of(tab, c, mask)];
 }
 
 // the learner's score of the graph whose family terms the lanes hold in x: likelihood -= ll[v] in node order through lane reads (no

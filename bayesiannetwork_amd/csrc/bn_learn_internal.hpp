@@ -2,7 +2,7 @@
 // bn_learn_plan.cpp: the host-only planning of a batch; bn_learn_batch.cpp: run_groups / run_subsets on the device and the
 // bn_learn_score_* entry points; bn_learn.cpp: the bn_learner object and bn_learn_try_parents (reference greedy.hpp, k2_algorithm.hpp);
 // bn_learn_exhaustive.cpp: bn_learn_best_parents and the brute-force searches (brute_force.hpp); bn_learn_terms.cpp: bn_term_table;
-// bn_learn_search.cpp: the device-resident searches over a term table, bn_learn_anneal and bn_learn_hc.
+// bn_learn_search.cpp: the device-resident searches over a term table, bn_learn_anneal, bn_learn_hc and bn_learn_climb.
 #ifndef BN_LEARN_INTERNAL_HPP
 #define BN_LEARN_INTERNAL_HPP
 #include <cmath>
@@ -29,6 +29,8 @@ struct LearnTimes {
     int64_t anneal_chains = 0, anneal_steps = 0;
     double hc_ns = 0.0;        // the hierarchical-clustering kernel
     int64_t hc_runs = 0, hc_merges = 0;
+    double climb_ns = 0.0;     // the hill-climbing kernel
+    int64_t climb_runs = 0, climb_steps = 0;
 };
 
 // The family term: kind 0 the log-likelihood term (AIC / MDL), 2 BDeu, 3 K2.  Held normalised (ess 0.0 where the kind does not

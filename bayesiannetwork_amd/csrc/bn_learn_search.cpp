@@ -1,8 +1,10 @@
 // bn_learn_search.cpp -- the device-resident structure searches over a term table (bn_learn_terms.cpp): bn_learn_anneal runs the
 // reference's simulated_annealing.hpp as many chains (bn_learn_anneal.hip), bn_learn_hc its stepwise_structure_hc.hpp as many runs
-// (bn_learn_hc.hip).  Both end alike: the run with the smallest score becomes the learner's graph (finish_search).
+// (bn_learn_hc.hip), bn_learn_climb tabu hill climbing as many runs (bn_learn_climb.hip).  All end alike: the run with the smallest
+// score becomes the learner's graph (finish_search).
 #include "bn_learn_internal.hpp"
 #include "bn_learn_anneal.hpp"
+#include "bn_learn_climb.hpp"
 #include "bn_learn_hc.hpp"
 
 namespace {
@@ -35,7 +37,7 @@ void adopt_winner(bn_learner* L, const std::vector<uint64_t>& win_mask, const st
     L->score = score;
 }
 
-// The tail of both searches, entered once the kernel and the event pair (ev0, ev1) around it are on the stream and the per-run scores
+// The tail of every search, entered once the kernel and the event pair (ev0, ev1) around it are on the stream and the per-run scores
 // are on the host: the winner is the run of the smallest score, strictly (ties stay with the lowest index); its row of `d_masks`
 // and `d_ll` ([runs][n]) and, where asked for, every run's masks are downloaded together with what `more()` enqueues; the
 // kernel's time is added to `ns`; the winner becomes the learner's graph.
@@ -289,5 +291,107 @@ extern "C" int bn_learn_hc(bn_learner* L, bn_term_table* tt, const bn_hc_params*
         }
     }
     if (n_trace_out) *n_trace_out = int32_t(n_trace);
+    return BN_OK;
+}
+
+// ---- tabu hill climbing: steepest descent over add, delete and reverse moves, a tabu list, perturbed restarts -------------------------
+
+static_assert(sizeof(bn_climb_trace) == sizeof(ClimbTrace) && sizeof(ClimbTrace) == 32, "the trace record is the ABI's");
+static_assert(sizeof(ClimbRecord) == 32, "one record per run");
+
+extern "C" int bn_learn_climb(bn_learner* L, bn_term_table* tt, const bn_climb_params* p, int32_t runs, uint64_t seed, double* score_out,
+                              uint32_t* counts_out, uint64_t* masks_out, bn_climb_trace* trace_out, int32_t* winner_out) {
+    if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
+    const int32_t n = L->n, q = tt->q;
+    if (n > kAnnealMaxNodes) return fail(BN_ERR_ARG, "climb: " + std::to_string(n) + " nodes (at most 64: a node has a lane)");
+    if (tt->t != L->t) return fail(BN_ERR_ARG, "climb: the term table was built from another table than the learner's");
+    if (int r = check_table_spec("climb", L, tt)) return r;
+    if (runs < 1 || runs > kClimbMaxRuns) return fail(BN_ERR_ARG, "climb: " + std::to_string(runs) + " runs (1 .. 65536)");
+    if (p->tabu_len < 0 || p->tabu_len > kClimbMaxTabu) return fail(BN_ERR_ARG, "climb: tabu_len " + std::to_string(p->tabu_len) + " (0 .. 64)");
+    if (p->max_steps > kClimbMaxSteps)
+        return fail(BN_ERR_ARG, "climb: max_steps " + std::to_string(p->max_steps) + " (at most 2^20 = " + std::to_string(kClimbMaxSteps) + ")");
+    if (p->perturb > kClimbMaxPerturb)
+        return fail(BN_ERR_ARG, "climb: perturb " + std::to_string(p->perturb) + " (at most 2^16 = " + std::to_string(kClimbMaxPerturb) + ")");
+    if (p->max_parents < 1) return fail(BN_ERR_ARG, "climb: max_parents " + std::to_string(p->max_parents) + " (at least 1)");
+    if (p->trace_run < -1 || p->trace_run >= runs) return fail(BN_ERR_ARG, "climb: trace_run out of range");
+    const bool tracing = p->trace_run >= 0 && trace_out && p->trace_cap > 0;
+    std::vector<uint64_t> pmask(size_t(n), 0);
+    std::vector<int64_t> rows(size_t(n), 1);
+    for (int32_t v = 0; v < n; ++v) {
+        if (int32_t(L->parents[size_t(v)].size()) > q)
+            return fail(BN_ERR_ARG, "climb: node " + std::to_string(v) + " starts with " + std::to_string(L->parents[size_t(v)].size()) +
+                                        " parents (the term table holds at most " + std::to_string(q) + ")");
+        for (int32_t u : L->parents[size_t(v)]) pmask[size_t(v)] |= uint64_t(1) << u;
+        rows[size_t(v)] = L->rows_of(v);
+    }
+    bn_info_table* t = L->t;
+    ON_DEVICE(t);
+    hipStream_t s = t->stream;
+    DeviceBuf<uint64_t> d_pmask, d_masks;
+    DeviceBuf<int64_t> d_rows;
+    DeviceBuf<double> d_ll0, d_ll;
+    DeviceBuf<ClimbRecord> d_rec;
+    DeviceBuf<ClimbTrace> d_trace;
+    EventOwner ev0, ev1;
+    int r;
+    if ((r = upload(d_pmask, pmask, s)) || (r = upload(d_rows, rows, s)) || (r = upload(d_ll0, L->ll, s)) || (r = dalloc(d_rec, size_t(runs))) ||
+        (r = dalloc(d_masks, size_t(runs) * size_t(n))) || (r = dalloc(d_ll, size_t(runs) * size_t(n))))
+        return r;
+    if (tracing && (r = dalloc(d_trace, size_t(p->trace_cap)))) return r;
+    HIPCHK(hipEventCreate(ev0.put()));
+    HIPCHK(hipEventCreate(ev1.put()));
+    ClimbArgs a{};
+    a.terms = tt->d_terms;
+    a.tab = tt->d_tab;
+    a.T = tt->T;
+    a.k = tt->d_k;
+    a.pmask0 = d_pmask;
+    a.rows0 = d_rows;
+    a.ll0 = d_ll0;
+    a.n = n;
+    a.q = q;
+    a.max_parents = std::min(p->max_parents, std::min(q, L->max_parents));
+    a.criterion = L->criterion;
+    a.params0 = L->params;
+    a.penalty = L->penalty;
+    a.tabu_len = p->tabu_len;
+    a.max_worse = p->max_worse;
+    a.max_steps = p->max_steps == 0 ? (1u << 16) : p->max_steps;
+    a.perturb = p->perturb;
+    a.seed_lo = uint32_t(seed);
+    a.seed_hi = uint32_t(seed >> 32);
+    a.runs = runs;
+    a.trace_run = tracing ? p->trace_run : -1;
+    a.trace_cap = tracing ? p->trace_cap : 0;
+    a.rec = d_rec;
+    a.masks = d_masks;
+    a.ll = d_ll;
+    a.trace = tracing ? d_trace.get() : nullptr;
+    HIPCHK(hipEventRecord(ev0, s));
+    if (int err = learn_launch_climb(a, s)) return fail(BN_ERR_HIP, std::string("hill-climbing kernel: ") + hipGetErrorString(hipError_t(err)));
+    HIPCHK(hipEventRecord(ev1, s));
+    std::vector<ClimbRecord> rec(static_cast<size_t>(runs));
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, size_t(runs) * sizeof(ClimbRecord), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<double> score(static_cast<size_t>(runs));
+    for (int32_t j = 0; j < runs; ++j) score[size_t(j)] = rec[size_t(j)].best_eval;
+    auto more = [&]() -> int {
+        if (tracing) {
+            const size_t len = std::min<size_t>(rec[size_t(p->trace_run)].steps, p->trace_cap);
+            if (len > 0) HIPCHK(hipMemcpyAsync(trace_out, d_trace, len * sizeof(ClimbTrace), hipMemcpyDeviceToHost, s));
+        }
+        return BN_OK;
+    };
+    if (int err = finish_search(L, s, score, d_masks, d_ll, masks_out, ev0, ev1, L->times.climb_ns, winner_out, more)) return err;
+    L->times.climb_runs += runs;
+    for (int32_t j = 0; j < runs; ++j) {
+        const ClimbRecord& x = rec[size_t(j)];
+        L->times.climb_steps += x.steps;
+        if (score_out) score_out[j] = x.best_eval;
+        if (counts_out) {
+            uint32_t* c = counts_out + 6 * size_t(j);
+            c[0] = x.steps; c[1] = x.improving; c[2] = x.perturbed; c[3] = x.best_step; c[4] = x.flags; c[5] = x.tabu_legal;
+        }
+    }
     return BN_OK;
 }

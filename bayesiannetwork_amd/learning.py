@@ -12,7 +12,8 @@ functors on top of it.  `score_subsets` scores EVERY subset of a candidate paren
 the reference's simulated annealing (simulated_annealing.hpp) as many independent device-resident chains over it, and
 `SimulatedAnnealing` is the reference's functor on top of that.  `Learner.hc` runs the reference's hierarchical clustering with
 stochastic pruning (stepwise_structure_hc.hpp) as many device-resident runs over the same table and the all-pairs mutual
-information; `StepwiseStructureHC` is its functor.
+information; `StepwiseStructureHC` is its functor.  `Learner.climb` is tabu hill climbing over add, delete and reverse moves (not in
+the reference) as device-resident runs over the same table; `HillClimbing` is its functor.
 The learner's score takes the DEVICE's fp64 logarithm (the header states the function); `AIC` / `MDL` of
 the learned model through evaluation.py agree with it to a few ulp per term, not bit for bit.
 
@@ -341,6 +342,37 @@ class Learner:
                                                    names="cluster,connections,value_bits,pruned")
         return out
 
+    def climb(self, term_table: "TermTable", tabu_len: int = 0, max_worse: int = 0, runs: int = 1, perturb: int = 0, seed: int = 0,
+              max_parents=None, max_steps: int = 0, trace_run=None, trace_cap: int = 0) -> dict:
+        """Tabu hill climbing (bn_learn_climb) as `runs` independent runs on the device: steepest descent over the add, delete
+        and reverse moves, a move on a node pair tabu for `tabu_len` applied steps, up to `max_worse` steps in a row without a new
+        best.  Run 0 starts from this learner's graph, run j >= 1 from that graph after `perturb` random proposals of stream (seed,
+        j).  The best graph of the run with the strictly smallest score (the lowest among equals) becomes this learner's graph.
+        max_parents: the in-degree a run refuses at (default and at most the term table's); max_steps 0: 2^16.  Returns the per-run
+        records: score [runs], steps / improving / perturbed / best_step / flags / tabu_legal [runs] (CLIMB_* bits), masks
+        [runs][n] (bit u of masks[j][v]: u -> v), winner, and with trace_run the structured array `trace` (CLIMB_TRACE_DTYPE) of
+        that run's applied steps (the first trace_cap; 0: max_steps)."""
+        runs = int(runs)
+        self._check_terms(term_table)
+        tracing = trace_run is not None
+        cap = (int(trace_cap) or int(max_steps) or (1 << 16)) if tracing else 0
+        p = _lib.ClimbParams(int(term_table.max_parents if max_parents is None else max_parents), int(tabu_len), int(max_worse), int(max_steps),
+                             int(perturb), int(trace_run) if tracing else -1, cap, 0)
+        c = max(runs, 1)
+        score = np.zeros(c)
+        counts = np.zeros((c, 6), dtype=np.uint32)
+        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
+        trace = np.zeros(max(cap, 1), dtype=CLIMB_TRACE_DTYPE)
+        winner = ctypes.c_int32()
+        _lib.check(_lib.lib().bn_learn_climb(self._h, term_table._h, ctypes.byref(p), runs, int(seed) & (2 ** 64 - 1), _p(score, ctypes.c_double),
+                                             _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), trace.ctypes.data if tracing else None,
+                                             ctypes.byref(winner)))
+        out = {name: counts[:, i].copy() for i, name in enumerate(("steps", "improving", "perturbed", "best_step", "flags", "tabu_legal"))}
+        out.update({"score": score, "masks": masks[:, :self.n], "winner": winner.value})
+        if tracing:
+            out["trace"] = trace[:min(int(out["steps"][int(trace_run)]), cap)].copy()
+        return out
+
     def score(self) -> float:
         out = ctypes.c_double()
         _lib.check(_lib.lib().bn_learn_score(self._h, ctypes.byref(out)))
@@ -369,6 +401,9 @@ END_TEMPERATURE, END_SAME_STATE, END_CAP = 1, 2, 4   # flags of a chain's record
 _RULES = {"reference": 0, "metropolis": 1}
 HC_TRACE_DTYPE = np.dtype([("value_bits", np.uint64), ("kind", np.uint8), ("a", np.uint8), ("b", np.uint8), ("c", np.uint8), ("pad", np.uint32)])
 HC_ONE_CLUSTER, HC_NO_SIMILARITY = 1, 2   # flags of a run's record
+CLIMB_TRACE_DTYPE = np.dtype([("d_bits", np.uint64), ("current_bits", np.uint64), ("kind", np.uint8), ("from", np.uint8), ("to", np.uint8),
+                              ("pad8", np.uint8), ("pad32", np.uint32), ("pad", np.uint64)])
+CLIMB_NO_MOVE, CLIMB_LOCAL_OPTIMUM, CLIMB_CAP = 1, 2, 4   # flags of a hill-climbing run's record
 
 
 class TermTable:
@@ -663,6 +698,46 @@ class SimulatedAnnealing(_Search):
             self._calls += 1
             out = self._finish(model, L)
             self.last.update({name: L.info(name) for name in ("anneal_ns", "anneal_chains", "anneal_steps")})
+            self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
+                              "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+            return out
+
+
+class HillClimbing(_Search):
+    """Tabu hill climbing over add, delete and reverse moves (Learner.climb; the search of bnlearn's hc / tabu and pgmpy's
+    HillClimbSearch, not in the reference).  `hc(model, tabu_len=0, max_worse=0, perturb=0, max_steps=0)`: `runs` independent runs,
+    run 0 from the model's graph and the others from perturbed copies of it, the best graph returned as (FlatModel with CPTs
+    fitted to it, score).  max_parents (default 3) bounds the in-degree: the family terms of every parent set up to it are computed
+    once, into a TermTable kept for the object's lifetime.  Run j of call number i uses the stream (seed + i, j); without a seed one
+    is drawn.  `last` also holds the climb counters, the winning run and the term table's."""
+
+    def __init__(self, criterion, sampling, max_parents: int = 3, runs: int = 1, seed=None, device: int = _lib.BN_DEVICE_CURRENT):
+        super().__init__(criterion, sampling, max_parents, seed, device)
+        self._runs = int(runs)
+        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
+        self._calls = 0
+        self._terms = None
+        self.records = None   # Learner.climb's records of the last call
+
+    def close(self) -> None:
+        if getattr(self, "_terms", None) is not None:
+            self._terms.close()
+            self._terms = None
+
+    __del__ = close
+
+    def term_table(self, model) -> TermTable:
+        if self._terms is None:
+            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
+        return self._terms
+
+    def __call__(self, model, tabu_len: int = 0, max_worse: int = 0, perturb: int = 0, max_steps: int = 0):
+        terms = self.term_table(model)
+        with self._learner(model) as L:
+            self.records = L.climb(terms, tabu_len, max_worse, self._runs, perturb, self._seed + self._calls, max_steps=max_steps)
+            self._calls += 1
+            out = self._finish(model, L)
+            self.last.update({name: L.info(name) for name in ("climb_ns", "climb_runs", "climb_steps")})
             self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
                               "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
             return out

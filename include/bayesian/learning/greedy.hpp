@@ -160,6 +160,21 @@ public:
         return winner;
     }
 
+    // hill_climbing.hpp: the runs climb on the learner over a term table of this session's table, run 0 from the learner's
+    // graph; the winner's best graph REPLACES the edges of `graph`.  Returns the winning run.
+    std::int32_t climb(graph_t& graph, bn_climb_params const& params, std::int32_t runs, std::uint64_t seed)
+    {
+        bn_term_table* terms = nullptr;
+        mi355x::engine_handle::check(bn_terms_create_spec(table_.handle(), &spec_, params.max_parents, &terms));
+        std::int32_t winner = 0;
+        int const rc = bn_learn_climb(learner_, terms, &params, runs, seed, nullptr, nullptr, nullptr, nullptr, &winner);
+        bn_terms_destroy(terms);
+        mi355x::engine_handle::check(rc);
+        graph.erase_all_edge();
+        apply_structure(graph);
+        return winner;
+    }
+
 private:
     std::vector<std::int32_t> indexes_of(std::vector<vertex_type> const& vs) const
     {

@@ -926,6 +926,64 @@ int bn_learn_hc(bn_learner *L, bn_term_table *terms, const bn_hc_params *params,
                 const double *similarity, double *score_out, uint32_t *counts_out, uint64_t *masks_out, bn_hc_trace *trace_out,
                 int32_t *n_trace_out, int32_t *winner_out);
 
+/* ---- tabu hill climbing as many device-resident runs: steepest descent over add, delete and reverse moves, a tabu list over node
+ *      pairs, perturbed restarts (the search of bnlearn's hc / tabu and pgmpy's HillClimbSearch; NOT IN THE REFERENCE). ----
+ *
+ *   bn_learn_climb runs `runs` independent searches (1 .. 2^16), one wave per run, lane v = node v (n <= 64), over a bn_term_table
+ *   built on the learner's table, and makes the best graph any run saw the learner's.
+ *   Graph of a run: parent masks pm[v], family terms ll[v], the exact int64 parameter count.  In-degree bound mp =
+ *   min(params.max_parents, the term table's q, the learner's max_parents).  `current` is the learner's stated score of the graph
+ *   (node-order sum plus penalty, exact parameter count: the bits of bn_learn_score), recomputed from the terms after every move.
+ *   Moves: id = (kind * n + from) * n + to.  Kind 0 adds from -> to, 1 deletes it, 2 turns it into to -> from.  Legal:
+ *     add     : from != to, the edge is absent, `to` does not reach `from`, `to` has fewer than mp parents, the new term is not NaN;
+ *     delete  : the edge is present;
+ *     reverse : the edge is present; with it removed `from` does not reach `to`; `from` has fewer than mp parents; the term of
+ *               `from` with `to` added is not NaN.
+ *   Delta of a family change of child c to a new parent set: (ll[c] - term_new); under AIC + double(p_new - p_old), under MDL
+ *   + double(p_new - p_old) * penalty, under BDeu / K2 nothing; p = (k[c] - 1) * rows exactly; every operation a plain fp64 one (no
+ *   fused multiply-add).  d of an add or a delete is the delta of `to`'s family; of a reverse delta(`to` without `from`) +
+ *   delta(`from` with `to`), one add, in that order.  A move whose d is NaN is not legal.
+ *   Tabu: a move on the unordered pair {from, to} is tabu while one of the last tabu_len (0 .. 64) APPLIED moves of this run was on
+ *   that pair; perturbations do not count.
+ *   Step, while steps < max_steps (0: 2^16; at most 2^20):
+ *     1. the legal, non-tabu move with the smallest d (IEEE <, so -0.0 and +0.0 tie), among equal d the lowest id;
+ *     2. none: flag 1, the run ends;
+ *     3. !(d < 0) and worse == max_worse: flag 2 (a local optimum), the run ends;
+ *     4. the move is applied, steps += 1, the pair enters the tabu ring (the oldest entry leaves it);
+ *     5. current = the stated score of the new graph;
+ *     6. current < best_eval strictly: the graph becomes the run's best, best_step = steps, worse = 0; otherwise worse += 1.
+ *   Leaving the loop at max_steps is flag 4.  tabu_len = 0, max_worse = 0 is the classic greedy climb; with both above 0 a run walks
+ *   through plateaus and over ridges and returns the best graph it saw.  (Step 3 compares with ==, as stated: a move with d < 0
+ *   whose recomputed score is not smaller in bits leaves worse above a max_worse of 0, and the run goes on to max_steps.)
+ *   Starts: run 0 from the learner's graph.  Run j >= 1 first makes `perturb` (0 .. 2^16) proposals from stream j, the stream of
+ *   chain j of bn_learn_anneal with the same seeding: kind = draw(3), from = draw(n), to = draw(n), applied when legal under the
+ *   rules above and skipped without a redraw otherwise.  The perturbed graph is the run's first best.  The climb draws nothing.  A
+ *   run depends on (seed, j) and the arguments only: not on `runs` or the launch shape.
+ *   Arguments (BN_ERR_ARG, the text names the limit, nothing launched): n <= 64; 1 <= runs <= 2^16; 0 <= tabu_len <= 64; max_steps <=
+ *   2^20; perturb <= 2^16; max_parents >= 1; the term table built on the learner's table and of the learner's score spec; no
+ *   starting family over q parents; -1 <= trace_run < runs.
+ *   Outputs (each may be NULL): score_out [runs] each run's best_eval; counts_out [runs][6]: steps, steps with d < 0,
+ *   perturbations applied, best_step, flags, moves that were legal but tabu at the last look; masks_out [runs][n] the best graphs'
+ *   parent masks (bit u of word v: u -> v); trace_out [trace_cap] for run trace_run (-1: none), per applied step in order (the
+ *   first trace_cap): kind, from, to, the bits of d, the bits of current; winner_out: the run with the STRICTLY smallest best_eval,
+ *   among equals the lowest.  The learner's graph and terms become the winner's: bn_learn_score equals its score bit for bit,
+ *   bn_learn_structure / bn_learn_terms work as after bn_learn_anneal.  Runs on the table's stream; no device-wide synchronise.
+ *   bn_learn_get also names "climb_ns" (device time of the kernel, summed), "climb_runs", "climb_steps". */
+typedef struct bn_climb_params {
+    int32_t max_parents, tabu_len;
+    uint32_t max_worse, max_steps, perturb;
+    int32_t trace_run;
+    uint32_t trace_cap, pad_;
+} bn_climb_params;
+typedef struct bn_climb_trace {
+    uint64_t d_bits, current_bits;
+    uint8_t kind, from, to, pad8_;
+    uint32_t pad32_;
+    uint64_t pad_;
+} bn_climb_trace;
+int bn_learn_climb(bn_learner *L, bn_term_table *terms, const bn_climb_params *params, int32_t runs, uint64_t seed,
+                   double *score_out, uint32_t *counts_out, uint64_t *masks_out, bn_climb_trace *trace_out, int32_t *winner_out);
+
 /* ---- Bayesian-Dirichlet scores: BDeu and K2 (Cooper-Herskovits) as family terms of every search above ----
  *
  *   A bn_score_spec names the family term: kind 0 the log-likelihood term ll above (used with AIC / MDL), kind 2 BDeu with the
