@@ -1,6 +1,6 @@
 // bn_learn_anneal.hip -- simulated annealing over network structures (reference bayesian/learning/simulated_annealing.hpp:41-115) as
 // many independent chains resident on the device.  AIC / MDL are decomposable and the in-degree is bounded by q, so every family
-// term a chain can ask for is in the term table (bn_learn_anneal.hpp) before it starts: a step is a few random draws, a cycle
+// term a chain can ask for is in the term table (bn_learn_terms.hpp) before it starts: a step is a few random draws, a cycle
 // check, one or two table lookups and a sum.
 //
 // One WAVE per chain, lane v = node v (n <= 64); four waves per workgroup, which share nothing but the rank tables in LDS.
@@ -60,29 +60,25 @@ __device__ __forceinline__ bool reaches(uint64_t pm, int n, int a, int b) {
 }  // namespace
 
 __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealArgs a) {
-    __shared__ uint32_t s_tab[kAnnealTabWords];
+    __shared__ uint32_t s_tab[kTermTabWords];
     __shared__ uint16_t s_list[kAnnealWaves][2][kAnnealMaxEdges];
-    for (int i = int(threadIdx.x); i < kAnnealTabBinom + (a.q + 1) * 64; i += kAnnealWaves * 64) s_tab[i] = a.tab[i];
-    __syncthreads();
-    const int wave = uni(int(threadIdx.x >> 6)), lane = int(threadIdx.x & 63);
-    const int chain = int(blockIdx.x) * kAnnealWaves + wave;
-    if (chain >= a.chains) return;   // (the surplus waves of the last workgroup; no workgroup barrier below)
-    uint16_t* list = s_list[wave][0];
-    uint16_t* kept = s_list[wave][1];
+    const SearchWave w = search_enter<kAnnealWaves>(s_tab, a);
+    if (w.surplus) return;
+    const int lane = w.lane, chain = w.run;
+    uint16_t* list = s_list[w.wave][0];
+    uint16_t* kept = s_list[w.wave][1];
     const int n = a.n;
-    const bool node = lane < n;
 
-    uint64_t pm = node ? a.pmask0[lane] : 0;
-    int64_t rows = node ? a.rows0[lane] : 1;
-    double ll = node ? a.ll0[lane] : 0.0;
-    const int32_t kk = node ? a.k[lane] : 1;
+    uint64_t pm;
+    int64_t rows;
+    double ll;
+    int32_t kk;
+    load_family(a, a.k, n, lane, pm, rows, ll, kk);
     int ne = a.n_edges0;
     for (int i = lane; i < ne; i += 64) list[i] = kept[i] = a.edges0[i];
     wave_sync();
 
-    uint4 g = philox4x32_10(uint32_t(chain), 0u, 0u, 0u, a.seed_lo, a.seed_hi);
-    g.x = uint32_t(uni(int(g.x))); g.y = uint32_t(uni(int(g.y))); g.z = uint32_t(uni(int(g.z))); g.w = uint32_t(uni(int(g.w)));
-    if ((g.x | g.y | g.z | g.w) == 0) g.x = 1;
+    uint4 g = seed_stream(chain, a.seed_lo, a.seed_hi);
 
     // the learner's score of the graph whose family terms the lanes hold in x
     auto evaluate = [&](double x, int64_t params) { return evaluate_terms(x, params, n, a.criterion, a.penalty); };
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealA
     int64_t params = a.params0;
     double current = evaluate(ll, params), temp = a.initial_temp;
     uint32_t no_changed = 0, proposals = 0, operated = 0, accepted = 0;
-    const bool traced = chain == a.trace_chain && a.trace != nullptr;
+    const bool traced = chain == a.trace_run && a.trace != nullptr;
 
     while (temp > a.final_temp && no_changed < a.same_state_max && proposals < a.max_proposals) {
         ++proposals;
@@ -116,8 +112,7 @@ __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealA
                 ok = !((pm_to >> from) & 1) && __popcll(pm_to) < a.max_parents;
             }
             if (ok && lane == to) {
-                pm_new = pm | (uint64_t(1) << from);
-                rows_new = rows * k_from;
+                with_parent(pm, rows, from, k_from, pm_new, rows_new);
                 changed = true;
             }
         } else {
@@ -141,14 +136,13 @@ __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealA
             if (method == 2) {   // add_edge(to, from) on the graph without from -> to
                 ok = !reaches(without, n, from, to) && __popcll(lane_u64(pm, from)) < a.max_parents;
                 if (ok && lane == from) {
-                    pm_new = pm | (uint64_t(1) << to);
-                    rows_new = rows * k_to;
+                    with_parent(pm, rows, to, k_to, pm_new, rows_new);
                     changed = true;
                 }
             }
             if (ok && lane == to) {
                 pm_new = without;
-                rows_new = int64_t(uint32_t(rows) / k_from);   // (an eligible family has at most 2^20 entries: exact in 32 bits)
+                rows_new = rows_without(rows, k_from);
                 changed = true;
             }
         }
@@ -163,9 +157,7 @@ __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealA
         if (!ok) continue;
         ++operated;
 
-        const int64_t delta = changed ? int64_t(kk - 1) * (rows_new - rows) : 0;
-        int64_t params_new = params + int64_t(lane_u64(uint64_t(delta), to));
-        if (method == 2) params_new += int64_t(lane_u64(uint64_t(delta), from));
+        const int64_t params_new = params + params_delta(kk, rows, rows_new, to, from, method == 2);
         const double now = evaluate(ll_new, params_new);
         const double diff = now - current;
         bool accept = diff <= 0;
@@ -200,18 +192,11 @@ __global__ __launch_bounds__(kAnnealWaves * 64) void learn_anneal_kernel(AnnealA
     if (!(no_changed < a.same_state_max)) flags |= kAnnealEndSame;
     if (!(proposals < a.max_proposals)) flags |= kAnnealEndCap;
     if (lane == 0) a.rec[chain] = AnnealRecord{current, proposals, operated, accepted, flags, uint32_t(ne), 0u};
-    if (node) {
-        a.masks[int64_t(chain) * n + lane] = pm;
-        a.ll[int64_t(chain) * n + lane] = ll;
-    }
+    store_graph(a, chain, lane, pm, ll);
     if (a.edges)
         for (int i = lane; i < ne; i += 64) a.edges[int64_t(chain) * a.edge_stride + i] = list[i];
 }
 
-int learn_launch_anneal(const AnnealArgs& a, void* stream) {
-    const int blocks = (a.chains + kAnnealWaves - 1) / kAnnealWaves;
-    hipLaunchKernelGGL(learn_anneal_kernel, dim3(unsigned(blocks)), dim3(kAnnealWaves * 64), 0, hipStream_t(stream), a);
-    return int(hipGetLastError());
-}
+int learn_launch_anneal(const AnnealArgs& a, void* stream) { return launch_search<kAnnealWaves>(learn_anneal_kernel, a, stream); }
 
 }  // namespace bnmi

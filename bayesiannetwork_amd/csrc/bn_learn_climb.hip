@@ -1,7 +1,7 @@
 // bn_learn_climb.hip -- tabu hill climbing over network structures as many independent runs resident on the device: steepest
 // descent over the add, delete and reverse moves of a graph, a tabu list over node pairs, perturbed restarts (the search of
 // bnlearn's hc / tabu and pgmpy's HillClimbSearch; include/bn_mi355x.h states the contract).  Every family term a run can ask for
-// is in the term table (bn_learn_anneal.hpp) before it starts.
+// is in the term table (bn_learn_terms.hpp) before it starts.
 //
 // One WAVE per run, lane v = node v (n <= 64); four waves per workgroup, which share nothing but the rank tables in LDS.
 //   lane v     : node v's parent mask, family term ll[v], row product, arity; its ancestor mask anc[v] (who reaches v) and its
@@ -35,11 +35,6 @@ namespace {
 constexpr int kNoMove = 0x7fffffff;
 constexpr int kClimbBatch = 4;   // the `to` whose term loads a step has in flight together
 
-__device__ __forceinline__ uint32_t from_lane_u32(uint32_t x, int src) { return uint32_t(__builtin_amdgcn_ds_bpermute(src << 2, int(x))); }
-__device__ __forceinline__ uint64_t from_lane_u64(uint64_t x, int src) {
-    return (uint64_t(from_lane_u32(uint32_t(x >> 32), src)) << 32) | from_lane_u32(uint32_t(x), src);
-}
-
 // (d, id) before (e, ie)?  kNoMove: no move at all
 __device__ __forceinline__ bool before(double d, int id, double e, int ie) {
     return id != kNoMove && (ie == kNoMove || d < e || (d == e && id < ie));
@@ -48,20 +43,19 @@ __device__ __forceinline__ bool before(double d, int id, double e, int ie) {
 }  // namespace
 
 __global__ __launch_bounds__(kClimbWaves * 64) void learn_climb_kernel(ClimbArgs a) {
-    __shared__ uint32_t s_tab[kAnnealTabWords];
-    for (int i = int(threadIdx.x); i < kAnnealTabBinom + (a.q + 1) * 64; i += kClimbWaves * 64) s_tab[i] = a.tab[i];
-    __syncthreads();
-    const int wave = uni(int(threadIdx.x >> 6)), lane = int(threadIdx.x & 63);
-    const int run = int(blockIdx.x) * kClimbWaves + wave;
-    if (run >= a.runs) return;   // (the surplus waves of the last workgroup; no workgroup barrier below)
+    __shared__ uint32_t s_tab[kTermTabWords];
+    const SearchWave w = search_enter<kClimbWaves>(s_tab, a);
+    if (w.surplus) return;
+    const int lane = w.lane, run = w.run;
     const int n = a.n, mp = a.max_parents;
     const bool node = lane < n;
     const uint64_t me = uint64_t(1) << lane;
 
-    uint64_t pm = node ? a.pmask0[lane] : 0;
-    int64_t rows = node ? a.rows0[lane] : 1;
-    double ll = node ? a.ll0[lane] : 0.0;
-    const int32_t kk = node ? a.k[lane] : 1;
+    uint64_t pm;
+    int64_t rows;
+    double ll;
+    int32_t kk;
+    load_family(a, a.k, n, lane, pm, rows, ll, kk);
     uint64_t anc = 0, desc = 0, tmask = 0;
     uint32_t ring = 0xFFFFu;
     int64_t params = a.params0;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(kClimbWaves * 64) void learn_climb_kernel(ClimbArgs
                 p.pen0 = penalty_of(int64_t(k_to - 1) * (rows_to * kk - rows_to));
             }
         } else if (p.has) {
-            const int64_t rows_less = int64_t(uint32_t(rows_to) / uint32_t(kk));   // (an eligible family has at most 2^20 entries: exact in 32 bits)
+            const int64_t rows_less = rows_without(rows_to, uint32_t(kk));
             p.want0 = true;
             p.at0 = int64_t(to) * a.T + rank_of(s_tab, to, pm_to & ~me);
             p.pen0 = penalty_of(int64_t(k_to - 1) * (rows_less - rows_to));
@@ -144,33 +138,23 @@ __global__ __launch_bounds__(kClimbWaves * 64) void learn_climb_kernel(ClimbArgs
         const int64_t rows_was = rows;
         bool changed = false;
         if (lane == to) {
-            if (kind == 0) {
-                pm |= uint64_t(1) << from;
-                rows = rows * k_from;
-            } else {
-                pm &= ~(uint64_t(1) << from);
-                rows = int64_t(uint32_t(rows) / k_from);
-            }
+            if (kind == 0) with_parent(pm, rows, from, k_from, pm, rows);
+            else without_parent(pm, rows, from, k_from, pm, rows);
             changed = true;
         }
         if (kind == 2 && lane == from) {
-            pm |= uint64_t(1) << to;
-            rows = rows * k_to;
+            with_parent(pm, rows, to, k_to, pm, rows);
             changed = true;
         }
         if (changed) ll = term_of(a.terms, a.T, s_tab, lane, pm);
-        const int64_t dp = int64_t(kk - 1) * (rows - rows_was);
-        params += int64_t(lane_u64(uint64_t(dp), to));
-        if (kind == 2) params += int64_t(lane_u64(uint64_t(dp), from));
+        params += params_delta(kk, rows_was, rows, to, from, kind == 2);
         rebuild();
     };
 
     rebuild();
     uint32_t perturbed = 0;
     if (run >= 1 && a.perturb > 0) {
-        uint4 g = philox4x32_10(uint32_t(run), 0u, 0u, 0u, a.seed_lo, a.seed_hi);
-        g.x = uint32_t(uni(int(g.x))); g.y = uint32_t(uni(int(g.y))); g.z = uint32_t(uni(int(g.z))); g.w = uint32_t(uni(int(g.w)));
-        if ((g.x | g.y | g.z | g.w) == 0) g.x = 1;
+        uint4 g = seed_stream(run, a.seed_lo, a.seed_hi);
         for (uint32_t i = 0; i < a.perturb; ++i) {
             const int kind = int(draw_below(g, 3u));
             const int from = int(draw_below(g, uint32_t(n)));
@@ -266,16 +250,9 @@ __global__ __launch_bounds__(kClimbWaves * 64) void learn_climb_kernel(ClimbArgs
     if (flags == 0) flags = kClimbEndCap;
 
     if (lane == 0) a.rec[run] = ClimbRecord{best_eval, steps, improving, perturbed, best_step, flags, tabu_legal};
-    if (node) {
-        a.masks[int64_t(run) * n + lane] = best_pm;
-        a.ll[int64_t(run) * n + lane] = best_ll;
-    }
+    store_graph(a, run, lane, best_pm, best_ll);
 }
 
-int learn_launch_climb(const ClimbArgs& a, void* stream) {
-    const int blocks = (a.runs + kClimbWaves - 1) / kClimbWaves;
-    hipLaunchKernelGGL(learn_climb_kernel, dim3(unsigned(blocks)), dim3(kClimbWaves * 64), 0, hipStream_t(stream), a);
-    return int(hipGetLastError());
-}
+int learn_launch_climb(const ClimbArgs& a, void* stream) { return launch_search<kClimbWaves>(learn_climb_kernel, a, stream); }
 
 }  // namespace bnmi

@@ -1,14 +1,13 @@
 // bn_learn_climb.hpp -- tabu hill climbing over a precomputed table of family terms: steepest descent over add, delete and reverse
 // moves with a tabu list and perturbed restarts.  Host-side view of the kernel in bn_learn_climb.hip; the C ABI (bn_learn_climb of
-// include/bn_mi355x.h) is in bn_learn_search.cpp.  The term table and its rank tables are bn_learn_anneal.hpp's.
+// include/bn_mi355x.h) is in bn_learn_search.cpp.  The term table and its rank tables are bn_learn_terms.hpp's.
 #pragma once
 
-#include <cstdint>
+#include "bn_learn_search.hpp"
 
 namespace bnmi {
 
 constexpr int kClimbWaves = 4;               // runs per workgroup: they share the rank tables in LDS and nothing else
-constexpr int kClimbMaxRuns = 1 << 16;
 constexpr int kClimbMaxTabu = 64;            // the ring has a lane per entry
 constexpr uint32_t kClimbMaxSteps = 1u << 20;
 constexpr uint32_t kClimbMaxPerturb = 1u << 16;
@@ -28,27 +27,10 @@ struct ClimbTrace {       // per applied step of the traced run
     uint64_t pad_;
 };
 
-struct ClimbArgs {
-    const double* terms;        // [n][T]
-    const uint32_t* tab;        // [kAnnealTabWords]
-    int64_t T;
-    const int32_t* k;           // [n] arities
-    const uint64_t* pmask0;     // [n] the starting graph: parent masks, row products, family terms
-    const int64_t* rows0;
-    const double* ll0;
-    int32_t n, q, max_parents;  // q: the table's bound (the rank tables); max_parents <= q: what a run refuses at
-    int32_t criterion;
-    int64_t params0;
-    double penalty;
+struct ClimbArgs : SearchArgs, StartGraph {   // (masks, ll: of the best graph a run saw)
     int32_t tabu_len;
     uint32_t max_worse, max_steps, perturb;
-    uint32_t seed_lo, seed_hi;
-    int32_t runs;
-    int32_t trace_run;          // -1: none
-    uint32_t trace_cap;
     ClimbRecord* rec;           // [runs]
-    uint64_t* masks;            // [runs][n] parent masks of the best graph
-    double* ll;                 // [runs][n] its family terms
     ClimbTrace* trace;          // null, or [trace_cap]
 };
 

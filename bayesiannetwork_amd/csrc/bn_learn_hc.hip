@@ -1,7 +1,7 @@
 // bn_learn_hc.hip -- hierarchical-clustering stepwise structure search (reference bayesian/learning/stepwise_structure_hc.hpp:131-360
 // over greedy.hpp:67-101) as many independent runs resident on the device.  Everything a run reads exists before it starts: the
 // similarity matrix S (the all-pairs mutual information, or the caller's) and the term table of every family of at most q parents
-// (bn_learn_anneal.hpp).  A run is table lookups, random draws and list maintenance; no pass over the samples.
+// (bn_learn_terms.hpp).  A run is table lookups, random draws and list maintenance; no pass over the samples.
 //
 // One WAVE per run, lane v = node v (n <= 64); two waves per workgroup, which share nothing but the rank tables in LDS.
 //   lane v     : node v's parent mask, family term ll[v], exact int64 row product, arity
@@ -55,18 +55,16 @@ __device__ __forceinline__ int shuffle_lanes(uint4& g, int x, int len, int lane)
 }  // namespace
 
 __global__ __launch_bounds__(kHcWaves * 64) void learn_hc_kernel(HcArgs a) {
-    __shared__ uint32_t s_tab[kAnnealTabWords];
+    __shared__ uint32_t s_tab[kTermTabWords];
     __shared__ double s_val[kHcWaves][kHcMaxSims];
     __shared__ double s_cval[kHcWaves][2][kHcMaxIds];
     __shared__ uint16_t s_start[kHcWaves][kHcMaxIds];
     __shared__ uint8_t s_sa[kHcWaves][kHcMaxSims], s_sb[kHcWaves][kHcMaxSims];
     __shared__ uint8_t s_nodes[kHcWaves][kHcNodeBytes];
     __shared__ uint8_t s_len[kHcWaves][kHcMaxIds], s_ccnt[kHcWaves][2][kHcMaxIds], s_clusters[kHcWaves][64];
-    for (int i = int(threadIdx.x); i < kAnnealTabBinom + (a.q + 1) * 64; i += kHcWaves * 64) s_tab[i] = a.tab[i];
-    __syncthreads();
-    const int wave = uni(int(threadIdx.x >> 6)), lane = int(threadIdx.x & 63);
-    const int run = int(blockIdx.x) * kHcWaves + wave;
-    if (run >= a.runs) return;   // (the surplus wave of the last workgroup; no workgroup barrier below)
+    const SearchWave w = search_enter<kHcWaves>(s_tab, a);
+    if (w.surplus) return;
+    const int wave = w.wave, lane = w.lane, run = w.run;
     double* val = s_val[wave];
     uint8_t *sa = s_sa[wave], *sb = s_sb[wave], *nodes = s_nodes[wave], *len = s_len[wave], *clusters = s_clusters[wave];
     uint16_t* start = s_start[wave];
@@ -100,9 +98,7 @@ __global__ __launch_bounds__(kHcWaves * 64) void learn_hc_kernel(HcArgs a) {
     }
     wave_sync();
 
-    uint4 g = philox4x32_10(uint32_t(run), 0u, 0u, 0u, a.seed_lo, a.seed_hi);
-    g.x = uint32_t(uni(int(g.x))); g.y = uint32_t(uni(int(g.y))); g.z = uint32_t(uni(int(g.z))); g.w = uint32_t(uni(int(g.w)));
-    if ((g.x | g.y | g.z | g.w) == 0) g.x = 1;
+    uint4 g = seed_stream(run, a.seed_lo, a.seed_hi);
 
     double current = evaluate_terms(ll, params, n, a.criterion, a.penalty);
     uint32_t merges = 0, tried = 0, kept = 0, pruned = 0, pairs_kept = 0, visits = 0;
@@ -156,15 +152,13 @@ __global__ __launch_bounds__(kHcWaves * 64) void learn_hc_kernel(HcArgs a) {
                 int64_t rows_new = rows;
                 double ll_new = ll;
                 if (lane == c) {
-                    pm_new = pm | (uint64_t(1) << p);
-                    rows_new = rows * k_p;
+                    with_parent(pm, rows, p, k_p, pm_new, rows_new);
                     ll_new = term_of(a.terms, a.T, s_tab, lane, pm_new);
                 }
                 const double added = lane_f64(ll_new, c);
                 if (added != added) continue;   // a family over the per-family limit
                 ++tried;
-                const int64_t delta = int64_t(kk - 1) * (rows_new - rows);
-                const int64_t params_new = params + int64_t(lane_u64(uint64_t(delta), c));
+                const int64_t params_new = params + params_delta(kk, rows, rows_new, c, c, false);
                 const double next = evaluate_terms(ll_new, params_new, n, a.criterion, a.penalty);
                 if (next < current) {
                     pm = pm_new;
@@ -272,16 +266,9 @@ __global__ __launch_bounds__(kHcWaves * 64) void learn_hc_kernel(HcArgs a) {
 
     const uint32_t flags = (nc == 1 ? kHcOneCluster : 0u) | (m == 0 ? kHcNoSimilarity : 0u);
     if (lane == 0) a.rec[run] = HcRecord{current, merges, tried, kept, pruned, pairs_kept, flags, visits, 0u};
-    if (node) {
-        a.masks[int64_t(run) * n + lane] = pm;
-        a.ll[int64_t(run) * n + lane] = ll;
-    }
+    store_graph(a, run, lane, pm, ll);
 }
 
-int learn_launch_hc(const HcArgs& a, void* stream) {
-    const int blocks = (a.runs + kHcWaves - 1) / kHcWaves;
-    hipLaunchKernelGGL(learn_hc_kernel, dim3(unsigned(blocks)), dim3(kHcWaves * 64), 0, hipStream_t(stream), a);
-    return int(hipGetLastError());
-}
+int learn_launch_hc(const HcArgs& a, void* stream) { return launch_search<kHcWaves>(learn_hc_kernel, a, stream); }
 
 }  // namespace bnmi

@@ -1,9 +1,9 @@
 // bn_learn_hc.hpp -- hierarchical-clustering stepwise structure search over a precomputed table of family terms (reference
 // bayesian/learning/stepwise_structure_hc.hpp).  Host-side view of the kernel in bn_learn_hc.hip; the C ABI (bn_learn_hc of
-// include/bn_mi355x.h) is in bn_learn.cpp.  The term table and its rank tables are bn_learn_anneal.hpp's.
+// include/bn_mi355x.h) is in bn_learn_search.cpp.  The term table and its rank tables are bn_learn_terms.hpp's.
 #pragma once
 
-#include <cstdint>
+#include "bn_learn_search.hpp"
 
 namespace bnmi {
 
@@ -13,7 +13,6 @@ constexpr int kHcMaxIds = 128;               // cluster ids 0 .. 2n - 2 <= 126
 // node lists of every cluster ever made: n singletons, then per merge the merged list; the sum over the merges of the merged
 // sizes is largest when one cluster takes a singleton at a time: 2 + 3 + ... + 64 = 2 079
 constexpr int kHcNodeBytes = 64 + 2079 + 33; // = 2 176
-constexpr int kHcMaxRuns = 1 << 16;
 
 constexpr uint32_t kHcOneCluster = 1, kHcNoSimilarity = 2;
 
@@ -29,23 +28,10 @@ struct HcTrace {          // per merge (kind 0) and per pruning visit (kind 1) o
     uint32_t pad_;
 };
 
-struct HcArgs {
-    const double* terms;        // [n][T]
-    const uint32_t* tab;        // [kAnnealTabWords]
-    int64_t T;
-    const int32_t* k;           // [n] arities
+struct HcArgs : SearchArgs {    // (params0: of the empty graph)
     const double* S;            // [n][n] similarities, read as S[l][r]: l from make_similarity's first cluster
-    int32_t n, q, max_parents;  // q: the table's bound (the rank tables); max_parents <= q: what a run refuses at
-    int32_t criterion;
-    int64_t params0;            // parameters of the empty graph
-    double penalty, alpha, average;
-    uint32_t seed_lo, seed_hi;
-    int32_t runs;
-    int32_t trace_run;          // -1: none
-    uint32_t trace_cap;
+    double alpha, average;
     HcRecord* rec;              // [runs]
-    uint64_t* masks;            // [runs][n] final parent masks
-    double* ll;                 // [runs][n] final family terms
     HcTrace* trace;             // null, or [trace_cap]
 };
 

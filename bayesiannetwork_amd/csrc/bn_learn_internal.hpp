@@ -148,7 +148,7 @@ struct bn_term_table {
     int device = 0;
     int32_t n = 0, q = 0;
     int64_t T = 0;                       // entries per child
-    std::vector<uint32_t> tab;           // the rank tables (bn_learn_anneal.hpp)
+    std::vector<uint32_t> tab;           // the rank tables (bn_learn_terms.hpp)
     DeviceBuf<double> d_terms;
     DeviceBuf<uint32_t> d_tab;
     DeviceBuf<int32_t> d_k;

@@ -1,12 +1,12 @@
 // bn_learn_terms.cpp -- bn_term_table (include/bn_mi355x.h, bn_terms_*): the family term of EVERY parent set of at most q nodes per
 // child, made by one batch of run_groups (bn_learn_batch.cpp) and kept on the device for the searches of bn_learn_search.cpp.
 #include "bn_learn_internal.hpp"
-#include "bn_learn_anneal.hpp"
+#include "bn_learn_terms.hpp"
 
 // sorted parents, none of them c
 int64_t bn_term_table::rank(int32_t c, const int32_t* par, int32_t j) const {
     int64_t r = tab[size_t(j)];
-    for (int32_t i = 0; i < j; ++i) r += tab[size_t(kAnnealTabBinom + (i + 1) * 64 + (par[i] - (par[i] > c ? 1 : 0)))];
+    for (int32_t i = 0; i < j; ++i) r += tab[size_t(kTermTabBinom + (i + 1) * 64 + (par[i] - (par[i] > c ? 1 : 0)))];
     return r;
 }
 
@@ -22,8 +22,8 @@ extern "C" int bn_terms_create_spec(bn_info_table* t, const bn_score_spec* spec_
     if (int r = check_spec(spec_in, spec)) return r;
     if (max_parents < 1 || max_parents > kLearnMaxParents) return fail(BN_ERR_ARG, "term table: max_parents must be in 1..16");
     const int32_t n = t->n, q = max_parents;
-    if (n > kAnnealMaxNodes)
-        return fail(BN_ERR_ARG, "term table: " + std::to_string(n) + " nodes (at most " + std::to_string(kAnnealMaxNodes) + ": a node has a lane)");
+    if (n > kTermMaxNodes)
+        return fail(BN_ERR_ARG, "term table: " + std::to_string(n) + " nodes (at most " + std::to_string(kTermMaxNodes) + ": a node has a lane)");
     // C(a, i) for a <= 63, i <= 16 (C(63, 16) < 2^49)
     std::vector<std::vector<uint64_t>> C(64, std::vector<uint64_t>(18, 0));
     for (int a = 0; a < 64; ++a) {
@@ -33,13 +33,13 @@ extern "C" int bn_terms_create_spec(bn_info_table* t, const bn_score_spec* spec_
     std::vector<int64_t> offset(size_t(q) + 2, 0);
     for (int32_t j = 0; j <= q; ++j) {
         offset[size_t(j) + 1] = offset[size_t(j)] + int64_t(n >= 1 ? C[size_t(n - 1)][size_t(j)] : 0);
-        if (offset[size_t(j) + 1] * n > kAnnealMaxEntries) {
+        if (offset[size_t(j) + 1] * n > kTermMaxEntries) {
             // (the sum only grows: name the whole table's size, in 128-bit-free arithmetic -- every term is below 2^49 and q <= 16)
             int64_t total = 0;
             for (int32_t u = 0; u <= q; ++u) total += int64_t(C[size_t(n - 1)][size_t(u)]);
             return fail(BN_ERR_ARG, "term table: " + std::to_string(n) + " nodes x " + std::to_string(total) + " parent sets of at most " +
                                         std::to_string(q) + " = " + std::to_string(total * n) + " entries (at most 2^22 = " +
-                                        std::to_string(kAnnealMaxEntries) + ")");
+                                        std::to_string(kTermMaxEntries) + ")");
         }
     }
     std::unique_ptr<bn_term_table> tt(new (std::nothrow) bn_term_table);
@@ -50,10 +50,10 @@ extern "C" int bn_terms_create_spec(bn_info_table* t, const bn_score_spec* spec_
     tt->q = q;
     tt->spec = spec;
     tt->T = offset[size_t(q) + 1];
-    tt->tab.assign(size_t(kAnnealTabWords), 0u);
+    tt->tab.assign(size_t(kTermTabWords), 0u);
     for (int32_t j = 0; j <= q; ++j) tt->tab[size_t(j)] = uint32_t(offset[size_t(j)]);
     for (int32_t i = 0; i <= q; ++i)
-        for (int32_t a = 0; a + 1 < n; ++a) tt->tab[size_t(kAnnealTabBinom + i * 64 + a)] = uint32_t(C[size_t(a)][size_t(i)]);   // (<= C(n - 1, q) <= T)
+        for (int32_t a = 0; a + 1 < n; ++a) tt->tab[size_t(kTermTabBinom + i * 64 + a)] = uint32_t(C[size_t(a)][size_t(i)]);   // (<= C(n - 1, q) <= T)
 
     // every family once: the groups (c, B, candidates above max(B)) for every B of fewer than q nodes; a family over the per-family
     // limit is left out of the batch (its supersets too) and keeps its NaN

@@ -266,6 +266,23 @@ class Learner:
         _lib.check(_lib.lib().bn_learn_brute_force_hint(self._h, len(ps), _p(ps, ctypes.c_int32), len(cs), _p(cs, ctypes.c_int32)))
         return self.score()
 
+    def _search(self, call, term_table: "TermTable", p, runs: int, seed: int, names, trace_dtype, cap: int, tracing: bool):
+        """The plumbing of the searches over a term table: the per-run score, counts [runs][len(names)] and masks, the trace
+        buffer and the winner, around call(head, score, counts, masks, trace, winner) -- the library call, `head` being its first
+        five arguments.  Returns (the records every search has: names' columns, masks, winner; the scores; the trace buffer)."""
+        c = max(runs, 1)
+        score = np.zeros(c)
+        counts = np.zeros((c, len(names)), dtype=np.uint32)
+        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
+        trace = np.zeros(max(cap, 1), dtype=trace_dtype)
+        winner = ctypes.c_int32()
+        head = (self._h, term_table._h, ctypes.byref(p), runs, int(seed) & (2 ** 64 - 1))
+        _lib.check(call(head, _p(score, ctypes.c_double), _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64),
+                        trace.ctypes.data if tracing else None, ctypes.byref(winner)))
+        out = {name: counts[:, i].copy() for i, name in enumerate(names)}
+        out.update({"masks": masks[:, :self.n], "winner": winner.value})
+        return out, score, trace
+
     def anneal(self, term_table: "TermTable", initial_temp: float, final_temp: float, decreasing_rate: float, boltzmann: float = 1.0,
                same_state_max: int = 100, chains: int = 64, seed: int = 0, rule: str = "reference", max_proposals: int = 1 << 20,
                trace_chain=None, trace_cap=None) -> dict:
@@ -283,21 +300,13 @@ class Learner:
         cap = int(max_proposals if trace_cap is None else trace_cap) if tracing else 0
         p = _lib.AnnealParams(float(initial_temp), float(final_temp), float(decreasing_rate), float(boltzmann), int(same_state_max),
                               int(max_proposals), _RULES[rule], int(trace_chain) if tracing else -1, cap, 0)
-        c = max(chains, 1)
-        stride = max(self.n * term_table.max_parents, 1)
-        ev = np.zeros(c)
-        counts = np.zeros((c, 4), dtype=np.uint32)
-        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
-        n_edges = np.zeros(c, dtype=np.int32)
-        edges = np.zeros((c, stride), dtype=np.uint16)
-        trace = np.zeros(max(cap, 1), dtype=TRACE_DTYPE)
-        winner = ctypes.c_int32()
-        _lib.check(_lib.lib().bn_learn_anneal(self._h, term_table._h, ctypes.byref(p), chains, int(seed) & (2 ** 64 - 1), _p(ev, ctypes.c_double),
-                                              _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), _p(n_edges, ctypes.c_int32),
-                                              _p(edges, ctypes.c_uint16), trace.ctypes.data if tracing else None, ctypes.byref(winner)))
-        out = {"eval": ev, "proposals": counts[:, 0].copy(), "operated": counts[:, 1].copy(), "accepted": counts[:, 2].copy(),
-               "flags": counts[:, 3].copy(), "masks": masks[:, :self.n],
-               "edges": [[(int(e) & 255, int(e) >> 8) for e in edges[j, :n_edges[j]]] for j in range(chains)], "winner": winner.value}
+        n_edges = np.zeros(max(chains, 1), dtype=np.int32)
+        edges = np.zeros((max(chains, 1), max(self.n * term_table.max_parents, 1)), dtype=np.uint16)
+        out, ev, trace = self._search(
+            lambda head, ev, counts, masks, trace, winner: _lib.lib().bn_learn_anneal(
+                *head, ev, counts, masks, _p(n_edges, ctypes.c_int32), _p(edges, ctypes.c_uint16), trace, winner),
+            term_table, p, chains, seed, ("proposals", "operated", "accepted", "flags"), TRACE_DTYPE, cap, tracing)
+        out.update({"eval": ev, "edges": [[(int(e) & 255, int(e) >> 8) for e in edges[j, :n_edges[j]]] for j in range(chains)]})
         if tracing:
             out["trace"] = trace[:min(int(out["operated"][int(trace_chain)]), cap)].copy()
         return out
@@ -317,23 +326,17 @@ class Learner:
         cap = int(trace_cap) if tracing else 0
         p = _lib.HcParams(float(alpha), int(term_table.max_parents if max_parents is None else max_parents),
                           int(trace_run) if tracing else -1, cap, 0)
-        c = max(runs, 1)
         S = None
         if similarity is not None:
             S = np.ascontiguousarray(similarity, dtype=np.float64)
             if S.shape != (self.n, self.n):
                 raise ValueError(f"similarity: an [{self.n}][{self.n}] matrix")
-        score = np.zeros(c)
-        counts = np.zeros((c, 6), dtype=np.uint32)
-        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
-        trace = np.zeros(max(cap, 1), dtype=HC_TRACE_DTYPE)
-        n_trace, winner = ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(_lib.lib().bn_learn_hc(self._h, term_table._h, ctypes.byref(p), runs, int(seed) & (2 ** 64 - 1),
-                                          _p(S, ctypes.c_double) if S is not None else None, _p(score, ctypes.c_double),
-                                          _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), trace.ctypes.data if tracing else None,
-                                          ctypes.byref(n_trace), ctypes.byref(winner)))
-        out = {name: counts[:, i].copy() for i, name in enumerate(("merges", "tried", "kept", "pruned", "pairs_kept", "flags"))}
-        out.update({"score": score, "masks": masks[:, :self.n], "winner": winner.value})
+        n_trace = ctypes.c_int32()
+        out, score, trace = self._search(
+            lambda head, score, counts, masks, trace, winner: _lib.lib().bn_learn_hc(
+                *head, _p(S, ctypes.c_double) if S is not None else None, score, counts, masks, trace, ctypes.byref(n_trace), winner),
+            term_table, p, runs, seed, ("merges", "tried", "kept", "pruned", "pairs_kept", "flags"), HC_TRACE_DTYPE, cap, tracing)
+        out["score"] = score
         if tracing:
             tr = trace[:n_trace.value]
             merge, visit = tr[tr["kind"] == 0], tr[tr["kind"] == 1]
@@ -358,17 +361,10 @@ class Learner:
         cap = (int(trace_cap) or int(max_steps) or (1 << 16)) if tracing else 0
         p = _lib.ClimbParams(int(term_table.max_parents if max_parents is None else max_parents), int(tabu_len), int(max_worse), int(max_steps),
                              int(perturb), int(trace_run) if tracing else -1, cap, 0)
-        c = max(runs, 1)
-        score = np.zeros(c)
-        counts = np.zeros((c, 6), dtype=np.uint32)
-        masks = np.zeros((c, max(self.n, 1)), dtype=np.uint64)
-        trace = np.zeros(max(cap, 1), dtype=CLIMB_TRACE_DTYPE)
-        winner = ctypes.c_int32()
-        _lib.check(_lib.lib().bn_learn_climb(self._h, term_table._h, ctypes.byref(p), runs, int(seed) & (2 ** 64 - 1), _p(score, ctypes.c_double),
-                                             _p(counts, ctypes.c_uint32), _p(masks, ctypes.c_uint64), trace.ctypes.data if tracing else None,
-                                             ctypes.byref(winner)))
-        out = {name: counts[:, i].copy() for i, name in enumerate(("steps", "improving", "perturbed", "best_step", "flags", "tabu_legal"))}
-        out.update({"score": score, "masks": masks[:, :self.n], "winner": winner.value})
+        out, score, trace = self._search(
+            lambda head, *outputs: _lib.lib().bn_learn_climb(*head, *outputs), term_table, p, runs, seed,
+            ("steps", "improving", "perturbed", "best_step", "flags", "tabu_legal"), CLIMB_TRACE_DTYPE, cap, tracing)
+        out["score"] = score
         if tracing:
             out["trace"] = trace[:min(int(out["steps"][int(trace_run)]), cap)].copy()
         return out
@@ -660,7 +656,41 @@ class StepwiseStructure(_Search):
             return self._finish(model, L)
 
 
-class SimulatedAnnealing(_Search):
+class _TermSearch(_Search):
+    """What the searches over a term table share: the table, kept for the object's lifetime; the seed of call number i, seed + i
+    (without a seed one is drawn); `records`, the Learner method's records of the last call on the device."""
+
+    def __init__(self, criterion, sampling, max_parents, seed, device):
+        super().__init__(criterion, sampling, max_parents, seed, device)
+        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
+        self._calls = 0
+        self._terms = None
+        self.records = None
+
+    def close(self) -> None:
+        if getattr(self, "_terms", None) is not None:
+            self._terms.close()
+            self._terms = None
+
+    __del__ = close
+
+    def term_table(self, model) -> TermTable:
+        if self._terms is None:
+            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
+        return self._terms
+
+    def _next_seed(self) -> int:
+        self._calls += 1
+        return self._seed + self._calls - 1
+
+    def _note(self, L: Learner, terms: TermTable, names) -> None:
+        """`last` gains the search's counters `names`, the winner and the term table's counters."""
+        self.last.update({name: L.info(name) for name in names})
+        self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
+                          "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+
+
+class SimulatedAnnealing(_TermSearch):
     """bn::learning::simulated_annealing<Eval> (simulated_annealing.hpp).  `sa(model, initial_temp, final_temp, decreasing_rate,
     boltzmann=1.0, same_state_max=100)`: `chains` independent chains from the model's graph, the best final graph returned as
     (FlatModel with CPTs fitted to it, score).  max_parents (default 3) bounds the in-degree: the family terms of every parent
@@ -672,38 +702,19 @@ class SimulatedAnnealing(_Search):
                  max_proposals: int = 1 << 20, device: int = _lib.BN_DEVICE_CURRENT):
         super().__init__(criterion, sampling, max_parents, seed, device)
         self._chains, self._rule, self._max_proposals = int(chains), rule, int(max_proposals)
-        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
-        self._calls = 0
-        self._terms = None
-        self.records = None   # Learner.anneal's records of the last call
-
-    def close(self) -> None:
-        if getattr(self, "_terms", None) is not None:
-            self._terms.close()
-            self._terms = None
-
-    __del__ = close
-
-    def term_table(self, model) -> TermTable:
-        if self._terms is None:
-            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
-        return self._terms
 
     def __call__(self, model, initial_temp: float, final_temp: float, decreasing_rate: float, boltzmann: float = 1.0,
                  same_state_max: int = 100):
         terms = self.term_table(model)
         with self._learner(model) as L:
             self.records = L.anneal(terms, initial_temp, final_temp, decreasing_rate, boltzmann, same_state_max, self._chains,
-                                    self._seed + self._calls, self._rule, self._max_proposals)
-            self._calls += 1
+                                    self._next_seed(), self._rule, self._max_proposals)
             out = self._finish(model, L)
-            self.last.update({name: L.info(name) for name in ("anneal_ns", "anneal_chains", "anneal_steps")})
-            self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
-                              "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+            self._note(L, terms, ("anneal_ns", "anneal_chains", "anneal_steps"))
             return out
 
 
-class HillClimbing(_Search):
+class HillClimbing(_TermSearch):
     """Tabu hill climbing over add, delete and reverse moves (Learner.climb; the search of bnlearn's hc / tabu and pgmpy's
     HillClimbSearch, not in the reference).  `hc(model, tabu_len=0, max_worse=0, perturb=0, max_steps=0)`: `runs` independent runs,
     run 0 from the model's graph and the others from perturbed copies of it, the best graph returned as (FlatModel with CPTs
@@ -714,32 +725,13 @@ class HillClimbing(_Search):
     def __init__(self, criterion, sampling, max_parents: int = 3, runs: int = 1, seed=None, device: int = _lib.BN_DEVICE_CURRENT):
         super().__init__(criterion, sampling, max_parents, seed, device)
         self._runs = int(runs)
-        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
-        self._calls = 0
-        self._terms = None
-        self.records = None   # Learner.climb's records of the last call
-
-    def close(self) -> None:
-        if getattr(self, "_terms", None) is not None:
-            self._terms.close()
-            self._terms = None
-
-    __del__ = close
-
-    def term_table(self, model) -> TermTable:
-        if self._terms is None:
-            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
-        return self._terms
 
     def __call__(self, model, tabu_len: int = 0, max_worse: int = 0, perturb: int = 0, max_steps: int = 0):
         terms = self.term_table(model)
         with self._learner(model) as L:
-            self.records = L.climb(terms, tabu_len, max_worse, self._runs, perturb, self._seed + self._calls, max_steps=max_steps)
-            self._calls += 1
+            self.records = L.climb(terms, tabu_len, max_worse, self._runs, perturb, self._next_seed(), max_steps=max_steps)
             out = self._finish(model, L)
-            self.last.update({name: L.info(name) for name in ("climb_ns", "climb_runs", "climb_steps")})
-            self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
-                              "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+            self._note(L, terms, ("climb_ns", "climb_runs", "climb_steps"))
             return out
 
 
@@ -777,7 +769,7 @@ class _Stream:
         return (self.next() + 0.5) * 2.0 ** -32
 
 
-class StepwiseStructureHC(_Search):
+class StepwiseStructureHC(_TermSearch):
     """bn::learning::stepwise_structure_hc<Eval, BetweenLearning> (stepwise_structure_hc.hpp): nodes are clustered by mutual
     information; the two most similar clusters are merged, edges from the one to the other learned with `learn_with_hint`, and the
     merged cluster's pairs with the others pruned at random (`alpha`: 0 prunes nothing, 1 everything).  `hc(model, alpha)` returns
@@ -795,38 +787,19 @@ class StepwiseStructureHC(_Search):
         self._between = Greedy if between is None else between
         self._runs = int(runs)
         self._seeded = seed is not None
-        self._seed = int(self._rng.integers(1 << 62)) if seed is None else int(seed)
-        self._calls = 0
-        self._terms = None
-        self.records = None   # Learner.hc's records of the last call (device path)
-
-    def close(self) -> None:
-        if getattr(self, "_terms", None) is not None:
-            self._terms.close()
-            self._terms = None
-
-    __del__ = close
-
-    def term_table(self, model) -> TermTable:
-        if self._terms is None:
-            self._terms = TermTable(self._ensure_table(model), self._max_parents, self._name)
-        return self._terms
 
     def _resident(self) -> bool:
         return self._between is Greedy or isinstance(self._between, Greedy)
 
     def __call__(self, model, alpha: float):
         table = self._ensure_table(model)
-        seed = self._seed + self._calls
-        self._calls += 1
+        seed = self._next_seed()
         with Learner(table, None, self._name, self._max_parents) as L:   # (:134: erase_all_edge)
             if self._resident():
                 terms = self.term_table(model)
                 self.records = L.hc(terms, alpha, self._runs, seed)
                 out = self._finish(model, L)
-                self.last.update({name: L.info(name) for name in ("hc_ns", "hc_runs", "hc_merges")})
-                self.last.update({"winner": self.records["winner"], "term_entries": terms.info("entries"), "term_passes": terms.info("passes"),
-                                  "term_families_scored": terms.info("families_scored"), "term_build_ns": terms.info("build_ns")})
+                self._note(L, terms, ("hc_ns", "hc_runs", "hc_merges"))
                 return out
             merges = self._host_run(L, table, float(alpha), seed)
             out = self._finish(model, L)

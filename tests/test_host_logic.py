@@ -343,6 +343,11 @@ def test_hot_kernels_do_not_spill(bnlib):
     assert len(mpe_mid) == 6   # {1, 2, 4 rounds} x {sweep, finishing launch}
     for name, r in mpe_mid.items():
         assert r["vgpr"] <= 128 and r["spill"] == 0, (name, r)
+    for obj, kernel in (("bn_learn_anneal.o", "learn_anneal_kernel"), ("bn_learn_hc.o", "learn_hc_kernel"), ("bn_learn_climb.o", "learn_climb_kernel")):
+        hit = {name: r for name, r in kr.kernel_resources(os.path.join(csrc, obj)).items() if kernel in name}   # the three search kernels
+        assert len(hit) == 1, (obj, sorted(hit))
+        for name, r in hit.items():
+            assert r["spill"] == 0 and r["scratch"] == 0, (name, r)
 
 
 def test_small_plan_emulated_equals_oracle(bnlib, oracle_mod):
