@@ -67,6 +67,14 @@ class ScoreSpec(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("ess", ctypes.c_double)]
 
 
+class PcParams(ctypes.Structure):   # bn_pc_params
+    _fields_ = [("alpha", ctypes.c_double), ("max_cond", ctypes.c_int32), ("df_rule", ctypes.c_int32), ("max_tests", ctypes.c_int64)]
+
+
+class PcLevel(ctypes.Structure):   # bn_pc_level
+    _fields_ = [("tests", ctypes.c_int64), ("removed", ctypes.c_int64), ("count_ns", ctypes.c_double), ("stat_ns", ctypes.c_double)]
+
+
 class LayoutInfo(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_classes", ctypes.c_int32),
                 ("n_tiles", ctypes.c_int32), ("lanes_per_node_max", ctypes.c_int32),
@@ -206,6 +214,11 @@ SYMBOLS = [
     ("bn_learn_create_spec", ctypes.c_int, [ctypes.c_void_p, i32p, i32p, ctypes.c_int32, ctypes.POINTER(ScoreSpec), ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_void_p)]),
     ("bn_terms_create_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bn_ci_tests", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, i32p, i32p, i32p, i32p, ctypes.c_int32, ctypes.c_double, f64p, i64p, f64p,
+                                   u8p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_ci_chisq_sf", ctypes.c_int, [ctypes.c_int64, f64p, i64p, f64p]),
+    ("bn_learn_pc", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PcParams), u8p, u8p, u8p, i32p, i32p, ctypes.POINTER(PcLevel), i32p, i64p]),
+    ("bn_pdag_to_dag", ctypes.c_int, [ctypes.c_int32, u8p, i32p, i32p]),
 ]
 
 

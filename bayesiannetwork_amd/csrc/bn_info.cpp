@@ -328,6 +328,11 @@ extern "C" int bn_info_get(const bn_info_table* t, const char* name, int64_t* va
     else if (s == "learn_count_ns") *value_out = int64_t(t->learn_count_ns);
     else if (s == "learn_lattice_ns") *value_out = int64_t(t->learn_lattice_ns);
     else if (s == "learn_score_ns") *value_out = int64_t(t->learn_score_ns);
-    else return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes, learn_count_ns, learn_lattice_ns, learn_score_ns)");
+    else if (s == "ci_count_ns") *value_out = int64_t(t->ci_count_ns);
+    else if (s == "ci_stat_ns") *value_out = int64_t(t->ci_stat_ns);
+    else if (s == "ci_launches") *value_out = t->ci_launches;
+    else
+        return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes, learn_count_ns, learn_lattice_ns, learn_score_ns, ci_count_ns, "
+                                "ci_stat_ns, ci_launches)");
     return BN_OK;
 }

@@ -19,6 +19,10 @@ struct bn_info_table {
     float last_pairs_ms = 0.0f;
     // device time of the kernels of the last bn_learn_score_groups / bn_learn_score_subsets call (bn_info_get "learn_*_ns")
     double learn_count_ns = 0.0, learn_lattice_ns = 0.0, learn_score_ns = 0.0;
+    // device time of the counting and statistic kernels of the last bn_ci_tests / bn_learn_pc call (0 when it was refused), and the
+    // number of kernels those calls have launched on the table so far (bn_info_get "ci_count_ns", "ci_stat_ns", "ci_launches")
+    double ci_count_ns = 0.0, ci_stat_ns = 0.0;
+    int64_t ci_launches = 0;
 
     InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
     ~bn_info_table() {   // (the members' own destructors would run after the guard's)

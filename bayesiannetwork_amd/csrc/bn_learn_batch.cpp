@@ -16,9 +16,11 @@ int cu_count(const bn_info_table* t) {
     return cus;
 }
 
+}  // namespace
+
 // Workgroups the patterns are split over per chunk.  A short batch leaves a long table to a handful of CUs: split the patterns until
 // about four workgroups per CU exist, each keeping at least two tiles (bn_score_nodes' rule).  BN_LEARN_SPLITS > 0 fixes the number.
-int count_splits(const bn_info_table* t, int32_t n_chunks) {
+int bn_eng::count_splits(const bn_info_table* t, int32_t n_chunks) {
     int splits = 0;
     if (const char* env = std::getenv("BN_LEARN_SPLITS")) splits = std::atoi(env);
     if (splits <= 0) {
@@ -28,8 +30,6 @@ int count_splits(const bn_info_table* t, int32_t n_chunks) {
     }
     return std::max(1, std::min(splits, 65535));
 }
-
-}  // namespace
 
 int bn_eng::run_groups(bn_info_table* t, const bn_score_spec& spec, const std::vector<GroupIn>& groups, double* ll_out, uint64_t* counts_out,
                        LearnTimes* times) {

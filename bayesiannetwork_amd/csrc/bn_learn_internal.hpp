@@ -62,6 +62,8 @@ int run_groups(bn_info_table* t, const bn_score_spec& spec, const std::vector<Gr
 // ll_out [2^m] in mask order (bit j: cand[j] is a parent); counts_out: null, or every family's counts in the fitted layout, mask order
 int run_subsets(bn_info_table* t, const bn_score_spec& spec, int32_t child, int32_t n_base, const int32_t* base, int32_t m, const int32_t* cand,
                 double* ll_out, uint64_t* counts_out, LearnTimes* times);
+// workgroups the counting launch splits the patterns over per chunk (bn_learn_batch.cpp; bn_learn_pc.cpp counts the same way)
+int count_splits(const bn_info_table* t, int32_t n_chunks);
 }  // namespace bn_eng
 
 // What a node reaches over a `children` adjacency (graph.hpp:270, is_able_trace); the marks and the stack are kept between searches.

@@ -14,7 +14,10 @@ bn_score_nodes.  Not in the reference: `log_likelihood_rows` (per distinct patte
 (per node, optionally with the family counts), `log_cpt` and `parameters` as functions of their own.
 
 `BDeu(ess)` and `K2Score()` are the Bayesian-Dirichlet scores (not in the reference): called on a model and a table they give minus
-the log marginal likelihood of the table under the model's structure, the function learning.py's searches minimise under them."""
+the log marginal likelihood of the table under the model's structure, the function learning.py's searches minimise under them.
+
+`ci_tests(table, tests)` runs a batch of G^2 conditional-independence tests "x independent of y given S" (bn_ci_tests: the tests of
+bnlearn's ci.test "mi" / "mi-adf"; not in the reference) and `chisq_sf(g, df)` evaluates their chi-square tail on the device."""
 from __future__ import annotations
 
 import ctypes
@@ -320,3 +323,66 @@ class K2Score(_BDScore):
 
     def __repr__(self):
         return "K2Score()"
+
+
+# ---- conditional-independence tests (bn_ci_tests, bn_ci_chisq_sf) ----------------------------------
+
+DF_RULES = {"nominal": 0, "adjusted": 1}
+
+
+def _df_rule(df_rule) -> int:
+    if df_rule in DF_RULES:
+        return DF_RULES[df_rule]
+    if df_rule in (0, 1):
+        return int(df_rule)
+    raise ValueError('df_rule: "nominal" (bnlearn mi) or "adjusted" (mi-adf)')
+
+
+def ci_tests(table: InfoTable, tests, df_rule="nominal", counts: bool = False, alpha: float = 0.05) -> dict:
+    """tests: [(x, y, S), ...], S any iterable of columns in any order.  Returns {"stat": G [T], "df": int64 [T], "p": [T],
+    "independent": bool [T] (p > alpha)}; counts=True adds "counts": per test the uint64 table N[s][b][a] (s over the sorted S,
+    b the state of y, a the state of x) of shape (strata, k_y, k_x).  The library groups the tests by (x, S); no result depends on
+    their order."""
+    tests = [(int(x), int(y), [int(v) for v in s]) for x, y, s in tests]
+    T = len(tests)
+    xs = np.array([t[0] for t in tests], dtype=np.int32)
+    ys = np.array([t[1] for t in tests], dtype=np.int32)
+    sptr = np.zeros(T + 1, dtype=np.int32)
+    for i, t in enumerate(tests):
+        sptr[i + 1] = sptr[i] + len(t[2])
+    sidx = np.array([v for t in tests for v in t[2]], dtype=np.int32)
+    stat, p = np.zeros(max(T, 1)), np.zeros(max(T, 1))
+    df, ind = np.zeros(max(T, 1), dtype=np.int64), np.zeros(max(T, 1), dtype=np.uint8)
+    N, shapes = None, []
+    if counts:
+        k, ok = table.k, True
+        for x, y, s in tests:
+            if not all(0 <= v < table.n for v in [x, y] + s):
+                ok = False   # (out of range: the library names the test)
+                break
+            shapes.append((math.prod(int(k[v]) for v in set(s)), int(k[y]), int(k[x])))
+        N = np.zeros(max(sum(a * b * c for a, b, c in shapes) if ok else 1, 1), dtype=np.uint64)
+    _lib.check(_lib.lib().bn_ci_tests(table._h, T, _p(xs, ctypes.c_int32), _p(ys, ctypes.c_int32), _p(sptr, ctypes.c_int32),
+                                      _p(sidx, ctypes.c_int32), _df_rule(df_rule), float(alpha), _p(stat, ctypes.c_double),
+                                      _p(df, ctypes.c_int64), _p(p, ctypes.c_double), _p(ind, ctypes.c_uint8),
+                                      _p(N, ctypes.c_uint64) if counts else None))
+    out = {"stat": stat[:T], "df": df[:T], "p": p[:T], "independent": ind[:T].astype(bool)}
+    if counts:
+        blocks, at = [], 0
+        for shape in shapes:
+            size = shape[0] * shape[1] * shape[2]
+            blocks.append(N[at:at + size].reshape(shape))
+            at += size
+        out["counts"] = blocks
+    return out
+
+
+def chisq_sf(g, df) -> np.ndarray:
+    """The chi-square upper tail Q(df / 2, g / 2) as the header states it, evaluated on the current device (bn_ci_chisq_sf)."""
+    g = np.ascontiguousarray(np.atleast_1d(g), dtype=np.float64)
+    df = np.ascontiguousarray(np.atleast_1d(df), dtype=np.int64)
+    if g.shape != df.shape:
+        raise ValueError("one df per g")
+    out = np.zeros(max(g.size, 1))
+    _lib.check(_lib.lib().bn_ci_chisq_sf(g.size, _p(g, ctypes.c_double), _p(df, ctypes.c_int64), _p(out, ctypes.c_double)))
+    return out[:g.size]

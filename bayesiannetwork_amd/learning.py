@@ -14,6 +14,9 @@ the reference's simulated annealing (simulated_annealing.hpp) as many independen
 stochastic pruning (stepwise_structure_hc.hpp) as many device-resident runs over the same table and the all-pairs mutual
 information; `StepwiseStructureHC` is its functor.  `Learner.climb` is tabu hill climbing over add, delete and reverse moves (not in
 the reference) as device-resident runs over the same table; `HillClimbing` is its functor.
+`PC` is constraint-based learning (not in the reference): the PC-stable skeleton from G^2 conditional-independence tests decided level
+by level on the device (bn_learn_pc), then v-structures and Meek's rules; it returns the equivalence class (`PCResult.cpdag`) with
+the separating sets, and `cpdag_to_dag` gives one DAG of the class, which can seed a `Learner`.
 The learner's score takes the DEVICE's fp64 logarithm (the header states the function); `AIC` / `MDL` of
 the learned model through evaluation.py agree with it to a few ulp per term, not bit for bit.
 
@@ -863,3 +866,75 @@ class StepwiseStructureHC(_TermSearch):
                         continue
                     sims.append((c, new, new_value))
         return merges
+
+
+# ---- constraint-based learning: PC-stable (bn_learn_pc, bn_pdag_to_dag) ------------------------------
+
+class PCResult:
+    """skeleton, cpdag: [n][n] uint8 marks (both [a][b] and [b][a] set: a - b; only [a][b]: a -> b); sepsets: {(a, b) with a < b:
+    tuple S} for every removed edge; levels: per level {"tests", "removed", "count_ns", "stat_ns"}; tests_skipped: tests over the
+    2^20-cell limit (not run, dependent)."""
+
+    def __init__(self, skeleton, cpdag, sepsets, levels, tests_skipped):
+        self.skeleton, self.cpdag, self.sepsets, self.levels, self.tests_skipped = skeleton, cpdag, sepsets, levels, tests_skipped
+
+    def dag(self):
+        """Per-node parent lists of a consistent DAG extension of the cpdag."""
+        return cpdag_to_dag(self.cpdag)
+
+
+def cpdag_to_dag(cpdag):
+    """A consistent DAG extension of a PDAG mark matrix (Dor-Tarsi, the lowest eligible node first) as per-node parent lists,
+    parents increasing: what `Learner(table, structure=...)` takes.  No extension: BnError (BN_ERR_STATE)."""
+    m = np.ascontiguousarray(cpdag, dtype=np.uint8)
+    n = m.shape[0]
+    if m.shape != (n, n):
+        raise ValueError("cpdag must be [n][n]")
+    ptr = np.zeros(n + 1, dtype=np.int32)
+    idx = np.zeros(max(n * (n - 1) // 2, 1), dtype=np.int32)
+    _lib.check(_lib.lib().bn_pdag_to_dag(n, _p(m, ctypes.c_uint8), _p(ptr, ctypes.c_int32), _p(idx, ctypes.c_int32)))
+    return [idx[ptr[v]:ptr[v + 1]].tolist() for v in range(n)]
+
+
+class PC:
+    """PC-stable under the G^2 test: `PC(alpha, max_cond, df_rule)(table_or_model, start=None)`.  A test is independent iff its
+    p-value > alpha; levels |S| = 0 .. max_cond (at most 8); df_rule "nominal" (bnlearn mi) or "adjusted" (mi-adf).  `sampling` (an
+    InfoTable or an engine.Sampler) is needed when the call is given a model instead of a table; `start` is a symmetric [n][n]
+    adjacency to begin from instead of the complete graph.  max_tests: the per-level cap (0: the library's default, 2^22)."""
+
+    def __init__(self, alpha: float = 0.05, max_cond: int = 3, df_rule="nominal", sampling=None, max_tests: int = 0,
+                 device: int = _lib.BN_DEVICE_CURRENT):
+        from .evaluation import _df_rule
+        self.alpha, self.max_cond, self.df_rule, self.max_tests = float(alpha), int(max_cond), _df_rule(df_rule), int(max_tests)
+        self._sampling, self._device = sampling, device
+
+    def __call__(self, table_or_model, start=None) -> PCResult:
+        if isinstance(table_or_model, InfoTable):
+            table = table_or_model
+        elif isinstance(self._sampling, InfoTable):
+            table = self._sampling
+        elif self._sampling is not None:
+            table = table_from_sampler(self._sampling, range(table_or_model.n), table_or_model.k, self._device)
+        else:
+            raise ValueError("PC: give an InfoTable, or a model with PC(sampling=...)")
+        n, mc = table.n, self.max_cond
+        params = _lib.PcParams(self.alpha, mc, self.df_rule, self.max_tests)
+        st = None
+        if start is not None:
+            st = np.ascontiguousarray(np.asarray(start) != 0, dtype=np.uint8)
+            if st.shape != (n, n):
+                raise ValueError("start must be [n][n]")
+        skel, cpdag = np.zeros((n, n), dtype=np.uint8), np.zeros((n, n), dtype=np.uint8)
+        sep_len = np.full((n, n), -1, dtype=np.int32)
+        sep_idx = np.zeros((n, n, max(mc, 1)), dtype=np.int32)
+        levels = (_lib.PcLevel * (max(mc, 0) + 1))()
+        n_levels, skipped = ctypes.c_int32(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().bn_learn_pc(table._h, ctypes.byref(params), _p(st, ctypes.c_uint8) if st is not None else None,
+                                          _p(skel, ctypes.c_uint8), _p(cpdag, ctypes.c_uint8), _p(sep_len, ctypes.c_int32),
+                                          _p(sep_idx, ctypes.c_int32) if mc > 0 else None, levels, ctypes.byref(n_levels),
+                                          ctypes.byref(skipped)))
+        sepsets = {(a, b): tuple(int(v) for v in sep_idx[a, b, :sep_len[a, b]])
+                   for a in range(n) for b in range(a + 1, n) if sep_len[a, b] >= 0}
+        recs = [{"tests": int(levels[i].tests), "removed": int(levels[i].removed), "count_ns": float(levels[i].count_ns),
+                 "stat_ns": float(levels[i].stat_ns)} for i in range(n_levels.value)]
+        return PCResult(skel, cpdag, sepsets, recs, int(skipped.value))

@@ -1033,6 +1033,100 @@ int bn_learn_create_spec(bn_info_table *table, const int32_t *in_ptr, const int3
                          const bn_score_spec *spec, int32_t max_parents, bn_learner **out);
 int bn_terms_create_spec(bn_info_table *table, const bn_score_spec *spec, int32_t max_parents, bn_term_table **out);
 
+/* ---- conditional-independence tests (G^2) and constraint-based structure learning (PC-stable); not in the reference: the tests of
+ *      bnlearn's ci.test "mi" / "mi-adf" and the search of its pc.stable, pgmpy's PC and pcalg. ----
+ *
+ *   A TEST is (x, y, S): "x independent of y given S", x != y, neither in S, |S| <= 8, S in any order (it is sorted increasing; a
+ *   duplicate is BN_ERR_ARG).  Its table has k_x * k_y * prod k_S <= 2^20 cells (bn_learn_score_groups' family limit).
+ *     N[s][b][a]  exact uint64 counts: s the mixed-radix index over the sorted S, first column most significant, b the state of y, a
+ *                 the state of x, least significant; cell r = (s * k_y + b) * k_x + a.  They are the counts bn_learn_score_groups
+ *                 makes for the group "child x, base S, candidate y", taken through the same counting launch: the library groups
+ *                 the tests by (x, S) itself, and no result depends on the grouping, the order of the tests, the split
+ *                 (BN_LEARN_SPLITS), the passes over the count scratch or the order of the patterns.
+ *     marginals   per stratum s: N_s, row sums R[s][b] = sum over a, column sums C[s][a] = sum over b; uint64, exact.
+ *     G           over the cells r with N != 0:  t_r = double(N) * log((double(N) * double(N_s)) / (double(R) * double(C))), every
+ *                 operation a plain fp64 one, log the DEVICE's fp64 log; the additions are bn_score_nodes': 256 partial sums (partial
+ *                 t takes r = t, t + 256, ... from +0.0), folded by halves; G = 2.0 * sum; a G that is not > 0.0 (a rounding below
+ *                 zero, -0.0) is +0.0.
+ *     df (int64)  df_rule 0, nominal (bnlearn "mi"):  (k_x - 1) * (k_y - 1) * prod k_S;
+ *                 df_rule 1, adjusted (bnlearn "mi-adf"):  the sum over the strata with N_s != 0 of
+ *                 (rows b with R != 0, minus 1) * (columns a with C != 0, minus 1).
+ *     p           chisq_sf(G, df), the chi-square upper tail Q(df / 2, G / 2) as this function (plain fp64 operations, the device's
+ *                 log and exp, lgamma_pos above):
+ *                   if (df <= 0 || !(G > 0.0)) return 1.0;
+ *                   a = 0.5 * double(df);  x = 0.5 * G;  pref = exp(((a * log(x)) - x) - lgamma_pos(a));
+ *                   if (x < a + 1.0) {                                  the series for P
+ *                     ap = a;  del = 1.0 / a;  sum = del;
+ *                     repeat at most 100000 times { ap = ap + 1.0;  del = (del * x) / ap;  sum = sum + del;
+ *                                                   if (del < sum * 2^-52) break; }
+ *                     q = 1.0 - (sum * pref);
+ *                   } else {                                            the continued fraction for Q, modified Lentz
+ *                     b = (x + 1.0) - a;  c = 1.0 / 2^-1000;  d = 1.0 / b;  h = d;
+ *                     for i = 1 .. 100000 { an = (-double(i)) * (double(i) - a);  b = b + 2.0;
+ *                                           d = (an * d) + b;   if (fabs(d) < 2^-1000) d = 2^-1000;
+ *                                           c = b + (an / c);   if (fabs(c) < 2^-1000) c = 2^-1000;
+ *                                           d = 1.0 / d;  del = d * c;  h = h * del;
+ *                                           if (fabs(del - 1.0) < 2^-52) break; }
+ *                     q = pref * h;
+ *                   }
+ *                   if (!(q > 0.0)) return 0.0;   return q > 1.0 ? 1.0 : q;
+ *                 Both loops end after about sqrt(2 a log(2^52)) steps (some 6500 at df = 2^20), far below the cap.  Never NaN; a
+ *                 vanishing tail is 0.0 or a denormal.
+ *     decision    the test is INDEPENDENT iff p > alpha (bnlearn's rule), 0 < alpha < 1.
+ *   G, df and p of a test are functions of its counts alone: the same bits alone, twice in a batch, in any batch, inside bn_learn_pc.
+ *   bn_ci_tests: tests in CSR form (x, y [n_tests], s_ptr [n_tests + 1], s_idx); stat_out, df_out, p_out [n_tests]; indep_out NULL
+ *   or [n_tests] (1: independent); counts_out NULL or every test's N back to back in the order of the tests.  BN_ERR_ARG (the text
+ *   names the test, nothing is launched): x == y, x or y in S, a duplicate in S, |S| > 8, an id out of range, more than 2^20 cells,
+ *   df_rule not 0 or 1, alpha outside (0, 1).
+ *   bn_ci_chisq_sf: p_out[i] = chisq_sf(g[i], df[i]) evaluated ON THE DEVICE (the current one); g finite and >= 0, df >= 0.
+ *   bn_info_get "ci_count_ns", "ci_stat_ns": device time of the counting and statistic kernels of the last bn_ci_tests / bn_learn_pc
+ *   call on the table (0 after a refused call); "ci_launches": kernels those calls have launched on the table so far.
+ *   The environment variable BN_CI_SCRATCH_CELLS (> 0) lowers the cells of the count scratch per pass (default 2^25), so that small
+ *   batches take several passes and bn_learn_pc's levels several chunks: a test arrangement, no result depends on it.
+ *
+ *   bn_learn_pc: the order-independent ("stable") PC skeleton, then orientation.  n <= 1024 columns.
+ *     Start: the complete graph over the columns, or start_adj [n][n] (symmetric, the diagonal is not read).
+ *     Level l = 0, 1, ..., max_cond (0 .. 8).  With A the adjacency at the START of the level: for every ordered pair (x, y) adjacent
+ *     in A with |A(x) \ {y}| >= l, one test (x, y, S) for every S in A(x) \ {y} with |S| = l; at l = 0 only x < y.  The RANK of a test
+ *     among those of its edge {x, y} is side * C(|A(min)| - 1, l) + the lexicographic index of S among the l-subsets of
+ *     A(x) \ {y}, side 0 when x = min(x, y) and 1 otherwise (C(m, l) = 0 for m < l): increasing (side, S lexicographic).  After the
+ *     level the edge is removed iff one of its tests is independent, and sepset(x, y) is the S of its LOWEST-RANK independent test
+ *     (on the device one uint32 atomicMin per edge; the host reads back one rank per edge and nothing else).  Every test of a level
+ *     is run.  The search stops when no ordered pair qualifies at level l or after level max_cond.
+ *     A test over 2^20 cells is not run and counts as dependent; tests_skipped_out sums them.  A level that asks for more than
+ *     max_tests tests (over-limit ones included; 0: the default 2^22, at most 2^26) refuses the call with BN_ERR_STATE naming the
+ *     level and the number; nothing is trimmed and no output is written.
+ *     Orientation (host).  v-structures: for every z, x < y in increasing (z, x, y) with x - z - y, x and y not adjacent, a recorded
+ *     sepset(x, y) and z not in it: x -> z <- y; an edge already oriented the other way stays (the first orientation wins).  Then
+ *     Meek's R1, R2, R3 to a fixed point: a scan visits the ordered pairs (a, b) in increasing (a, b) and turns an undirected a - b
+ *     into a -> b at once if R1 (some c -> a, c and b not adjacent), else R2 (some c with a -> c -> b), else R3 (some c, d not
+ *     adjacent with a - c, a - d, c -> b, d -> b) applies; scans repeat until one changes nothing.
+ *     Outputs: skeleton_out, cpdag_out [n][n] uint8 marks (both [a][b] and [b][a] set: a - b; only [a][b]: a -> b); sep_len_out
+ *     [n][n] (-1: none recorded: the pair is adjacent, or was not adjacent at the start), sep_idx_out [n][n][max_cond] (increasing;
+ *     may be NULL when max_cond == 0); levels_out [max_cond + 1] records, *n_levels_out of them written; tests_skipped_out may be NULL.
+ *   bn_pdag_to_dag: a consistent DAG extension of a PDAG in the same marks (Dor-Tarsi): while nodes remain, the LOWEST node with no
+ *   outgoing directed edge to a remaining node and whose every undirected remaining neighbour is adjacent to all other remaining
+ *   nodes adjacent to it takes its undirected edges as incoming and is removed.  in_ptr_out [n + 1], in_idx_out [adjacent pairs],
+ *   parents increasing: what bn_learn_create takes.  No such node at some step: BN_ERR_STATE, the PDAG has no extension. */
+typedef struct bn_pc_params {
+    double alpha;        /* a test is independent iff p > alpha */
+    int32_t max_cond;    /* the last level (largest |S|), 0 .. 8 */
+    int32_t df_rule;     /* 0 nominal, 1 adjusted */
+    int64_t max_tests;   /* per level; 0: 2^22 */
+} bn_pc_params;
+typedef struct bn_pc_level {
+    int64_t tests, removed;     /* tests run at the level; edges it removed */
+    double count_ns, stat_ns;   /* device time of its counting and statistic kernels */
+} bn_pc_level;
+int bn_ci_tests(bn_info_table *table, int32_t n_tests, const int32_t *x, const int32_t *y, const int32_t *s_ptr, const int32_t *s_idx,
+                int32_t df_rule, double alpha, double *stat_out, int64_t *df_out, double *p_out, uint8_t *indep_out,
+                uint64_t *counts_out);
+int bn_ci_chisq_sf(int64_t n, const double *g, const int64_t *df, double *p_out);
+int bn_learn_pc(bn_info_table *table, const bn_pc_params *params, const uint8_t *start_adj, uint8_t *skeleton_out, uint8_t *cpdag_out,
+                int32_t *sep_len_out, int32_t *sep_idx_out, bn_pc_level *levels_out, int32_t *n_levels_out,
+                int64_t *tests_skipped_out);
+int bn_pdag_to_dag(int32_t n, const uint8_t *pdag, int32_t *in_ptr_out, int32_t *in_idx_out);
+
 /* ---- layout introspection (host only; valid for BN_DEVICE_HOST_ONLY engines too) ---- */
 typedef struct bn_layout_info {
     int32_t n_nodes, n_edges, n_classes, n_tiles;
