@@ -219,6 +219,10 @@ SYMBOLS = [
     ("bn_ci_chisq_sf", ctypes.c_int, [ctypes.c_int64, f64p, i64p, f64p]),
     ("bn_learn_pc", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PcParams), u8p, u8p, u8p, i32p, i32p, ctypes.POINTER(PcLevel), i32p, i64p]),
     ("bn_pdag_to_dag", ctypes.c_int, [ctypes.c_int32, u8p, i32p, i32p]),
+    ("bn_info_cond_pair_entropies", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, f64p, f64p, f64p, f64p]),
+    ("bn_info_cond_pair_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("bn_tree_max_spanning", ctypes.c_int, [ctypes.c_int32, f64p, ctypes.c_int32, ctypes.c_int32, i32p]),
+    ("bn_learn_tree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, i32p, ctypes.c_int32, i32p, f64p, f64p]),
 ]
 
 

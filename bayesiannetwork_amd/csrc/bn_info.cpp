@@ -136,8 +136,10 @@ namespace {
 // column.  hxy [m][m] and h [m] on the host; dump_off / dump: the pair blocks pair_counts asks for.
 // d_mi (device, may be null): [m][m] mi = h[x] + h[y] - hxy[x][y], made on the device from the kernel's own h and hxy; the rows and
 // columns of a wide column, whose entropies are finished on the host, are written from there.
+// cond >= 0 (hz = H(cond)): the conditional form -- h is hxz, hxy is hxyz, the blocks are [k_cond][k_x][k_y], a wide pair is the
+// single call over {x, y, cond} on its automatic route, and d_mi is cmi = hxz[x] + hxz[y] - hxyz[x][y] - hz.
 int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, double* hxy, const std::vector<int64_t>* dump_off,
-              unsigned long long* dump_host, size_t dump_len, double* d_mi = nullptr) {
+              unsigned long long* dump_host, size_t dump_len, double* d_mi = nullptr, int32_t cond = -1, double hz = 0.0) {
     // slots: widths 32, 16, 8, 4, 2 in that order (stable in the caller's order), so each starts aligned
     std::vector<int32_t> order;
     std::vector<int32_t> wide;
@@ -166,6 +168,7 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
         }
     for (size_t i = 0; i < size_t(m) * size_t(m); ++i) hxy[i] = 0.0;
     t->last_pairs_ms = 0.0f;
+    if (cond >= 0) t->cond_pairs_ns = 0.0;
     if (Kpad > 0) {
         EventOwner ev0, ev1;
         DeviceBuf<int32_t> d_ci, d_cv, d_ss, d_sk, d_sc, d_su;
@@ -185,14 +188,15 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
         HIPCHK(hipEventCreate(ev0.put()));
         HIPCHK(hipEventCreate(ev1.put()));
         PairArgs a{t->d_T, t->Ppad, t->d_wd, t->D, int32_t(Kpad / kInfoTile), d_ci, d_cv, d_ss, d_sk, d_sc, d_su, m, t->Nd,
-                   d_hxy, d_h, d_off, d_dump};
+                   d_hxy, d_h, d_off, d_dump, cond >= 0 ? t->d_T + size_t(cond) * size_t(t->Ppad) : nullptr,
+                   cond >= 0 ? t->k[size_t(cond)] : 0};
         const bool flush = t->D > 1 || t->Ppad > kInfoSegment;
         HIPCHK(hipEventRecord(ev0, t->stream));
         if (int e = info_launch_pairs(a, flush, t->stream))
             return fail(BN_ERR_HIP, std::string("all-pairs kernel: ") + hipGetErrorString(hipError_t(e)));
         HIPCHK(hipEventRecord(ev1, t->stream));
         if (d_mi)
-            if (int e = info_launch_mi(d_h, d_hxy, m, d_mi, t->stream))
+            if (int e = cond >= 0 ? info_launch_cmi(d_h, d_hxy, m, hz, d_mi, t->stream) : info_launch_mi(d_h, d_hxy, m, d_mi, t->stream))
                 return fail(BN_ERR_HIP, std::string("mutual-information kernel: ") + hipGetErrorString(hipError_t(e)));
         HIPCHK(hipMemcpyAsync(hxy, d_hxy, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
         std::vector<double> hs(static_cast<size_t>(m));
@@ -200,43 +204,59 @@ int all_pairs(bn_info_table* t, int32_t m, const int32_t* vars, double* h, doubl
         if (dump_off) HIPCHK(hipMemcpyAsync(dump_host, d_dump, dump_len * 8, hipMemcpyDeviceToHost, t->stream));
         HIPCHK(hipStreamSynchronize(t->stream));
         HIPCHK(hipEventElapsedTime(&t->last_pairs_ms, ev0, ev1));
+        if (cond >= 0) t->cond_pairs_ns = double(t->last_pairs_ms) * 1e6;
         for (int32_t u : order) h[u] = hs[size_t(u)];
     }
     // pairs with a column of arity > 32: one dense joint table each (the single call's route, so its bits)
     for (int32_t x : wide)
         for (int32_t y = 0; y < m; ++y) {
             if (t->k[vars[y]] > 32 && y < x) continue;   // (done as (y, x))
-            const int32_t pair[2] = {vars[x], vars[y]};
+            const int32_t set3[3] = {vars[x], vars[y], cond};
             InfoSet s{};
             uint64_t cells = 0;
             int key_bits = 0;
-            if (int r = make_set(t, 2, pair, s, cells, key_bits)) return r;
+            if (int r = make_set(t, cond >= 0 ? 3 : 2, set3, s, cells, key_bits)) return r;
             std::vector<unsigned long long> c;
             const int64_t o = dump_off ? (*dump_off)[size_t(x) * m + y] : -1, o2 = dump_off ? (*dump_off)[size_t(y) * m + x] : -1;
-            if (o >= 0 || o2 >= 0) c.assign(size_t(cells), 0);
+            if (o >= 0 || o2 >= 0) {
+                if (cells == 0 || cells > kInfoDenseMaxCells)
+                    return fail(BN_ERR_ARG, "the counts of a pair with a column of arity > 32 come from the dense route: more than 2^22 cells");
+                c.assign(size_t(cells), 0);
+            }
             double H = 0.0;
-            if (int r = run_entropy(t, s, cells, key_bits, 1, &H, c.empty() ? nullptr : c.data())) return r;
+            if (int r = run_entropy(t, s, cells, key_bits, cond >= 0 && c.empty() ? 0 : 1, &H, c.empty() ? nullptr : c.data())) return r;
             hxy[size_t(x) * m + y] = hxy[size_t(y) * m + x] = H;
             if (x == y) h[x] = H;
             if (c.empty()) continue;
-            // c is in key order: the smaller column the row; a column of arity 1 has no key digit
-            const int32_t kx = t->k[vars[x]], ky = t->k[vars[y]];
-            const bool x_major = vars[x] <= vars[y];
-            for (int32_t i = 0; i < kx; ++i)
-                for (int32_t j = 0; j < ky; ++j) {
-                    unsigned long long v;
-                    if (vars[x] == vars[y]) v = i == j ? c[size_t(i)] : 0;
-                    else v = x_major ? c[size_t(i) * ky + j] : c[size_t(j) * kx + i];
-                    if (o >= 0) dump_host[o + i * ky + j] = v;
-                    if (o2 >= 0 && x != y) dump_host[o2 + j * kx + i] = v;
-                }
+            // c is in key order: the set's columns increasing, the smallest the most significant digit; a column of arity 1 has none
+            const int32_t kx = t->k[vars[x]], ky = t->k[vars[y]], kz = cond >= 0 ? t->k[size_t(cond)] : 1;
+            size_t sx = 0, sy = 0, sz = 0, stride = 1;
+            for (int32_t i = s.nv - 1; i >= 0; --i) {
+                if (s.col[i] == vars[x]) sx = stride;
+                if (s.col[i] == vars[y]) sy = stride;
+                if (s.col[i] == cond) sz = stride;
+                stride *= size_t(s.k[i]);
+            }
+            for (int32_t z = 0; z < kz; ++z)
+                for (int32_t i = 0; i < kx; ++i)
+                    for (int32_t j = 0; j < ky; ++j) {
+                        unsigned long long v;
+                        if (vars[x] == vars[y]) v = i == j ? c[size_t(z) * sz + size_t(i) * sx] : 0;
+                        else v = c[size_t(z) * sz + size_t(i) * sx + size_t(j) * sy];
+                        const int64_t zo = int64_t(z) * kx * ky;
+                        if (o >= 0) dump_host[o + zo + i * ky + j] = v;
+                        if (o2 >= 0 && x != y) dump_host[o2 + zo + j * kx + i] = v;
+                    }
         }
     if (d_mi && !wide.empty()) {
         std::vector<double> rows(wide.size() * size_t(m));
         for (size_t w = 0; w < wide.size(); ++w) {
             const int32_t x = wide[w];
             double* row = rows.data() + w * size_t(m);
-            for (int32_t y = 0; y < m; ++y) row[y] = h[x] + h[y] - hxy[size_t(x) * m + y];   // (= h[y] + h[x] - hxy[y][x]: the column too)
+            for (int32_t y = 0; y < m; ++y) {   // (= h[y] + h[x] - hxy[y][x]: the column too)
+                row[y] = h[x] + h[y] - hxy[size_t(x) * m + y];
+                if (cond >= 0) row[y] = row[y] - hz;
+            }
             HIPCHK(hipMemcpyAsync(d_mi + size_t(x) * m, row, size_t(m) * 8, hipMemcpyHostToDevice, t->stream));
             HIPCHK(hipMemcpy2DAsync(d_mi + x, size_t(m) * 8, row, 8, 8, size_t(m), hipMemcpyHostToDevice, t->stream));
         }
@@ -261,6 +281,55 @@ int info_pair_mi_device(bn_info_table* t, double* d_mi, std::vector<double>& mi_
     return BN_OK;
 }
 
+// the weight matrix of the tree learners, left on the device at d_w [m][m]: mi of `vars` (cond < 0) or cmi given `cond`, and the same
+// matrix on the host (the same bits).  `vars` are in range and do not hold cond; the caller has entered the table's device.
+int info_pair_matrix_device(bn_info_table* t, int32_t cond, int32_t m, const int32_t* vars, double* d_w, std::vector<double>& w_host) {
+    std::vector<double> h(static_cast<size_t>(m)), hxy(size_t(m) * size_t(m));
+    double hz = 0.0;
+    if (cond >= 0) {
+        InfoSet s{};
+        uint64_t cells = 0;
+        int key_bits = 0;
+        if (int r = make_set(t, 1, &cond, s, cells, key_bits)) return r;
+        if (int r = run_entropy(t, s, cells, key_bits, 0, &hz, nullptr)) return r;
+    }
+    if (int r = all_pairs(t, m, vars, h.data(), hxy.data(), nullptr, nullptr, 0, d_w, cond, hz)) return r;
+    w_host.resize(hxy.size());
+    for (int32_t x = 0; x < m; ++x)
+        for (int32_t y = 0; y < m; ++y) {
+            double w = h[size_t(x)] + h[size_t(y)] - hxy[size_t(x) * m + y];
+            if (cond >= 0) w = w - hz;
+            w_host[size_t(x) * m + y] = w;
+        }
+    return BN_OK;
+}
+
+extern "C" int bn_info_cond_pair_entropies(bn_info_table* t, int32_t cond, int32_t m, const int32_t* vars, double* hz_out, double* hxz_out,
+                                           double* hxyz_out, double* cmi_out) {
+    if (!t || !vars || !hz_out || !hxz_out || !hxyz_out) return fail(BN_ERR_ARG, "null argument");
+    if (cond < 0 || cond >= t->n) return fail(BN_ERR_ARG, "conditioning column out of range");
+    if (m <= 0) return fail(BN_ERR_ARG, "m must be > 0");
+    for (int32_t u = 0; u < m; ++u) {
+        if (vars[u] < 0 || vars[u] >= t->n) return fail(BN_ERR_ARG, "variable index out of range");
+        if (vars[u] == cond) return fail(BN_ERR_ARG, "the conditioning column is among vars");
+    }
+    ON_DEVICE(t);
+    InfoSet s{};
+    uint64_t cells = 0;
+    int key_bits = 0;
+    if (int r = make_set(t, 1, &cond, s, cells, key_bits)) return r;
+    if (int r = run_entropy(t, s, cells, key_bits, 0, hz_out, nullptr)) return r;
+    DeviceBuf<double> d_cmi;
+    if (cmi_out)
+        if (int r = dalloc(d_cmi, size_t(m) * size_t(m))) return r;
+    if (int r = all_pairs(t, m, vars, hxz_out, hxyz_out, nullptr, nullptr, 0, cmi_out ? d_cmi.get() : nullptr, cond, *hz_out)) return r;
+    if (cmi_out) {
+        HIPCHK(hipMemcpyAsync(cmi_out, d_cmi, size_t(m) * size_t(m) * 8, hipMemcpyDeviceToHost, t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+    }
+    return BN_OK;
+}
+
 extern "C" int bn_info_pair_entropies(bn_info_table* t, int32_t m, const int32_t* vars, double* h_out, double* hxy_out, double* mi_out) {
     if (!t || !h_out || !hxy_out) return fail(BN_ERR_ARG, "null argument");
     std::vector<int32_t> all;
@@ -281,11 +350,16 @@ extern "C" int bn_info_pair_entropies(bn_info_table* t, int32_t m, const int32_t
     return BN_OK;
 }
 
-extern "C" int bn_info_pair_counts(bn_info_table* t, int32_t n_pairs, const int32_t* pairs, uint64_t* counts_out) {
+namespace {
+
+// cond < 0: the blocks [k_x][k_y] of bn_info_pair_counts; else the blocks [k_cond][k_x][k_y] of bn_info_cond_pair_counts
+int pair_counts(bn_info_table* t, int32_t cond, int32_t n_pairs, const int32_t* pairs, uint64_t* counts_out) {
     if (!t || !counts_out || n_pairs <= 0 || !pairs) return fail(BN_ERR_ARG, "null argument or n_pairs <= 0");
+    const size_t kz = cond >= 0 ? size_t(t->k[size_t(cond)]) : 1;
     std::vector<int32_t> uniq;
     for (int32_t i = 0; i < 2 * n_pairs; ++i) {
         if (pairs[i] < 0 || pairs[i] >= t->n) return fail(BN_ERR_ARG, "variable index out of range");
+        if (pairs[i] == cond) return fail(BN_ERR_ARG, "the conditioning column is among the pairs");
         uniq.push_back(pairs[i]);
     }
     std::sort(uniq.begin(), uniq.end());
@@ -297,20 +371,32 @@ extern "C" int bn_info_pair_counts(bn_info_table* t, int32_t n_pairs, const int3
     for (int32_t i = 0; i < n_pairs; ++i) {
         const int32_t x = pos(pairs[2 * i]), y = pos(pairs[2 * i + 1]);
         int64_t& o = off[size_t(x) * m + y];
-        if (o < 0) { o = len; len += int64_t(t->k[pairs[2 * i]]) * t->k[pairs[2 * i + 1]]; }
+        if (o < 0) { o = len; len += int64_t(kz) * t->k[pairs[2 * i]] * t->k[pairs[2 * i + 1]]; }
         where[size_t(i)] = o;
     }
     std::vector<unsigned long long> dump(size_t(std::max<int64_t>(len, 1)));
     std::vector<double> h(static_cast<size_t>(m)), hxy(size_t(m) * m);
     ON_DEVICE(t);
-    if (int r = all_pairs(t, m, uniq.data(), h.data(), hxy.data(), &off, dump.data(), size_t(len))) return r;
+    if (int r = all_pairs(t, m, uniq.data(), h.data(), hxy.data(), &off, dump.data(), size_t(len), nullptr, cond)) return r;
     uint64_t* o = counts_out;
     for (int32_t i = 0; i < n_pairs; ++i) {
-        const size_t cells = size_t(t->k[pairs[2 * i]]) * size_t(t->k[pairs[2 * i + 1]]);
+        const size_t cells = kz * size_t(t->k[pairs[2 * i]]) * size_t(t->k[pairs[2 * i + 1]]);
         std::copy(dump.begin() + where[size_t(i)], dump.begin() + where[size_t(i)] + int64_t(cells), o);
         o += cells;
     }
     return BN_OK;
+}
+
+}  // namespace
+
+extern "C" int bn_info_pair_counts(bn_info_table* t, int32_t n_pairs, const int32_t* pairs, uint64_t* counts_out) {
+    return pair_counts(t, -1, n_pairs, pairs, counts_out);
+}
+
+extern "C" int bn_info_cond_pair_counts(bn_info_table* t, int32_t cond, int32_t n_pairs, const int32_t* pairs, uint64_t* counts_out) {
+    if (!t) return fail(BN_ERR_ARG, "null argument or n_pairs <= 0");
+    if (cond < 0 || cond >= t->n) return fail(BN_ERR_ARG, "conditioning column out of range");
+    return pair_counts(t, cond, n_pairs, pairs, counts_out);
 }
 
 extern "C" int bn_info_last_pairs_ms(const bn_info_table* t, double* ms_out) {
@@ -331,8 +417,10 @@ extern "C" int bn_info_get(const bn_info_table* t, const char* name, int64_t* va
     else if (s == "ci_count_ns") *value_out = int64_t(t->ci_count_ns);
     else if (s == "ci_stat_ns") *value_out = int64_t(t->ci_stat_ns);
     else if (s == "ci_launches") *value_out = t->ci_launches;
+    else if (s == "cond_pairs_ns") *value_out = int64_t(t->cond_pairs_ns);
+    else if (s == "tree_ns") *value_out = int64_t(t->tree_ns);
     else
         return fail(BN_ERR_ARG, "unknown name (n_vars, n_patterns, digit_passes, learn_count_ns, learn_lattice_ns, learn_score_ns, ci_count_ns, "
-                                "ci_stat_ns, ci_launches)");
+                                "ci_stat_ns, ci_launches, cond_pairs_ns, tree_ns)");
     return BN_OK;
 }

@@ -49,6 +49,10 @@ struct PairArgs {
     double* h;                              // [m]
     const int64_t* dump_off;                // [m][m] offset of the block in `dump`, -1: not wanted (null: no dump)
     unsigned long long* dump;
+    // the conditional form (null / 0: unconditional): the conditioning column's row of T and its arity; then hxy, h and dump hold
+    // H(X, Y, Z), H(X, Z) and the blocks [kz][k_x][k_y]
+    const uint8_t* zrow;
+    int32_t kz;
 };
 
 // each returns a hipError_t value (0: success)
@@ -63,5 +67,7 @@ int info_launch_pairs(const PairArgs& a, bool flush, void* stream);
 // mi[x][y] = h[x] + h[y] - hxy[x][y] over [m][m] on the device (transinformation.hpp:60): the arithmetic bn_info_pair_entropies
 // does on the host, so the same bits
 int info_launch_mi(const double* h, const double* hxy, int32_t m, double* mi, void* stream);
+// cmi[x][y] = hxz[x] + hxz[y] - hxyz[x][y] - hz over [m][m] on the device, left to right
+int info_launch_cmi(const double* hxz, const double* hxyz, int32_t m, double hz, double* cmi, void* stream);
 
 }  // namespace bnmi

@@ -149,7 +149,13 @@ __device__ __forceinline__ v4i onehot(uint4 x, unsigned srep) {
 // (w >> 1, w & 1) as 2 x 2 MFMA 32x32x32 i8 tiles.  K of the MFMA = 32 patterns: lane (r, h) holds
 // the 16 patterns 16h .. 16h+15 of row r for A and of column r for B (the same lane map on both sides,
 // so each A byte meets the B byte of the same pattern).  A = one-hot x digit d of the count, B = one-hot.
-template <bool FLUSH>
+//
+// COND: the conditional form.  For each state s of the column a.zrow (a.kz states, in increasing order) the count digit is also
+// masked by T[z][p] == s -- one match80 on the 16 bytes of z, applied to wv, masks A0 and A1 together -- so the accumulators hold
+// N(x, y, s); the epilogue folds each pair's block into part_s and adds it to the pair's entry (0.0 + part_0 + part_1 + ...).  Every
+// entry has one owner thread, the same for every state, so the sum runs through the output matrix itself.  The table is read
+// once per state.
+template <bool FLUSH, bool COND>
 __global__ __launch_bounds__(256) void info_pairs_mfma(PairArgs a) {
     __shared__ unsigned long long lds[4][32 * 33];
     int ti = 0, b = int(blockIdx.x);
@@ -173,86 +179,102 @@ __global__ __launch_bounds__(256) void info_pairs_mfma(PairArgs a) {
 
     v16i acc[2][2];
     unsigned long long acc64[2][2][FLUSH ? 16 : 1];
-    if (FLUSH)
+    const int nstates = COND ? a.kz : 1;
+    for (int zs = 0; zs < nstates; ++zs) {
+        const unsigned zrep = unsigned(zs) * 0x01010101u;
+        if (FLUSH)
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j)
+                    for (int e = 0; e < 16; ++e) acc64[i][j][FLUSH ? e : 0] = 0;
         for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j)
-                for (int e = 0; e < 16; ++e) acc64[i][j][FLUSH ? e : 0] = 0;
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
+            for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
 
-    if (active) {
-        for (int d = 0; d < a.D; ++d) {
-            const uint8_t* wdp = a.wd + int64_t(d) * a.Ppad + 16 * h;
-            for (int64_t seg = 0; seg < a.Ppad; seg += kInfoSegment) {
-                const int64_t segend = seg + kInfoSegment < a.Ppad ? seg + kInfoSegment : a.Ppad;
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
-                for (int64_t p = seg; p < segend; p += 32) {
-                    const uint4 wv = *reinterpret_cast<const uint4*>(wdp + p);
-                    const uint4 xa0 = *reinterpret_cast<const uint4*>(ap[0] + p);
-                    const uint4 xa1 = *reinterpret_cast<const uint4*>(ap[1] + p);
-                    const uint4 xb0 = *reinterpret_cast<const uint4*>(bp[0] + p);
-                    const uint4 xb1 = *reinterpret_cast<const uint4*>(bp[1] + p);
-                    const v4i A0 = onehot_weighted(xa0, as[0], wv), A1 = onehot_weighted(xa1, as[1], wv);
-                    const v4i B0 = onehot(xb0, bs[0]), B1 = onehot(xb1, bs[1]);
-                    acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A0, B0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A0, B1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A1, B0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A1, B1, acc[1][1], 0, 0, 0);
-                }
-                if (FLUSH)
+        if (active) {
+            for (int d = 0; d < a.D; ++d) {
+                const uint8_t* wdp = a.wd + int64_t(d) * a.Ppad + 16 * h;
+                for (int64_t seg = 0; seg < a.Ppad; seg += kInfoSegment) {
+                    const int64_t segend = seg + kInfoSegment < a.Ppad ? seg + kInfoSegment : a.Ppad;
                     for (int i = 0; i < 2; ++i)
-                        for (int j = 0; j < 2; ++j)
-                            for (int e = 0; e < 16; ++e)
-                                acc64[i][j][FLUSH ? e : 0] +=
-                                    (unsigned long long)(unsigned)acc[i][j][e] << (7 * d);
+                        for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
+                    for (int64_t p = seg; p < segend; p += 32) {
+                        uint4 wv = *reinterpret_cast<const uint4*>(wdp + p);
+                        if (COND) {
+                            const uint4 xz = *reinterpret_cast<const uint4*>(a.zrow + 16 * h + p);
+                            unsigned mz;
+                            mz = match80(xz.x, zrep); wv.x &= mz - (mz >> 7);
+                            mz = match80(xz.y, zrep); wv.y &= mz - (mz >> 7);
+                            mz = match80(xz.z, zrep); wv.z &= mz - (mz >> 7);
+                            mz = match80(xz.w, zrep); wv.w &= mz - (mz >> 7);
+                        }
+                        const uint4 xa0 = *reinterpret_cast<const uint4*>(ap[0] + p);
+                        const uint4 xa1 = *reinterpret_cast<const uint4*>(ap[1] + p);
+                        const uint4 xb0 = *reinterpret_cast<const uint4*>(bp[0] + p);
+                        const uint4 xb1 = *reinterpret_cast<const uint4*>(bp[1] + p);
+                        const v4i A0 = onehot_weighted(xa0, as[0], wv), A1 = onehot_weighted(xa1, as[1], wv);
+                        const v4i B0 = onehot(xb0, bs[0]), B1 = onehot(xb1, bs[1]);
+                        acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A0, B0, acc[0][0], 0, 0, 0);
+                        acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A0, B1, acc[0][1], 0, 0, 0);
+                        acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A1, B0, acc[1][0], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A1, B1, acc[1][1], 0, 0, 0);
+                    }
+                    if (FLUSH)
+                        for (int i = 0; i < 2; ++i)
+                            for (int j = 0; j < 2; ++j)
+                                for (int e = 0; e < 16; ++e)
+                                    acc64[i][j][FLUSH ? e : 0] +=
+                                        (unsigned long long)(unsigned)acc[i][j][e] << (7 * d);
+                }
             }
         }
-    }
 
-    // epilogue: one 32 x 32 quarter at a time through LDS; each aligned k_x x k_y block lies in one quarter
-    unsigned long long* L = lds[w];
-    for (int q = 0; q < 4; ++q) {
-        const int qr = q >> 1, qc = q & 1;
-        if (active)
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * h;   // C/D map of the 32x32 MFMA: column = lane & 31
-                L[row * 33 + r] = FLUSH ? acc64[qr][qc][FLUSH ? e : 0] : (unsigned long long)(unsigned)acc[qr][qc][e];
-            }
-        __syncthreads();
-        if (active)
-            for (int t = lane; t < 32 * 32; t += 64) {
-                const int ra = t >> 5, cb = t & 31;
-                const int R = row0 + qr * 32 + ra, C = col0 + qc * 32 + cb;
-                if (R > C) continue;
-                const int vx = a.colvar[R], vy = a.colvar[C];
-                if (vx < 0 || vy < 0 || a.sv_start[vx] != R || a.sv_start[vy] != C) continue;
-                const int kx = a.sv_k[vx], ky = a.sv_k[vy];
-                const unsigned long long* blk = L + ra * 33 + cb;
-                double part = 0.0;
-                if (a.sv_col[vx] <= a.sv_col[vy]) {   // x the more significant key digit
-                    for (int i = 0; i < kx; ++i)
-                        for (int j = 0; j < ky; ++j) fold_cell(part, blk[i * 33 + j], a.Nd);
-                } else {
-                    for (int j = 0; j < ky; ++j)
-                        for (int i = 0; i < kx; ++i) fold_cell(part, blk[i * 33 + j], a.Nd);
+        // epilogue: one 32 x 32 quarter at a time through LDS; each aligned k_x x k_y block lies in one quarter
+        unsigned long long* L = lds[w];
+        for (int q = 0; q < 4; ++q) {
+            const int qr = q >> 1, qc = q & 1;
+            if (active)
+                for (int e = 0; e < 16; ++e) {
+                    const int row = (e & 3) + 8 * (e >> 2) + 4 * h;   // C/D map of the 32x32 MFMA: column = lane & 31
+                    L[row * 33 + r] = FLUSH ? acc64[qr][qc][FLUSH ? e : 0] : (unsigned long long)(unsigned)acc[qr][qc][e];
                 }
-                const double H = 0.0 + part;
-                const int ux = a.sv_user[vx], uy = a.sv_user[vy];
-                a.hxy[int64_t(ux) * a.m + uy] = H;
-                a.hxy[int64_t(uy) * a.m + ux] = H;
-                if (vx == vy) a.h[ux] = H;
-                if (a.dump_off) {
-                    const int64_t o = a.dump_off[int64_t(ux) * a.m + uy], o2 = a.dump_off[int64_t(uy) * a.m + ux];
-                    for (int i = 0; i < kx; ++i)
-                        for (int j = 0; j < ky; ++j) {
-                            const unsigned long long c = blk[i * 33 + j];
-                            if (o >= 0) a.dump[o + i * ky + j] = c;
-                            if (o2 >= 0 && ux != uy) a.dump[o2 + j * kx + i] = c;
+            __syncthreads();
+            if (active)
+                for (int t = lane; t < 32 * 32; t += 64) {
+                    const int ra = t >> 5, cb = t & 31;
+                    const int R = row0 + qr * 32 + ra, C = col0 + qc * 32 + cb;
+                    if (R > C) continue;
+                    const int vx = a.colvar[R], vy = a.colvar[C];
+                    if (vx < 0 || vy < 0 || a.sv_start[vx] != R || a.sv_start[vy] != C) continue;
+                    const int kx = a.sv_k[vx], ky = a.sv_k[vy];
+                    const unsigned long long* blk = L + ra * 33 + cb;
+                    double part = 0.0;
+                    if (a.sv_col[vx] <= a.sv_col[vy]) {   // x the more significant key digit
+                        for (int i = 0; i < kx; ++i)
+                            for (int j = 0; j < ky; ++j) fold_cell(part, blk[i * 33 + j], a.Nd);
+                    } else {
+                        for (int j = 0; j < ky; ++j)
+                            for (int i = 0; i < kx; ++i) fold_cell(part, blk[i * 33 + j], a.Nd);
+                    }
+                    const int ux = a.sv_user[vx], uy = a.sv_user[vy];
+                    const double H = (COND && zs > 0 ? a.hxy[int64_t(ux) * a.m + uy] : 0.0) + part;
+                    a.hxy[int64_t(ux) * a.m + uy] = H;
+                    a.hxy[int64_t(uy) * a.m + ux] = H;
+                    if (vx == vy) a.h[ux] = H;
+                    if (a.dump_off) {
+                        int64_t o = a.dump_off[int64_t(ux) * a.m + uy], o2 = a.dump_off[int64_t(uy) * a.m + ux];
+                        if (COND) {   // the block of this state: [k_cond][k_x][k_y]
+                            if (o >= 0) o += int64_t(zs) * kx * ky;
+                            if (o2 >= 0) o2 += int64_t(zs) * kx * ky;
                         }
+                        for (int i = 0; i < kx; ++i)
+                            for (int j = 0; j < ky; ++j) {
+                                const unsigned long long c = blk[i * 33 + j];
+                                if (o >= 0) a.dump[o + i * ky + j] = c;
+                                if (o2 >= 0 && ux != uy) a.dump[o2 + j * kx + i] = c;
+                            }
+                    }
                 }
-            }
-        __syncthreads();
+            __syncthreads();
+        }
     }
 }
 
@@ -355,10 +377,29 @@ int info_launch_mi(const double* h, const double* hxy, int32_t m, double* mi, vo
 
 int info_launch_pairs(const PairArgs& a, bool flush, void* stream) {
     const unsigned blocks = unsigned(int64_t(a.ntile) * (a.ntile + 1) / 2);
-    if (flush)
-        hipLaunchKernelGGL(info_pairs_mfma<true>, dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
+    if (a.zrow) {
+        if (flush)
+            hipLaunchKernelGGL((info_pairs_mfma<true, true>), dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
+        else
+            hipLaunchKernelGGL((info_pairs_mfma<false, true>), dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
+    } else if (flush)
+        hipLaunchKernelGGL((info_pairs_mfma<true, false>), dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
     else
-        hipLaunchKernelGGL(info_pairs_mfma<false>, dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
+        hipLaunchKernelGGL((info_pairs_mfma<false, false>), dim3(blocks), dim3(256), 0, hipStream_t(stream), a);
+    return int(hipGetLastError());
+}
+
+__global__ void info_cmi_kernel(const double* __restrict__ hxz, const double* __restrict__ hxyz, int32_t m, double hz,
+                                double* __restrict__ cmi) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= int64_t(m) * m) return;
+    const int32_t x = int32_t(i / m), y = int32_t(i % m);
+    cmi[i] = hxz[x] + hxz[y] - hxyz[i] - hz;
+}
+
+int info_launch_cmi(const double* hxz, const double* hxyz, int32_t m, double hz, double* cmi, void* stream) {
+    const int64_t cells = int64_t(m) * m;
+    hipLaunchKernelGGL(info_cmi_kernel, dim3(unsigned((cells + 255) / 256)), dim3(256), 0, hipStream_t(stream), hxz, hxyz, m, hz, cmi);
     return int(hipGetLastError());
 }
 

@@ -23,6 +23,9 @@ struct bn_info_table {
     // number of kernels those calls have launched on the table so far (bn_info_get "ci_count_ns", "ci_stat_ns", "ci_launches")
     double ci_count_ns = 0.0, ci_stat_ns = 0.0;
     int64_t ci_launches = 0;
+    // device time of the conditional all-pairs kernel of the last bn_info_cond_pair_* / TAN call, and of the spanning-tree kernel of the
+    // last bn_learn_tree call (bn_info_get "cond_pairs_ns", "tree_ns")
+    double cond_pairs_ns = 0.0, tree_ns = 0.0;
 
     InfoDev dev() const { return InfoDev{n, P, Ppad, D, d_T, d_w, d_wd}; }
     ~bn_info_table() {   // (the members' own destructors would run after the guard's)
@@ -35,3 +38,5 @@ struct bn_info_table {
 
 // bn_info.cpp: the all-pairs mutual information of every column, left on the device (bn_learn_hc's similarity matrix)
 int info_pair_mi_device(bn_info_table* t, double* d_mi, std::vector<double>& mi_host);
+// ... and the tree learners' weight matrix over `vars`: mi (cond < 0) or cmi given `cond`, on the device and on the host
+int info_pair_matrix_device(bn_info_table* t, int32_t cond, int32_t m, const int32_t* vars, double* d_w, std::vector<double>& w_host);

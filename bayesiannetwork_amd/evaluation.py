@@ -17,7 +17,10 @@ bn_score_nodes.  Not in the reference: `log_likelihood_rows` (per distinct patte
 the log marginal likelihood of the table under the model's structure, the function learning.py's searches minimise under them.
 
 `ci_tests(table, tests)` runs a batch of G^2 conditional-independence tests "x independent of y given S" (bn_ci_tests: the tests of
-bnlearn's ci.test "mi" / "mi-adf"; not in the reference) and `chisq_sf(g, df)` evaluates their chi-square tail on the device."""
+bnlearn's ci.test "mi" / "mi-adf"; not in the reference) and `chisq_sf(g, df)` evaluates their chi-square tail on the device.
+
+`InfoTable.cond_pair_entropies` / `conditional_mutual_information_matrix` give H(X, Y, Z), H(X, Z), H(Z) and I(X; Y | Z) of every pair
+of columns given one conditioning column at once (bn_info_cond_pair_entropies; not in the reference): the weights of learning.TAN."""
 from __future__ import annotations
 
 import ctypes
@@ -97,6 +100,39 @@ class InfoTable:
         blocks, o = [], 0
         for (x, y), s in zip(pr, sizes):
             blocks.append(out[o:o + s].reshape(int(self.k[x]), int(self.k[y])))
+            o += s
+        return blocks
+
+    def cond_pair_entropies(self, cond: int, variables=None, cmi: bool = True) -> dict:
+        """hz = H(Z), hxz [m] = H(X, Z), hxyz [m][m] = H(X, Y, Z) and (cmi=True) cmi [m][m] = hxz[x] + hxz[y] - hxyz[x][y] - hz for the
+        conditioning column Z = `cond` and the columns `variables` (None: every column but cond)."""
+        cond = int(cond)
+        if variables is None:
+            variables = [v for v in range(self.n) if v != cond]
+        v = np.ascontiguousarray(variables, dtype=np.int32).reshape(-1)
+        m = len(v)
+        hz = ctypes.c_double()
+        hxz, hxyz = np.zeros(max(m, 1)), np.zeros((max(m, 1), max(m, 1)))
+        cm = np.zeros((max(m, 1), max(m, 1))) if cmi else None
+        _lib.check(_lib.lib().bn_info_cond_pair_entropies(self._h, cond, m, _p(v, ctypes.c_int32), ctypes.byref(hz), _p(hxz, ctypes.c_double),
+                                                          _p(hxyz, ctypes.c_double), _p(cm, ctypes.c_double) if cmi else None))
+        out = {"hz": hz.value, "hxz": hxz, "hxyz": hxyz}
+        if cmi:
+            out["cmi"] = cm
+        return out
+
+    def cond_pair_counts(self, cond: int, pairs) -> list:
+        """The exact k_cond x k_x x k_y count blocks of `pairs` [(x, y), ...] as the conditional all-pairs kernel made them."""
+        cond = int(cond)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        kz = int(self.k[cond]) if 0 <= cond < self.n else 1   # (out of range: the library says so)
+        ok = all(0 <= int(v) < self.n for v in pr.reshape(-1))
+        sizes = [kz * int(self.k[x]) * int(self.k[y]) for x, y in pr] if ok else [1]
+        out = np.zeros(max(sum(sizes), 1), dtype=np.uint64)
+        _lib.check(_lib.lib().bn_info_cond_pair_counts(self._h, cond, len(pr), _p(pr, ctypes.c_int32), _p(out, ctypes.c_uint64)))
+        blocks, o = [], 0
+        for (x, y), s in zip(pr, sizes):
+            blocks.append(out[o:o + s].reshape(kz, int(self.k[x]), int(self.k[y])))
             o += s
         return blocks
 
@@ -183,6 +219,26 @@ def mutual_information_matrix(sampler_or_table, variables=None, k=None) -> dict:
     uniq, pos = _columns(vs)
     with table_from_sampler(sampler_or_table, uniq, k) as t:
         return t.pair_entropies(pos)
+
+
+def conditional_mutual_information_matrix(sampler_or_table, cond, variables=None, k=None) -> dict:
+    """Not in the reference: hz, hxz [m], hxyz [m][m] and cmi [m][m] = I(X; Y | cond) of every pair of `variables` at once (None: every
+    column of an InfoTable, every node of a Sampler's patterns, but `cond`)."""
+    if isinstance(sampler_or_table, InfoTable):
+        return sampler_or_table.cond_pair_entropies(cond, variables)
+    cond = int(cond)
+    if variables is None:
+        width = len(next(iter(sampler_or_table.table()))) if sampler_or_table.sampling_size() else 0
+        variables = [v for v in range(width) if v != cond]
+    vs = [int(v) for v in variables]
+    if cond in vs:
+        raise ValueError("the conditioning column is among the variables")
+    if sampler_or_table.sampling_size() == 0:
+        m = len(vs)
+        return {"hz": 0.0, "hxz": np.zeros(m), "hxyz": np.zeros((m, m)), "cmi": np.zeros((m, m))}
+    uniq, pos = _columns(vs + [cond])
+    with table_from_sampler(sampler_or_table, uniq, k) as t:
+        return t.cond_pair_entropies(pos[-1], pos[:-1])
 
 
 # ---- log-likelihood, AIC, MDL (bn_score_* of include/bn_mi355x.h) ---------------------------------

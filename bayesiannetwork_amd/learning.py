@@ -22,7 +22,10 @@ the learned model through evaluation.py agree with it to a few ulp per term, not
 
 Differences from the reference: a family is limited to 16 parents (`max_parents` may lower that) and 2^20 table entries -- a
 candidate beyond them is not added; the returned model carries CPTs fitted to the FINAL structure (the reference leaves the CPTs of
-the last rejected candidate in the graph); `seed=` / `orders=` make the shuffles reproducible."""
+the last rejected candidate in the graph); `seed=` / `orders=` make the shuffles reproducible.
+`ChowLiu` and `TAN` (not in the reference; bnlearn's chow.liu / tree.bayes) are the tree learners: the maximum spanning tree of the
+all-pairs (class-conditional) mutual information, both matrices and the tree made on the device (bn_learn_tree); `max_spanning_tree`
+is the tree of any weight matrix under the library's edge order."""
 from __future__ import annotations
 
 import contextlib
@@ -190,13 +193,16 @@ def score_subsets(table: InfoTable, child: int, base, cand, counts: bool = False
 
 class Learner:
     """bn_learner: a graph over the columns of `table`, its family terms and its score.  `structure`: None (no edges), a
-    FlatModel, or per-node parent lists.  `criterion`: see the module's text; `info("criterion")` gives 0 AIC, 1 MDL, 2 BDeu, 3 K2."""
+    FlatModel, per-node parent lists, or the pair (in_ptr [n + 1], in_idx) that `structure()` returns.  `criterion`: see the module's text; `info("criterion")` gives 0 AIC, 1 MDL, 2 BDeu, 3 K2."""
 
     def __init__(self, table: InfoTable, structure=None, criterion="aic", max_parents: int = MAX_PARENTS):
         if structure is None:
             parents = [[] for _ in range(table.n)]
         elif isinstance(structure, FlatModel):
             parents = [structure.parents(v).tolist() for v in range(structure.n)]
+        elif isinstance(structure, tuple) and len(structure) == 2 and len(structure[0]) == table.n + 1:   # (in_ptr, in_idx)
+            ptr, idx = structure
+            parents = [[int(u) for u in idx[ptr[v]:ptr[v + 1]]] for v in range(table.n)]
         else:
             parents = [list(p) for p in structure]
         if len(parents) != table.n:
@@ -938,3 +944,90 @@ class PC:
         recs = [{"tests": int(levels[i].tests), "removed": int(levels[i].removed), "count_ns": float(levels[i].count_ns),
                  "stat_ns": float(levels[i].stat_ns)} for i in range(n_levels.value)]
         return PCResult(skel, cpdag, sepsets, recs, int(skipped.value))
+
+
+# ---- tree learners: Chow-Liu and tree-augmented naive Bayes (bn_learn_tree, bn_tree_max_spanning) ----
+
+def max_spanning_tree(w, root: int = 0, device: int = _lib.BN_DEVICE_CURRENT) -> np.ndarray:
+    """parent [m] (int32, -1 at `root`) of the maximum spanning tree of the weights w [m][m] under the library's edge order: weight
+    descending, then (min, max) of the end points ascending.  Only the upper triangle is read."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    m = w.shape[0]
+    if w.ndim != 2 or w.shape != (m, m):
+        raise ValueError("w must be [m][m]")
+    parent = np.zeros(max(m, 1), dtype=np.int32)
+    _lib.check(_lib.lib().bn_tree_max_spanning(m, _p(w, ctypes.c_double), int(root), device, _p(parent, ctypes.c_int32)))
+    return parent[:m]
+
+
+class TreeResult:
+    """variables [m]: the columns of the tree; parent [m]: the parent column of variables[i], -1 at the root; weight [m]: the matrix
+    entry of that edge, 0.0 at the root; matrix [m][m]: the mutual information (Chow-Liu) or the mutual information given the class
+    (TAN) of the variables; root: the root column; cond: the class column, -1 for Chow-Liu; n: the table's columns."""
+
+    def __init__(self, n, variables, parent, weight, matrix, root, cond):
+        self.n, self.variables, self.parent, self.weight, self.matrix, self.root, self.cond = n, variables, parent, weight, matrix, root, cond
+
+    def parents(self):
+        """Per column of the table the sorted list of its parents: the tree parent and, for TAN, the class."""
+        out = [[] for _ in range(self.n)]
+        for v, p in zip(self.variables, self.parent):
+            ps = ([int(p)] if p >= 0 else []) + ([self.cond] if self.cond >= 0 else [])
+            out[int(v)] = sorted(ps)
+        return out
+
+    def structure(self):
+        """(in_ptr, in_idx): what `Learner(table, structure=...)` and `structure_model` take."""
+        return _csr(self.parents())
+
+
+class _TreeLearner:
+    def __init__(self, sampling=None, root=None, device: int = _lib.BN_DEVICE_CURRENT):
+        self._sampling, self.root, self._device = sampling, root, device
+
+    def _run(self, table_or_model, what, cond, variables) -> TreeResult:
+        if isinstance(table_or_model, InfoTable):
+            return self._learn(table_or_model, cond, variables)
+        if isinstance(self._sampling, InfoTable):
+            return self._learn(self._sampling, cond, variables)
+        if self._sampling is None:
+            raise ValueError(f"{what}: give an InfoTable, or a model with {what}(sampling=...)")
+        # a sampler: the table made from it lives for this call only
+        with table_from_sampler(self._sampling, range(table_or_model.n), table_or_model.k, self._device) as table:
+            return self._learn(table, cond, variables)
+
+    def _learn(self, table, cond, variables) -> TreeResult:
+        if variables is None:
+            variables = [v for v in range(table.n) if v != cond]
+        v = np.ascontiguousarray(variables, dtype=np.int32).reshape(-1)
+        m = len(v)
+        parent, weight = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1))
+        matrix = np.zeros((max(m, 1), max(m, 1)))
+        root = -1 if self.root is None else int(self.root)
+        _lib.check(_lib.lib().bn_learn_tree(table._h, cond, m, _p(v, ctypes.c_int32), root, _p(parent, ctypes.c_int32),
+                                            _p(weight, ctypes.c_double), _p(matrix, ctypes.c_double)))
+        return TreeResult(table.n, v, parent[:m], weight[:m], matrix[:m, :m], int(v[parent[:m] < 0][0]), cond)
+
+
+class ChowLiu(_TreeLearner):
+    """The Chow-Liu tree (bnlearn chow.liu, pgmpy TreeSearch "chow-liu"): `ChowLiu(sampling=None, root=None)(table_or_model,
+    variables=None)` is the maximum spanning tree of the all-pairs mutual information, oriented away from `root` (None: the lowest
+    column).  `sampling` is needed when the call is given a model instead of a table.  Returns a TreeResult."""
+
+    def __call__(self, table_or_model, variables=None) -> TreeResult:
+        return self._run(table_or_model, "ChowLiu", -1, variables)
+
+
+class TAN(_TreeLearner):
+    """Tree-augmented naive Bayes (bnlearn tree.bayes, pgmpy TreeSearch "tan"): `TAN(class_node, sampling=None, root=None)(
+    table_or_model, variables=None)` is the maximum spanning tree of the features under I(X; Y | class), plus the class as a parent of
+    every feature.  Returns a TreeResult."""
+
+    def __init__(self, class_node: int, sampling=None, root=None, device: int = _lib.BN_DEVICE_CURRENT):
+        super().__init__(sampling, root, device)
+        self.class_node = int(class_node)
+
+    def __call__(self, table_or_model, variables=None) -> TreeResult:
+        if self.class_node < 0:
+            raise ValueError("TAN: the class column must be >= 0")
+        return self._run(table_or_model, "TAN", self.class_node, variables)

@@ -671,6 +671,47 @@ int bn_info_pair_counts(bn_info_table *table, int32_t n_pairs, const int32_t *pa
 int bn_info_last_pairs_ms(const bn_info_table *table, double *ms_out);
 int bn_info_get(const bn_info_table *table, const char *name, int64_t *value_out);
 
+/* ---- all-pairs conditional entropies, maximum spanning tree, Chow-Liu and TAN trees ----
+ * Not in the reference: the tree learners of bnlearn (chow.liu, tree.bayes) and pgmpy (TreeSearch "chow-liu" / "tan").
+ *   bn_info_cond_pair_entropies: for a conditioning column `cond` (any arity 1..255) and m columns `vars`: hz = H(Z), hxz [m] =
+ *   H(X, Z), hxyz [m][m] = H(X, Y, Z) and, if cmi_out is not NULL, cmi [m][m] = I(X; Y | Z).
+ *     Summation order.  For each state s of cond in increasing order, part_s folds `part -= p * log2(p)` from 0.0 over the non-zero
+ *     cells N(x, y, s), p = c / N with N the table's total; within a state the cells are taken in the order bn_info_pair_entropies
+ *     uses for the pair (the lower column the more significant digit).  hxyz[x][y] = 0.0 + part_0 + part_1 + ... in state order; a
+ *     state that never occurs contributes part = 0.0.  So an entry is a function of the exact counts alone.
+ *     Entries.  hxyz is symmetric bit for bit; hxz[x] is its diagonal entry, H(X, Z) in the same order; hz has the bits of
+ *     bn_info_entropy({cond}); cmi[x][y] = hxz[x] + hxz[y] - hxyz[x][y] - hz, evaluated left to right on the device, no clamping.
+ *     Invariances.  An entry does not depend on m, on its position in vars, on duplicates in vars, on the pattern order or on the run.
+ *     With a cond of arity 1, hxyz, hxz and cmi have the bits of bn_info_pair_entropies' hxy, h and mi.
+ *     Arities.  x and y of arity <= 32 go through the conditional form of the all-pairs matrix-core kernel, which reads the table once
+ *     per state of cond.  A pair with a wider column takes the bits of the single call bn_info_entropy({x, y, cond}) (route 0) -- whose
+ *     order is that call's, not the one above -- and hxz of a wider column those of bn_info_entropy({x, cond}).
+ *     Refusals, BN_ERR_ARG with a bn_last_error text and nothing launched: cond out of range, cond among vars, a null pointer (vars
+ *     included; cmi_out may be NULL), m <= 0, a column out of range.
+ *   bn_info_cond_pair_counts: the twin of bn_info_pair_counts: for pair i the exact block [k_cond][k_x][k_y] as the epilogue saw it,
+ *   blocks back to back.  A pair with a column of arity > 32 is counted by the dense route: more than 2^22 cells, BN_ERR_ARG.
+ *   Both set bn_info_last_pairs_ms; bn_info_get "cond_pairs_ns" is the kernel time of the last conditional call, "tree_ns" that of the
+ *   spanning-tree kernel of the last bn_learn_tree.
+ *   bn_tree_max_spanning: the maximum spanning tree of the complete graph over m nodes with the weights w [m][m] (host), oriented from
+ *   `root`.  Edges are totally ordered by weight descending, then by (min(u, v), max(u, v)) ascending; -0.0 and 0.0 compare equal and
+ *   +-inf is allowed.  Under this strict total order the maximum spanning tree is unique, and that tree is the result.  Only w[lo][hi],
+ *   lo < hi, is read.  parent_out[v] is v's neighbour on the path to root, parent_out[root] = -1.  One workgroup runs Prim's algorithm
+ *   with every node's key in LDS: m <= 4096 (beyond: BN_ERR_ARG).  m == 1: no launch.  A NaN in the upper triangle, a root out of
+ *   range, a null pointer, m <= 0: BN_ERR_ARG, checked on the host.
+ *   bn_learn_tree: cond == -1: the Chow-Liu tree of the columns vars, the maximum spanning tree under the `mi` matrix of
+ *   bn_info_pair_entropies; cond >= 0: the tree of tree-augmented naive Bayes for the class column cond, under the `cmi` matrix of
+ *   bn_info_cond_pair_entropies (the edges class -> feature are the caller's to add).  The weights have those matrices' bits and stay
+ *   on the device between the two kernels.  vars NULL: every column but cond, increasing (m must be their number); root: a column of
+ *   vars, -1: the lowest.  parent_out [m]: the parent COLUMN of vars[i], -1 at the root; weight_out [m]: the matrix entry of the edge
+ *   (vars[i], parent), 0.0 at the root; matrix_out [m][m] (may be NULL): the weights.  Duplicates in vars, cond in vars, root not in
+ *   vars, a column out of range, m <= 0, m > 4096, null outputs: BN_ERR_ARG. */
+int bn_info_cond_pair_entropies(bn_info_table *table, int32_t cond, int32_t m, const int32_t *vars, double *hz_out, double *hxz_out,
+                                double *hxyz_out, double *cmi_out);
+int bn_info_cond_pair_counts(bn_info_table *table, int32_t cond, int32_t n_pairs, const int32_t *pairs, uint64_t *counts_out);
+int bn_tree_max_spanning(int32_t m, const double *w, int32_t root, int32_t device, int32_t *parent_out);
+int bn_learn_tree(bn_info_table *table, int32_t cond, int32_t m, const int32_t *vars, int32_t root, int32_t *parent_out,
+                  double *weight_out, double *matrix_out);
+
 /* ---- log-likelihood of a pattern table under the engine's network ----
  * Replaces: basic_info_criteria::calc_likelihood (bayesian/evaluation/basic_info_criteria.hpp:44-78), the term of
  * bn::evaluation::aic / mdl that depends on the data; calc_parameters (:100-117) is bn_get_info(eng, "parameters")
