@@ -9,7 +9,7 @@ from . import synth  # noqa: F401
 
 _EVALUATION = ("AIC", "MDL", "log_cpt", "log_likelihood_nodes", "log_likelihood_rows", "parameters", "ci_tests", "chisq_sf")
 _LEARNING = ("Greedy", "K2", "Learner", "score_groups", "score_subsets", "BruteForce", "StepwiseStructure", "TermTable",
-             "SimulatedAnnealing", "StepwiseStructureHC", "HillClimbing", "PC", "PCResult", "cpdag_to_dag")
+             "SimulatedAnnealing", "StepwiseStructureHC", "HillClimbing", "OptimalSearch", "PC", "PCResult", "cpdag_to_dag")
 _EM = ("MISSING", "em_expected_counts", "em_fit", "jt_em_fit")
 _INFERENCE = ("GibbsSampling",)
 __all__ = ["Evidence", "FlatModel", "from_parent_lists", "synth", *_EVALUATION, *_LEARNING, *_EM, *_INFERENCE]

@@ -54,6 +54,11 @@ class ClimbParams(ctypes.Structure):
                 ("trace_cap", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
 
 
+class OptimalParams(ctypes.Structure):   # bn_optimal_params
+    _fields_ = [("max_parents", ctypes.c_int32), ("pad_", ctypes.c_int32), ("allowed", ctypes.POINTER(ctypes.c_uint64)),
+                ("pad64_", ctypes.c_uint64)]
+
+
 class EmOptions(ctypes.Structure):   # bn_em_options
     _fields_ = [("max_iters", ctypes.c_int32), ("tol", ctypes.c_double), ("bp_eps", ctypes.c_double), ("bp_max_sweeps", ctypes.c_int32),
                 ("prior", ctypes.c_double)]
@@ -207,6 +212,8 @@ SYMBOLS = [
                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p, i32p]),
     ("bn_learn_climb", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ClimbParams), ctypes.c_int32, ctypes.c_uint64, f64p,
                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, i32p]),
+    ("bn_learn_optimal", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(OptimalParams), f64p, i32p,
+                                        ctypes.POINTER(ctypes.c_uint64)]),
     ("bn_learn_score_groups_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, i32p, i32p, i32p, i32p, i32p,
                                                   f64p, ctypes.POINTER(ctypes.c_uint64)]),
     ("bn_learn_score_subsets_spec", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreSpec), ctypes.c_int32, ctypes.c_int32, i32p,

@@ -160,12 +160,17 @@ extern "C" int bn_learn_get(const bn_learner* L, const char* name, int64_t* out)
     else if (s == "climb_ns") *out = int64_t(L->times.climb_ns);
     else if (s == "climb_runs") *out = L->times.climb_runs;
     else if (s == "climb_steps") *out = L->times.climb_steps;
+    else if (s == "optimal_ns") *out = int64_t(L->times.optimal_ns);
+    else if (s == "optimal_bps_ns") *out = int64_t(L->times.optimal_bps_ns);
+    else if (s == "optimal_sink_ns") *out = int64_t(L->times.optimal_sink_ns);
+    else if (s == "optimal_cells") *out = L->times.optimal_cells;
+    else if (s == "optimal_bytes") *out = L->times.optimal_bytes;
     else if (s == "edges") {
         *out = 0;
         for (const auto& p : L->parents) *out += int64_t(p.size());
     } else if (s == "parameters") *out = L->params;
     else if (s == "criterion") *out = L->criterion;
-    else return fail(BN_ERR_ARG, "unknown name (criterion, families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, hc_ns, hc_runs, hc_merges, climb_ns, climb_runs, climb_steps, edges, parameters)");
+    else return fail(BN_ERR_ARG, "unknown name (criterion, families_scored, passes, count_ns, score_ns, count_bytes, lattice_ns, subsets_scored, anneal_ns, anneal_chains, anneal_steps, hc_ns, hc_runs, hc_merges, climb_ns, climb_runs, climb_steps, optimal_ns, optimal_bps_ns, optimal_sink_ns, optimal_cells, optimal_bytes, edges, parameters)");
     return BN_OK;
 }
 

@@ -2,7 +2,8 @@
 // bn_learn_plan.cpp: the host-only planning of a batch; bn_learn_batch.cpp: run_groups / run_subsets on the device and the
 // bn_learn_score_* entry points; bn_learn.cpp: the bn_learner object and bn_learn_try_parents (reference greedy.hpp, k2_algorithm.hpp);
 // bn_learn_exhaustive.cpp: bn_learn_best_parents and the brute-force searches (brute_force.hpp); bn_learn_terms.cpp: bn_term_table;
-// bn_learn_search.cpp: the device-resident searches over a term table, bn_learn_anneal, bn_learn_hc and bn_learn_climb.
+// bn_learn_search.cpp: the device-resident searches over a term table, bn_learn_anneal, bn_learn_hc, bn_learn_climb and
+// bn_learn_optimal.
 #ifndef BN_LEARN_INTERNAL_HPP
 #define BN_LEARN_INTERNAL_HPP
 #include <cmath>
@@ -31,6 +32,9 @@ struct LearnTimes {
     int64_t hc_runs = 0, hc_merges = 0;
     double climb_ns = 0.0;     // the hill-climbing kernel
     int64_t climb_runs = 0, climb_steps = 0;
+    double optimal_ns = 0.0;   // the exact search's launches; of these, the best-parent-set passes and the best-sink levels
+    double optimal_bps_ns = 0.0, optimal_sink_ns = 0.0;
+    int64_t optimal_cells = 0, optimal_bytes = 0;   // of the last call: n * 2^(n - 1), the device memory it took
 };
 
 // The family term: kind 0 the log-likelihood term (AIC / MDL), 2 BDeu, 3 K2.  Held normalised (ess 0.0 where the kind does not

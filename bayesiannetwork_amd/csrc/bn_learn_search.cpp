@@ -1,11 +1,13 @@
 // bn_learn_search.cpp -- the device-resident structure searches over a term table (bn_learn_terms.cpp): bn_learn_anneal runs the
 // reference's simulated_annealing.hpp as many chains (bn_learn_anneal.hip), bn_learn_hc its stepwise_structure_hc.hpp as many runs
 // (bn_learn_hc.hip), bn_learn_climb tabu hill climbing as many runs (bn_learn_climb.hip).  All begin and end alike (SearchRun): the
-// same checks, buffers and arguments, and the run with the smallest score becomes the learner's graph.
+// same checks, buffers and arguments, and the run with the smallest score becomes the learner's graph.  bn_learn_optimal is the
+// exact search (bn_learn_optimal.hip): no runs, one graph, installed in the learner by the same tail.
 #include "bn_learn_internal.hpp"
 #include "bn_learn_anneal.hpp"
 #include "bn_learn_climb.hpp"
 #include "bn_learn_hc.hpp"
+#include "bn_learn_optimal_plan.hpp"
 
 namespace {
 
@@ -346,5 +348,82 @@ extern "C" int bn_learn_climb(bn_learner* L, bn_term_table* tt, const bn_climb_p
             c[0] = x.steps; c[1] = x.improving; c[2] = x.perturbed; c[3] = x.best_step; c[4] = x.flags; c[5] = x.tabu_legal;
         }
     }
+    return BN_OK;
+}
+
+// ---- the exact search: the DAG of smallest cost by dynamic programming over node subsets (Silander & Myllymaki 2006) --------------
+
+static_assert(sizeof(bn_optimal_params) == 24, "the parameter block is the ABI's");
+
+extern "C" int bn_learn_optimal(bn_learner* L, bn_term_table* tt, const bn_optimal_params* p, double* value_out, int32_t* order_out,
+                                uint64_t* masks_out) {
+    if (!L || !tt || !p) return fail(BN_ERR_ARG, "null argument");
+    if (tt->t != L->t) return fail(BN_ERR_ARG, "optimal: the term table was built from another table than the learner's");
+    if (int r = check_table_spec("optimal", L, tt)) return r;
+    OptimalPlan plan;
+    if (int r = plan_optimal(L->n, p->max_parents, tt->q, L->max_parents, p->allowed, plan)) return r;
+    const int32_t n = L->n;
+    const size_t nn = size_t(n);
+    std::vector<uint64_t> allowed(nn, ~uint64_t(0));
+    if (p->allowed) std::copy(p->allowed, p->allowed + n, allowed.begin());
+    DeviceGuard guard;   // (before the buffers: they are freed on the learner's device)
+    HIPCHK(guard.enter(L->t->device));
+    hipStream_t s = L->t->stream;
+    DeviceBuf<double> d_cost, d_R, d_ll, d_value;
+    DeviceBuf<uint32_t> d_rank;
+    DeviceBuf<uint8_t> d_sink;
+    DeviceBuf<uint64_t> d_allowed, d_masks;
+    DeviceBuf<int32_t> d_order;
+    EventOwner ev[4];
+    int r;
+    if ((r = dalloc(d_cost, size_t(plan.cells))) || (r = dalloc(d_rank, size_t(plan.cells))) || (r = dalloc(d_R, size_t(plan.sets))) ||
+        (r = dalloc(d_sink, size_t(plan.sets))) || (r = dalloc(d_ll, nn)) || (r = dalloc(d_value, 1)) || (r = dalloc(d_masks, nn)) ||
+        (r = dalloc(d_order, nn)) || (r = upload(d_allowed, allowed, s)))
+        return r;
+    for (EventOwner& e : ev) HIPCHK(hipEventCreate(e.put()));
+    auto launched = [](const char* what, int err) {
+        return err ? fail(BN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(hipError_t(err))) : BN_OK;
+    };
+    // step 1: the best parent set inside every candidate set, one launch per pass of the schedule
+    HIPCHK(hipEventRecord(ev[0], s));
+    OptimalBpsArgs b{tt->d_terms, tt->d_tab, tt->T, tt->d_k, d_allowed, n, tt->q, plan.mp, L->criterion < 2 ? 1 : 0, L->penalty, d_cost, d_rank, {}};
+    for (const OptimalPass& pass : plan.passes) {
+        b.pass = pass;
+        if ((r = launched("best-parent-set kernel", learn_launch_optimal_bps(b, s)))) return r;
+    }
+    HIPCHK(hipEventRecord(ev[1], s));
+    // step 2: the best sink of every set, level by level on the stream (R[empty] = +0.0)
+    HIPCHK(hipMemsetAsync(d_R, 0, sizeof(double), s));
+    for (int32_t level = 1; level <= n; ++level)
+        if ((r = launched("best-sink kernel", learn_launch_optimal_sink(OptimalSinkArgs{d_cost, d_R, d_sink, n, level}, s)))) return r;
+    HIPCHK(hipEventRecord(ev[2], s));
+    // step 3: the walk back from V
+    if ((r = launched("backtracking kernel",
+                      learn_launch_optimal_back(OptimalBackArgs{tt->d_terms, tt->d_tab, tt->T, d_rank, d_R, d_sink, n, tt->q, d_order, d_masks, d_ll, d_value}, s))))
+        return r;
+    HIPCHK(hipEventRecord(ev[3], s));
+    std::vector<uint64_t> win_mask(nn);
+    std::vector<double> win_ll(nn);
+    std::vector<int32_t> order(nn);
+    double value = 0.0;
+    HIPCHK(hipMemcpyAsync(win_mask.data(), d_masks, nn * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(win_ll.data(), d_ll, nn * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(order.data(), d_order, nn * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&value, d_value, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float ms_all = 0.0f, ms_bps = 0.0f, ms_sink = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms_all, ev[0], ev[3]));
+    HIPCHK(hipEventElapsedTime(&ms_bps, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_sink, ev[1], ev[2]));
+    L->times.optimal_ns += double(ms_all) * 1e6;
+    L->times.optimal_bps_ns += double(ms_bps) * 1e6;
+    L->times.optimal_sink_ns += double(ms_sink) * 1e6;
+    L->times.optimal_cells = plan.cells;
+    L->times.optimal_bytes = plan.bytes;
+    adopt_winner(L, win_mask, win_ll, 0.0);
+    L->score = L->score_with(-1, 0.0, L->params);   // the learner's own arithmetic on the graph: may differ from `value` in the last bits
+    if (value_out) *value_out = value;
+    if (order_out) std::copy(order.begin(), order.end(), order_out);
+    if (masks_out) std::copy(win_mask.begin(), win_mask.end(), masks_out);
     return BN_OK;
 }

@@ -378,6 +378,29 @@ class Learner:
             out["trace"] = trace[:min(int(out["steps"][int(trace_run)]), cap)].copy()
         return out
 
+    def optimal(self, term_table: "TermTable", max_parents=None, allowed=None) -> dict:
+        """The exact search (bn_learn_optimal): a DAG of the globally smallest sum of family costs within the in-degree bound, by
+        dynamic programming over node subsets; at most 24 nodes.  It becomes this learner's graph; the starting graph is not read.
+        max_parents: the in-degree bound (default and at most the term table's).  allowed: None, per-node lists of the nodes that
+        may be parents, per-node masks (bit u of allowed[v]: u may be a parent of v), an [n][n] adjacency matrix, or a PCResult
+        (its skeleton).  Returns value (the cost of the graph as the search added it up: R[V]), order (a topological order, parents
+        first), masks [n] (bit u of masks[v]: u -> v) and parents (per-node lists)."""
+        self._check_terms(term_table)
+        n = self.n
+        words = None
+        if allowed is not None:
+            words = _allowed_masks(allowed, n)
+        p = _lib.OptimalParams(int(term_table.max_parents if max_parents is None else max_parents), 0,
+                               _p(words, ctypes.c_uint64) if words is not None else None, 0)
+        value = ctypes.c_double()
+        order = np.zeros(max(n, 1), dtype=np.int32)
+        masks = np.zeros(max(n, 1), dtype=np.uint64)
+        _lib.check(_lib.lib().bn_learn_optimal(self._h, term_table._h, ctypes.byref(p), ctypes.byref(value), _p(order, ctypes.c_int32),
+                                               _p(masks, ctypes.c_uint64)))
+        masks = masks[:n]
+        return {"value": value.value, "order": order[:n], "masks": masks,
+                "parents": [[u for u in range(n) if (int(m) >> u) & 1] for m in masks]}
+
     def score(self) -> float:
         out = ctypes.c_double()
         _lib.check(_lib.lib().bn_learn_score(self._h, ctypes.byref(out)))
@@ -398,6 +421,29 @@ class Learner:
     def parents(self):
         ptr, idx = self.structure()
         return [idx[ptr[v]:ptr[v + 1]].tolist() for v in range(self.n)]
+
+
+def _allowed_masks(allowed, n: int) -> np.ndarray:
+    """Learner.optimal's `allowed` as [n] uint64 masks: a PCResult (its skeleton), an [n][n] matrix of marks, per-node lists of
+    node ids, or per-node masks (n integers)."""
+    if hasattr(allowed, "skeleton"):
+        allowed = allowed.skeleton
+    if isinstance(allowed, np.ndarray) and allowed.ndim == 2:
+        if allowed.shape != (n, n):
+            raise ValueError(f"allowed: an [{n}][{n}] matrix")
+        return np.array([sum(1 << u for u in range(n) if allowed[v, u]) for v in range(n)], dtype=np.uint64)
+    if len(allowed) != n:
+        raise ValueError(f"allowed: one entry per node ({n})")
+    words = np.zeros(n, dtype=np.uint64)
+    for v, a in enumerate(allowed):
+        if isinstance(a, (int, np.integer)):
+            words[v] = int(a)
+        else:
+            ids = [int(u) for u in a]
+            if any(not 0 <= u < 64 for u in ids):
+                raise ValueError("allowed: node ids within 0 .. 63")
+            words[v] = sum(1 << u for u in set(ids))
+    return words
 
 
 TRACE_DTYPE = np.dtype([("now_bits", np.uint64), ("method", np.uint8), ("from", np.uint8), ("to", np.uint8), ("accepted", np.uint8),
@@ -741,6 +787,27 @@ class HillClimbing(_TermSearch):
             self.records = L.climb(terms, tabu_len, max_worse, self._runs, perturb, self._next_seed(), max_steps=max_steps)
             out = self._finish(model, L)
             self._note(L, terms, ("climb_ns", "climb_runs", "climb_steps"))
+            return out
+
+
+class OptimalSearch(_TermSearch):
+    """The exact search (Learner.optimal; Silander & Myllymaki's dynamic programming over node subsets, the search of pgmpy's
+    ExhaustiveSearch, not in the reference).  `opt(model, allowed=None)`: the DAG of the globally smallest score within the in-degree
+    bound, returned as (FlatModel with CPTs fitted to it, score); the model's own graph is not read.  At most 24 nodes.  max_parents
+    (default 3) bounds the in-degree: the family terms of every parent set up to it are computed once, into a TermTable kept for the
+    object's lifetime.  allowed: as Learner.optimal's (a PC result's skeleton restricts the search to it).  `records` holds
+    Learner.optimal's result, `last` also the search's counters and the term table's."""
+
+    def __init__(self, criterion, sampling, max_parents: int = 3, device: int = _lib.BN_DEVICE_CURRENT):
+        super().__init__(criterion, sampling, max_parents, 0, device)
+
+    def __call__(self, model, allowed=None):
+        terms = self.term_table(model)
+        with self._learner(model) as L:
+            self.records = L.optimal(terms, allowed=allowed)
+            self.records["winner"] = 0
+            out = self._finish(model, L)
+            self._note(L, terms, ("optimal_ns", "optimal_bps_ns", "optimal_sink_ns", "optimal_cells", "optimal_bytes"))
             return out
 
 

@@ -175,6 +175,23 @@ public:
         return winner;
     }
 
+    // optimal_structure.hpp: the exact search on the learner over a term table of this session's table; the optimal graph REPLACES
+    // the edges of `graph` (the learner's own graph is not read).  allowed: empty, or one mask per node in vertex_list() order.
+    // Returns R[V], the cost of the graph as the search added it up.
+    double optimal(graph_t& graph, std::int32_t max_parents, std::vector<std::uint64_t> const& allowed)
+    {
+        bn_term_table* terms = nullptr;
+        mi355x::engine_handle::check(bn_terms_create_spec(table_.handle(), &spec_, max_parents, &terms));
+        bn_optimal_params const params{max_parents, 0, allowed.empty() ? nullptr : allowed.data(), 0};
+        double value = 0.0;
+        int const rc = bn_learn_optimal(learner_, terms, &params, &value, nullptr, nullptr);
+        bn_terms_destroy(terms);
+        mi355x::engine_handle::check(rc);
+        graph.erase_all_edge();
+        apply_structure(graph);
+        return value;
+    }
+
 private:
     std::vector<std::int32_t> indexes_of(std::vector<vertex_type> const& vs) const
     {

@@ -1025,6 +1025,49 @@ typedef struct bn_climb_trace {
 int bn_learn_climb(bn_learner *L, bn_term_table *terms, const bn_climb_params *params, int32_t runs, uint64_t seed,
                    double *score_out, uint32_t *counts_out, uint64_t *masks_out, bn_climb_trace *trace_out, int32_t *winner_out);
 
+/* ---- exact structure learning: the DAG of globally smallest cost by dynamic programming over node subsets (Silander & Myllymaki
+ *      2006; the search of pgmpy's ExhaustiveSearch; NOT IN THE REFERENCE). ----
+ *
+ *   bn_learn_optimal finds, over a bn_term_table built on the learner's table and of the learner's score spec, a DAG whose sum of
+ *   family costs is the smallest any DAG within the bounds has, and makes it the learner's graph.  The learner's starting graph is
+ *   not read.  1 <= n <= 24.  In-degree bound mp = min(params.max_parents, the term table's q, the learner's max_parents).
+ *   allowed: NULL, or [n] masks: bit u of allowed[v] set means u may be a parent of v; bit v of allowed[v] is ignored.
+ *   Family cost of child v with parent set S:  f(v, S) = (0.0 - ll(v, S)) + double(dp) * penalty,  dp = (k_v - 1) * rows(S) an exact
+ *   int64, penalty 1.0 under AIC and log2(N) / 2 under MDL; under BDeu / K2 f(v, S) = 0.0 - term and no more.  Every step one plain
+ *   fp64 operation (no fused multiply-add).  f is +inf where the term is NaN (not eligible), where |S| > mp, and where S is not
+ *   inside allowed[v]; the empty set is always eligible.
+ *   Step 1, for every v and every C inside V \ {v}:  bps[v][C] = min over S inside C of (f(v, S), rank(v, S)), compared
+ *     lexicographically: the smaller cost, among equal costs the smaller term-table rank.  C is indexed by its mask with bit v
+ *     squeezed out, c = (C & ((1 << v) - 1)) | ((C >> (v + 1)) << v), the rank tables' relabelling s' = s - (s > v).  Made as a
+ *     min-zeta transform: the cell of S starts as (f, rank) where |S| <= mp and as (+inf, 0xFFFFFFFF) otherwise, then for each of the
+ *     n - 1 bits b, g[c] = min(g[c], g[c ^ (1 << b)]) for every c with bit b set.  min does not round and the order is total: the
+ *     result does not depend on the order of the bits or of the cells.
+ *   Step 2:  R[empty] = +0.0;  for W not empty, R[W] = min over v in W, v ascending, of R[W \ v] + bps[v][squeeze(W \ v)].cost, one
+ *     fp64 add per term; the first v starts the minimum and a STRICTLY smaller value replaces it, so among equals the lowest v stays;
+ *     sink[W] = that v.
+ *   Step 3:  W = V;  for i = n - 1 .. 0:  s = sink[W], order_out[i] = s, W ^= 1 << s, the parents of s are the set of rank
+ *     bps[s][squeeze(W)].rank.
+ *   Outputs (each may be NULL): value_out = R[V]; order_out [n] a topological order, parents first; masks_out [n] the parent masks
+ *   (bit u of word v: u -> v).  The learner's graph, terms and parameter count become the result's, as after bn_learn_climb:
+ *   bn_learn_structure / bn_learn_terms work as usual and bn_learn_score is the learner's stated score of that graph (node-order sum
+ *   plus penalty on the summed parameter count).  That is another order of additions than R[V]'s: the two may differ in the last
+ *   bits.
+ *   Arguments (BN_ERR_ARG, the text names the limit; checked before any allocation or launch, the learner stays as it was): a null
+ *   pointer; a term table built on another table or of another spec (as bn_learn_anneal); n outside 1 .. 24; max_parents < 1; a bit
+ *   at or above n in a word of allowed.  Memory: n * 2^(n - 1) cells of 12 bytes and 2^n sets of 9 (2.4 GB at n = 24), allocated
+ *   for the call and freed when it returns; an allocation that fails returns BN_ERR_HIP with the runtime's out-of-memory text and
+ *   leaves the learner unchanged.  Runs on the table's stream, one launch per pass of step 1, per level of step 2 and for step 3,
+ *   with no host wait in between.  bn_learn_get also names "optimal_ns" (device time of all launches, summed over the calls),
+ *   "optimal_bps_ns" and "optimal_sink_ns" (steps 1 and 2 of it), and of the last call "optimal_cells" (n * 2^(n - 1)) and
+ *   "optimal_bytes" (the device memory of the four tables). */
+typedef struct bn_optimal_params {
+    int32_t max_parents, pad_;
+    const uint64_t *allowed;   /* NULL, or [n] */
+    uint64_t pad64_;
+} bn_optimal_params;
+int bn_learn_optimal(bn_learner *L, bn_term_table *terms, const bn_optimal_params *params, double *value_out, int32_t *order_out,
+                     uint64_t *masks_out);
+
 /* ---- Bayesian-Dirichlet scores: BDeu and K2 (Cooper-Herskovits) as family terms of every search above ----
  *
  *   A bn_score_spec names the family term: kind 0 the log-likelihood term ll above (used with AIC / MDL), kind 2 BDeu with the
